@@ -17,6 +17,12 @@ Contract: python bench.py --gpus N --steps K --warmup W
     as a CHILD (it never touches the GPU itself) and exits with the child's code;
   * under torchrun (RANK / LOCAL_RANK / WORLD_SIZE set) it is one rank of N.
 Rank 0 prints ONE JSON line.
+
+A plain run times the headline alone: set-up, --warmup passes, --steps timed passes, the line.  --full adds everything
+else the line used to carry: CPU baselines and oracle parity, PYP's default search, the executables (`dropin`), and the
+`reconstruct` / `csp` / `sva` blocks with their side figures.  --dump-outputs DIR writes what the timed calls of the last
+step returned (DIR/<name>.npy, float32 / float64, at most 64 MB in all); the inputs are seeded, so two builds compare
+output for output.
 """
 import argparse
 import json
@@ -53,7 +59,7 @@ def parse(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target wall time of each CPU oracle leg (0 = skip)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--workload", choices=["both", "refine", "reconstruct", "csp", "sva"], default="both",
-                    help="both = the refinement line (BASELINE.json configs[1], the headline metric) carrying a 'reconstruct' block "
+                    help="both = the refinement line (BASELINE.json configs[1], the headline metric), with --full carrying a 'reconstruct' block "
                          "(configs[2]) and the two next-row blocks 'csp' (configs[3]: constrained tilt-series refinement) and 'sva' "
                          "(configs[4]: sub-tomogram alignment); refine / reconstruct / csp / sva = that workload alone")
     ap.add_argument("--csp-particles", type=int, default=500, help="particles of the tilt series of the csp block (41 tilts, 128^2 boxes)")
@@ -62,7 +68,16 @@ def parse(argv=None):
     ap.add_argument("--no-side", action="store_true", help="csp / sva blocks: only the timed figure (no second series in flight, no global search, no average) - what the "
                                                            "counter passes of scripts/pmc_r04.sh profile, so that a kernel's dispatches are those of the timed calls")
     ap.add_argument("--no-dropin", action="store_true", help="leave the 'dropin' block (bin/refine3d + bin/reconstruct3d as child processes on a stack file) out")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="everything besides the timed figure: CPU baselines and oracle parity, the default_search and dropin "
+                                                        "blocks, the reconstruct / csp / sva blocks of the default line and their side figures (the --no-* "
+                                                        "options above then leave parts out); without it a run does what --no-cpu --no-side --no-dropin "
+                                                        "--no-next-rows do and the default line is the refinement alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed calls of the last step returned as "
+                                                                        "DIR/<name>.npy (float32 / float64; seeded row samples beyond 64 MB in all)")
+    a = ap.parse_args(argv)
+    if not a.full:              # a plain run: the headline figure and nothing else
+        a.no_cpu = a.no_side = a.no_dropin = a.no_next_rows = True
+    return a
 
 
 # --------------------------------------------------------------------------------------------- launcher
@@ -367,13 +382,13 @@ def main(argv=None):
             dist.init_process_group("nccl", device_id=torch.device("cuda", local))
         else:
             dist.init_process_group(backend)
-    ctx = dict(a=a, rank=rank, world=world, local=local, dev=torch.device("cuda", local), px=1.0)
+    ctx = dict(a=a, rank=rank, world=world, local=local, dev=torch.device("cuda", local), px=1.0, outputs={})
     from pyp_amd import synth
     ctx["vol"] = synth.phantom(a.box)
     line = None
     if a.workload in ("both", "refine"):
         line = refine_bench(ctx)
-    if a.workload in ("both", "reconstruct"):
+    if a.workload == "reconstruct" or (a.workload == "both" and a.full):
         rec = reconstruct_bench(ctx)
         if rank == 0:
             if line is None:
@@ -389,6 +404,8 @@ def main(argv=None):
                 else:
                     line[name] = blk
     if rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, ctx["outputs"])
         line["summary"] = summary_of(line)          # LAST key: the figures a reader of the line's tail needs
         print(json.dumps(line))
     if world > 1:
@@ -433,6 +450,26 @@ def summary_of(line):
             s[name] = {"value": b.get("value"), "unit": b.get("unit"), "roofline_frac": pick(b, "roofline", "frac"),
                        "parity_vs_oracle": par(b.get("parity_vs_oracle")) or pick(b, "parity_vs_oracle", "max_deg")}
     return s
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy, in float32 when it is float32 (or narrower), else in float64.  Beyond 64 MB in all,
+    every array keeps the same share of its rows, picked with a fixed seed and kept in order: runs with the same arguments write
+    the same rows."""
+    os.makedirs(d, exist_ok=True)
+    arrs = {}
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        arrs[k] = v.astype(np.float32 if v.dtype.kind == "f" and v.dtype.itemsize <= 4 else np.float64, copy=False)
+    total = sum(x.nbytes for x in arrs.values())
+    keep = min(1.0, DUMP_BYTES / total) if total else 1.0
+    for k, x in arrs.items():
+        if keep < 1.0 and x.ndim and len(x) > 1:
+            x = x[np.sort(np.random.default_rng(0).choice(len(x), max(1, int(len(x) * keep)), replace=False))]
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(x))
 
 
 def make_barrier(world):
@@ -491,6 +528,8 @@ def refine_bench(ctx):
         out = ref.refine(cfg, stack, start_rows)
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0, world, dev)
+    if a.dump_outputs:
+        ctx["outputs"]["refine_rows"] = out                # the rows ppm_refine_batch returned in the last timed step
     prof = host.profile_report()
     host.profile(False, False)
     counts = ref.last_counts()
@@ -793,6 +832,12 @@ def reconstruct_bench(ctx):
     dt = max_over_ranks(time.perf_counter() - t0, world, dev)
     prof = host.profile_report()
     host.profile(False, False)
+    if a.dump_outputs:
+        # the reduced half-map accumulators of the last timed step: a fixed, seeded sample of 2 M of their floats, and the particle counts
+        idx = np.unique(np.random.default_rng(0).integers(0, nfl, 1 << 21))
+        ctx["outputs"]["reconstruct_accumulator_sample"] = acc_t[torch.as_tensor(idx, device=dev)].cpu().numpy()
+        ctx["outputs"]["reconstruct_accumulator_sample_index"] = idx
+        ctx["outputs"]["reconstruct_counts"] = np.array(counts, dtype=np.float64)
     if rank != 0:
         acc.close()
         return None
@@ -1071,6 +1116,9 @@ def csp_bench(ctx):
         out = ref.csp_refine(cfg, cc, stack, rows2, p2, tilts)
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0, world, dev)
+    if a.dump_outputs:
+        for k, v in zip(("rows", "particles", "tilts"), out):          # what ppm_csp_refine returned in the last timed step
+            ctx["outputs"]["csp_" + k] = v
     prof = host.profile_report()
     host.profile(False, False)
     lc_csp = ref.last_counts()
@@ -1225,6 +1273,8 @@ def sva_bench(ctx):
         out, sc = ref.sva_align(cfg, vols, wedges, start)
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0, world, dev)
+    if a.dump_outputs:
+        ctx["outputs"]["sva_poses"], ctx["outputs"]["sva_scores"] = out.copy(), sc.copy()      # ppm_sva_align's answer in the last timed step
     prof = host.profile_report()
     host.profile(False, False)
     lc_sva = ref.last_counts()          # of the last timed alignment call

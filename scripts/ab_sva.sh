@@ -5,5 +5,5 @@ for round in 1 2; do
     echo "== blocks per CU $bpc round $round | sva $s"
   done
 done
-s=$(timeout -k 10 300 python bench.py --workload sva --sva-volumes 512 --steps 2 --warmup 1 --no-cpu 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); d=d.get('sva',d); print(d['value'], d['device_ms_per_sub_volume'], d['global_search']['value'], d['average']['value'], d['streamed']['value'], d['parity_vs_oracle'] if 'parity_vs_oracle' in d else '')")
+s=$(timeout -k 10 300 python bench.py --workload sva --sva-volumes 512 --steps 2 --warmup 1 --no-cpu --full 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); d=d.get('sva',d); print(d['value'], d['device_ms_per_sub_volume'], d['global_search']['value'], d['average']['value'], d['streamed']['value'], d['parity_vs_oracle'] if 'parity_vs_oracle' in d else '')")
 echo "== default, with side figures | $s"

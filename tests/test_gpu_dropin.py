@@ -2,11 +2,13 @@
 shell here-docs of positional answers, particle ranges fanned out, range files merged, dumps merged
 (src/pyp/refine/frealign/frealign.py:3014-3193, :1622-1835, :1838-1903, :1910-2175)."""
 import os
+import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import sockdir
 from pyp_amd import synth
 from pyp_amd.formats import cistem, mrc, parfile
 
@@ -405,7 +407,7 @@ def test_bench_two_ranks_share_one_gpu_over_gloo():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(PPM_FORCE_DEVICE="0", PPM_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--box", "64",
-                        "--band", "24", "--particles", "512", "--recon-particles", "1024", "--no-cpu"],
+                        "--band", "24", "--particles", "512", "--recon-particles", "1024", "--no-cpu", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -561,14 +563,15 @@ def test_native_executables_end_with_error_when_an_upload_fails(project, monkeyp
     assert not any((d / o).exists() for o in outs)
 
 
-def test_resident_server_keeps_the_stack_and_the_reference_between_calls(project, monkeypatch, tmp_path):
+def test_resident_server_keeps_the_stack_and_the_reference_between_calls(project, monkeypatch):
     """PPM_STACK_CACHE=1 (pyp_amd/csrc/dropin_server.h): the executables are clients of bin/ppm_server.  An iteration as PYP runs it -
     reconstruct3d, then refine3d, then reconstruct3d again over the same stack - uploads the range once: the later calls find it
     resident (and refine3d's second call finds its reference prepared).  Files equal those of the one-shot executables; a stack
     that changes on disk is uploaded again; --stop frees the device."""
     d, vol, imgs, truth, start = project
     server = os.path.join(BIN, "ppm_server")
-    monkeypatch.setenv("PPM_LOCK_DIR", str(tmp_path))
+    lockdir = sockdir.short_dir()                            # not tmp_path: the socket's path must fit a unix socket address
+    monkeypatch.setenv("PPM_LOCK_DIR", lockdir)
     used = truth.copy()
     used[:, cistem.COL["SCORE"]] = 20.0
     cistem.write_parameters(str(d / "s_used.cistem"), used)
@@ -627,4 +630,5 @@ def test_resident_server_keeps_the_stack_and_the_reference_between_calls(project
     finally:
         r = subprocess.run([server, "--stop"], capture_output=True, text=True, timeout=60)
         mrc.write(imgs, str(d / "p_stack.mrc"), pixel_size=PX)                          # the module's fixture as it was
+        shutil.rmtree(lockdir, ignore_errors=True)
     assert "stopping" in r.stdout

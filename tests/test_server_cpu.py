@@ -1,12 +1,15 @@
 """The resident per-GPU server behind the compiled executables (pyp_amd/csrc/dropin_server.h, bin/ppm_server; SURVEY.md 8b "multiplex via a
 daemon"): life cycle and protocol on a host without a GPU.  The compute paths are covered by tests/test_gpu_dropin.py on the GPU box."""
 import os
+import pathlib
+import shutil
 import subprocess
 import time
 
 import numpy as np
 import pytest
 
+import sockdir
 from pyp_amd.formats import cistem, mrc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,11 +26,14 @@ def _built(prog):
 
 
 @pytest.fixture()
-def lockdir(tmp_path, monkeypatch):
-    monkeypatch.setenv("PPM_LOCK_DIR", str(tmp_path / "lock"))
-    (tmp_path / "lock").mkdir()
-    yield tmp_path / "lock"
-    subprocess.run([SERVER, "--stop"], capture_output=True, timeout=30)          # whatever a test left running
+def lockdir(monkeypatch):
+    d = pathlib.Path(sockdir.short_dir())                   # not tmp_path: the socket's path must fit a unix socket address
+    monkeypatch.setenv("PPM_LOCK_DIR", str(d))
+    yield d
+    try:
+        subprocess.run([SERVER, "--stop"], capture_output=True, timeout=30)          # whatever a test left running
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
 
 
 def test_server_starts_reports_and_stops(lockdir):
