@@ -96,6 +96,7 @@ struct PrepP {
     const float *images; const double *rows; FftPlan plan;
     int N, B, W, H;
     float r_hi2, Rm, wfall, a;
+    float Rm2_bg;     // background statistics: pixels with integer r^2 > Rm2_bg = floor(Rm^2 in double), as the oracle's double test
     float focus[4];   // focus mask: sphere centre (pixels from the box centre) and radius in the reference; radius <= 0: centred mask of radius Rm
     int normalize, invert, do_mask, whiten;
     int nc, nchunks, L;
@@ -150,7 +151,7 @@ __global__ void __launch_bounds__(PT, MINW) k_prep(PrepP P) {
 
     // ---- statistics of the background (outside the mask radius); whole image if that is empty
     double s1 = 0, s2 = 0, cnt = 0, t1 = 0, t2 = 0;
-    const float Rm2 = P.Rm * P.Rm;
+    const float Rm2 = P.Rm2_bg;
     // scratch-free path without a mask: (x - mu) sc only changes the DC term (never used) and the scale, so the statistics are
     // gathered while the pixels are staged for the row transforms and the scale is applied to the band output: one image read
     const bool fold = inreg && !P.do_mask;

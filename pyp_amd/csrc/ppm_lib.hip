@@ -298,7 +298,7 @@ static int build_brick_items(ppm_accum *a, const Geom &gm, int BE, int nb) {
 }
 
 // ------------------------------------------------------------------------------ pre-processing launch
-static int launch_prep(DevBuf<float2> &spill /* the calling handle's scratch */, const float *d_images, const double *d_rows, int n_img, const Geom &gm, float Rm_px, float fall_px,
+static int launch_prep(DevBuf<float2> &spill /* the calling handle's scratch */, const float *d_images, const double *d_rows, int n_img, const Geom &gm, double Rm_px, float fall_px,
                        int normalize, int invert, int do_mask, int whiten, float2 *band, float *wring,
                        const uint32_t *samples, int S_pad, float2 *Il, float *cw, float2 *Wp, float *C2, float *nI,
                        unsigned *band_max = nullptr /* insertion: receives the chunk's largest |band| component */,
@@ -307,7 +307,10 @@ static int launch_prep(DevBuf<float2> &spill /* the calling handle's scratch */,
     PrepP P;
     P.images = d_images; P.rows = d_rows; P.plan = g.plans[gm.N].plan;
     P.N = gm.N; P.B = gm.B; P.W = gm.W; P.H = gm.H;
-    P.r_hi2 = (float)(gm.r_hi * gm.r_hi); P.Rm = Rm_px; P.wfall = fall_px; P.a = (float)gm.a;
+    P.r_hi2 = (float)(gm.r_hi * gm.r_hi); P.Rm = (float)Rm_px; P.wfall = fall_px; P.a = (float)gm.a;
+    // background pixels: r^2 > Rm^2 taken in double (an integer r^2 exceeds the double Rm^2 exactly when it exceeds its floor); a
+    // float Rm^2 rounds radii like 0.4 N px / px onto the integer r^2 of a pixel ring and drops that ring from the statistics
+    P.Rm2_bg = (float)std::min(std::floor(Rm_px * Rm_px), 16777216.0);
     P.normalize = normalize; P.invert = invert; P.do_mask = do_mask; P.whiten = whiten;
     for (int k = 0; k < 4; k++) P.focus[k] = focus_px ? focus_px[k] : 0.f;
     // LDS plan: L row pairs per row pass (L N <= 8 x threads: the next pass is prefetched into <= 8 register pairs per
@@ -784,7 +787,8 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
     // best hit continues at the full band (Tc iterations).  iters_hit < 0: hits stay at their grid points (test hook).
     const int Tb = cfg->iters_hit > 0 ? cfg->iters_hit : (cfg->iters_hit < 0 ? 0 : 2), Tc = cfg->iters_final > 0 ? cfg->iters_final : 7;
     const double fall = cfg->mask_falloff > 0 ? cfg->mask_falloff : 20.0;
-    const float fall_px = (float)(fall / gm.a), Rm_px = (float)(cfg->mask_radius / gm.a);
+    const float fall_px = (float)(fall / gm.a);
+    const double Rm_px = cfg->mask_radius / gm.a;
     const bool focus_on = cfg->focus[3] > 0.f;     // a focus mask replaces the centred masks of both stages
     const float focus_px[4] = { (float)(cfg->focus[0] / gm.a), (float)(cfg->focus[1] / gm.a), (float)(cfg->focus[2] / gm.a), (float)(cfg->focus[3] / gm.a) };
     const bool sep_search = !focus_on && cfg->global_search && cfg->search_mask_radius > 0 && cfg->search_mask_radius != cfg->mask_radius;
@@ -1020,7 +1024,7 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
                                  ref->samples.p, S_pad, ref->Il.p, ref->cw.p,
                                  (cfg->global_search && !sep_search) ? ref->Wp.p : nullptr, ref->C2.p, ref->nI.p, nullptr, focus_on ? focus_px : nullptr)) return rc;
         if (sep_search)
-            if (int rc = launch_prep(ref->spill, d_img, ref->rows_in.p, nb, gm, (float)(cfg->search_mask_radius / gm.a), fall_px, cfg->normalize, cfg->invert, 1, 1,
+            if (int rc = launch_prep(ref->spill, d_img, ref->rows_in.p, nb, gm, cfg->search_mask_radius / gm.a, fall_px, cfg->normalize, cfg->invert, 1, 1,
                                      ref->band.p, nullptr, nullptr, 0, nullptr, nullptr, ref->Wp.p, ref->C2.p, ref->nI.p)) return rc;
         LState *final_states = ref->states2.p;
         if (cfg->global_search) {
@@ -1241,7 +1245,7 @@ int ppm_insert_batch(ppm_accum_t *a, const ppm_recon_cfg *cfg, const void *image
         const float *d_img = images_on_device ? (const float *)images + (size_t)c0 * NN : a->images.p + (size_t)(ci & 1) * CH * NN;
         // the chunk's value bounds ([0] max |band| from k_prep, [1] max weight from k_insert_params) scale the fixed point
         HIPCHK(hipMemsetAsync(a->d_max, 0, 2 * sizeof(unsigned), cur_stream()));
-        if (int prc = launch_prep(a->spill, d_img, a->rows.p, nb, gm, cfg->mask_radius / cfg->pixel_size, 1.f, cfg->normalize, cfg->invert, 0, 0,
+        if (int prc = launch_prep(a->spill, d_img, a->rows.p, nb, gm, (double)cfg->mask_radius / (double)cfg->pixel_size, 1.f, cfg->normalize, cfg->invert, 0, 0,
                                   a->band.p, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, a->d_max)) return prc;
         // per-particle constants, then one block per (brick, particle slice, half)
         if (int r = a->pp.ensure(nb)) return r;
@@ -1467,7 +1471,9 @@ int ppm_finalize(ppm_accum_t *a, const ppm_final_cfg *cfg, float *half1, float *
     HIPCHK(t_tmp.alloc(nf));
     HIPCHK(t_s.alloc((size_t)8 * ns));
     float *tmp = t_tmp.p; double *d_s = t_s.p;
-    HIPCHK(hipMemset(d_s, 0, 8 * ns * sizeof(double)));
+    // every device step of the finalisation is ordered on the handle's stream: the stream is non-blocking, so a plain hipMemset / hipMemcpy
+    // (legacy null stream) is not ordered against the kernels below and the shell sums could start from a buffer not yet zeroed
+    HIPCHK(hipMemsetAsync(d_s, 0, 8 * ns * sizeof(double), cur_stream()));
     HIPCHK(hipMemcpyAsync(tmp, a->acc, nf * sizeof(float), hipMemcpyDeviceToDevice, cur_stream()));
     {
     ProfScope ps(PPM_K_FINAL);
@@ -1493,7 +1499,7 @@ int ppm_finalize(ppm_accum_t *a, const ppm_final_cfg *cfg, float *half1, float *
             s[4] = fc / (fc + vfrac * (1 - fc)); s[5] = md > 0 ? rec / md / vfrac : 0; s[6] = rec;
         }
     }
-    HIPCHK(hipMemcpy(d_s, kap.data(), ns * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpyAsync(d_s, kap.data(), ns * sizeof(double), hipMemcpyHostToDevice, cur_stream()));     // kap outlives the syncs below
     HIPCHK(t_f.alloc(n3));
     HIPCHK(t_out.alloc(n3));
     float2 *d_f = t_f.p; float *d_out = t_out.p;
@@ -1581,7 +1587,7 @@ extern "C" int ppm_csp_refine(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const p
             HIPCHK(hipMemcpyAsync(img.p, (const float *)images + (size_t)c0 * NN, (size_t)nb * NN * sizeof(float), hipMemcpyHostToDevice, cur_stream()));
             d_img = img.p;
         }
-        if (int rc = launch_prep(ref->spill, d_img, d_rows.p + (size_t)c0 * PPM_NCOL, nb, gm, (float)rm_px, (float)(fall / gm.a), cfg->normalize, cfg->invert, 1, 1,
+        if (int rc = launch_prep(ref->spill, d_img, d_rows.p + (size_t)c0 * PPM_NCOL, nb, gm, rm_px, (float)(fall / gm.a), cfg->normalize, cfg->invert, 1, 1,
                                  band.p, mode4 ? wring.p + (size_t)c0 * (gm.B + 2) : nullptr, ref->samples.p, S_pad, Il.p + (size_t)c0 * S_pad, cw.p + (size_t)c0 * S_pad, nullptr, nullptr, nullptr)) return rc;
         if (!images_on_device) HIPCHK(hipStreamSynchronize(cur_stream()));     // the staging buffer is reused by the next chunk
     }

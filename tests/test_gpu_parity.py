@@ -537,6 +537,16 @@ def test_errors_are_loud(d64, H):
         H.Reference(np.zeros((32, 32, 16), np.float32))
 
 
+def assert_stats_match(want, got):
+    """All 7 statistics columns: shell, resolution and radius are the same double arithmetic on both sides; FSC and part-FSC
+    are ratios of float32-stored sums (1e-4 absolute); part-SSNR and rec-SSNR carry 1 / (1 - FSC), which multiplies that
+    round-off by up to 1e3 near the 0.999 clip, so they are compared relative to max(1, |value|) at 1e-3."""
+    assert want.shape == got.shape
+    assert np.array_equal(want[:, :3], got[:, :3])
+    assert np.abs(want[:, 3:5] - got[:, 3:5]).max() < 1e-4
+    assert (np.abs(want[:, 5:7] - got[:, 5:7]) / np.maximum(np.abs(want[:, 5:7]), 1.0)).max() < 1e-3
+
+
 @pytest.mark.parametrize("sym", ["C1", "D2", "O"])
 def test_insertion_and_finalise_match_oracle(H, O, sym):
     n, px, m = 64, 2.0, 40
@@ -560,6 +570,7 @@ def test_insertion_and_finalise_match_oracle(H, O, sym):
     for a, b in ((w1, g1), (w2, g2), (wf, gf)):
         assert np.linalg.norm(a - b) / np.linalg.norm(a) < 1e-4
     assert np.abs(ws[:, 3:5] - gs[:, 3:5]).max() < 1e-4                  # FSC, part-FSC
+    assert_stats_match(ws, gs)
 
 
 def test_dose_weighted_insertion_matches_oracle(H, O):
@@ -600,6 +611,7 @@ def test_insertion_non_power_of_two_box(H, O, n):
     g = ga.finalize(fc)
     for a, b in zip(w[:3], g[:3]):
         assert np.linalg.norm(a - b) / np.linalg.norm(a) < 1e-4
+    assert_stats_match(w[3], g[3])
 
 
 @pytest.mark.parametrize("n,px,m,sym,minp", [(256, 1.0, 24, "C1", "4"), (160, 1.5, 12, "C2", None), (128, 2.0, 600, "C1", "64"),
