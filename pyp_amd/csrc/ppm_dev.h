@@ -337,11 +337,7 @@ __device__ __forceinline__ CubeTaps cube_fetch_tab(const CubeView &cv, const Cub
     t.fx = __builtin_amdgcn_fractf(X); t.fy = __builtin_amdgcn_fractf(Y); t.fz = __builtin_amdgcn_fractf(Z);
     const unsigned xl = tb.tx0[floor_to_int(X)];
     const uint2 ey = tb.ty0[floor_to_int(Y)], ez = tb.tz0[floor_to_int(Z)];
-#ifdef PPM_DBG_SMALLCUBE
-    const unsigned oa = (xl + ey.x + ez.x) & 0x3ff0u, ob = (oa + ey.y) & 0x3ff0u, oc = (oa + ez.y) & 0x3ff0u, od = (ob + ez.y) & 0x3ff0u;
-#else
     const unsigned oa = xl + ey.x + ez.x, ob = oa + ey.y, oc = oa + ez.y, od = ob + ez.y;
-#endif
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)cv.cube, 0, (int)(2u * cv.LB * 8u), 0x00020000);
     const cube_v4f a = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)oa, 0, 0), b = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)ob, 0, 0);
     const cube_v4f c = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)oc, 0, 0), d = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)od, 0, 0);

@@ -103,7 +103,7 @@ struct PrepP {
     float2 *band;  // [n][H*W] unscaled band spectrum (scratch; the final result for insertion)
     int TS, WS;    // line strides of the column buffer T and of the row work buffer Wk (>= 272 on the 256 fast path)
     int fast256;   // N == 256: register-level 16 x 16 FFT (lds_fft256), natural-order staging
-    int inreg;     // N == 256, k_prep<512, 2> only: the half spectrum stays in registers between the two phases (no global scratch)
+    int inreg;     // N == 256 (k_prep<512, 2>): the half spectrum stays in registers between the two phases (no global scratch)
     unsigned *band_max; // may be null: bits of max |re|, |im| over the band images of the launch (atomicMax; floats >= 0)
     float2 *spill; // [n][N][W] row-transformed half spectrum (global scratch between the row and the column phase)
     float *wring;  // [n][B+2] ring weights 1/sqrt(mean power), may be null
@@ -113,19 +113,23 @@ struct PrepP {
     float2 *Wp; float *C2; float *nI; int Bs, Hs; float r_s2, r_lo2;
 };
 
-// PT = 512 threads and <= 80 KB of LDS: two blocks per CU, so that one block's global-memory waits (image reads, the
-// spilled half spectrum) overlap the other's FFT work; PT = 1024 / 160 KB is kept for comparison (PPM_PREP_PT).
-// MINW = waves per SIMD the register allocation has to leave room for: 4 with PT = 512 makes two blocks per CU resident
-// (128 VGPRs, some spills), 1 lets the compiler keep everything in registers (one block per CU)
+// Two shapes (launch_prep, ppm_lib.hip), PT threads and MINW waves per SIMD the register allocation has to leave room for:
+//   k_prep<512, 2>  N = 256, the scratch-free path: one block per CU holds the half spectrum in registers between the row and
+//                   the column phase, 16 x 16 register FFTs (lds_fft256), natural-order staging;
+//   k_prep<256, 3>  every other box, the scratch path: the half spectrum goes through a global scratch, mixed-radix FFTs on the
+//                   plan's staging order; <= 40 KB of LDS and 168 VGPRs make three blocks per CU resident, so that one block's
+//                   barrier and global-memory waits overlap the others' FFT work.
+// The path is still taken from P.inreg / P.fast256 at run time (both are "N == 256"); the body is the one the shapes were tuned with.
 template <int PT, int MINW>
 __global__ void __launch_bounds__(PT, MINW) k_prep(PrepP P) {
+    static_assert((PT == 512 && MINW == 2) || (PT == 256 && MINW == 3), "the two shapes launch_prep plans for");
     constexpr int PW = PT / 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, N = P.N, B = P.B, W = P.W, H = P.H;
     const int p = blockIdx.x;
     const int TS = P.TS, WS = P.WS;                   // padded line strides (bank spread)
     float2 *T = (float2 *)smem;                       // [nc][TS] column chunk, followed by
-    constexpr bool kInreg = (PT == 512 && MINW == 2) || (PT == 1024 && MINW == 1);   // the instantiations that carry the scratch-free path
+    constexpr bool kInreg = PT == 512;                // the instantiation that carries the scratch-free path
     constexpr int HR = PT / 128, NIT = 64 / (HR > 0 ? HR : 1);   // scratch-free path: thread t holds column t & 127 of the rows (t >> 7) + HR it, it < NIT, of every row pass
     const bool inreg = kInreg && P.inreg;
     float2 *Wk = inreg ? T : T + (size_t)P.nc * TS;   // [L][WS]  the row work buffer (shares T's storage on the scratch-free path)

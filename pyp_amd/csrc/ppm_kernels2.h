@@ -161,11 +161,7 @@ __device__ __forceinline__ void sweep_plan(SweepPlan &plan, const SweepCtx &C, c
     const int lane = tid & 63, wave = tid >> 6, nw = C.nw, nr = C.nr;
     float *const ringA = C.ringA, *const sumB = C.sumB, *const sumC = C.sumC; double *const score = C.score;
     const float2 *const Il = C.Il; const float *const cw = C.cw; const float invN = C.invN;
-#ifdef PPM_DBG_NOSWEEP
-    const int nslots = plan.nslots, ng = plan.ng, S_used = 0;
-#else
     const int nslots = plan.nslots, ng = plan.ng, S_used = plan.S_used;
-#endif
     const float rmax2 = plan.rmax2;
     for (int i = tid; i < nslots * nw * nr; i += nthr) ringA[i] = 0.f;
     if (tid < kMaxCand * nw) sumB[tid] = 0.f;
@@ -204,12 +200,6 @@ __device__ __forceinline__ void sweep_plan(SweepPlan &plan, const SweepCtx &C, c
             else { CubeView one = C.cv; one.scale = 1.f; return cube_fetch(one, X, Y, Z); }
         };
         const bool mine = head && ring < nr;
-        // timing probe (results are wrong; scripts/ab_local.sh): PPM_DBG_NOATOM keeps the sums alive without LDS traffic
-#if defined(PPM_DBG_NOATOM)
-        auto ring_add = [&](float *cell, float v) { accC += 1e-30f * v; };
-#else
-        auto ring_add = [&](float *cell, float v) { atomicAdd(cell, v); };
-#endif
         float *const cellA = myA + ring;
         auto score_group = [&](int g, const CubeTaps &t) {
             const float2 v = cube_interp(t);
@@ -225,17 +215,17 @@ __device__ __forceinline__ void sweep_plan(SweepPlan &plan, const SweepCtx &C, c
                 bv += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(bv), 0x141, 0xF, 0xF, true));
                 av += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(av), 0x140, 0xF, 0xF, true));
                 bv += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(bv), 0x140, 0xF, 0xF, true));
-                if (mine) { ring_add(cellA + q0 * strideA, av); ring_add(myB + q0 * nw, bv); }
+                if (mine) { atomicAdd(cellA + q0 * strideA, av); atomicAdd(myB + q0 * nw, bv); }
                 return;
             }
             const float bv = group16_sum_dpp(n2);
-            if (mine) ring_add(myB + q0 * nw, bv);
+            if (mine) atomicAdd(myB + q0 * nw, bv);
             for (int k = 0; k < nv; k++) {
                 const int q = q0 + k;
                 float bx = b0x, by = b0y;
                 if (q > q_same) turned(q, bx, by);                   // a shifted probe (wave-uniform branch)
                 const float av = group16_sum_dpp(bx * v.x + by * v.y);
-                if (mine) ring_add(cellA + q * strideA, av);
+                if (mine) atomicAdd(cellA + q * strideA, av);
             }
         };
         // the next group's gathers fly while this group is scored; A and B alternate.  Inside the loop both fetches are unconditional,

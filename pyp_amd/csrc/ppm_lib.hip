@@ -272,16 +272,16 @@ static int build_brick_items(ppm_accum *a, const Geom &gm, int BE, int nb) {
         }
         a->load_r = r; a->items_cap = -1;
     }
-    const int smax_env = getenv("PPM_BRICK_SLICES") ? atoi(getenv("PPM_BRICK_SLICES")) : 16;
+    constexpr int kBrickSlices = 16;        // most slices one brick's particles are split into
     const int minp_env = getenv("PPM_BRICK_MINP") ? atoi(getenv("PPM_BRICK_MINP")) : 1024;
-    const int cap = std::max(1, std::min(smax_env, nb / std::max(1, minp_env)));
-    if (cap * 1000 + smax_env == a->items_cap) return 0;
+    const int cap = std::max(1, std::min(kBrickSlices, nb / std::max(1, minp_env)));
+    if (cap == a->items_cap) return 0;
     struct Tmp { BrickItem it; float load; };
     std::vector<Tmp> v;
     for (int bz = 0; bz < nby; bz++) for (int by = 0; by < nby; by++) for (int bx = 0; bx < nbx; bx++) {
         const float L = a->brick_load[((size_t)bz * nby + by) * nbx + bx];
         if (L < 0.f) continue;
-        const int S = std::max(1, std::min(cap, (int)std::lround(L * smax_env)));
+        const int S = std::max(1, std::min(cap, (int)std::lround(L * kBrickSlices)));
         for (int sl = 0; sl < S; sl++) {
             Tmp t; t.it.bx = (unsigned short)bx; t.it.by = (unsigned short)by; t.it.bz = (unsigned short)bz; t.it.s = (unsigned char)sl; t.it.S = (unsigned char)S;
             t.load = L / S; v.push_back(t);
@@ -293,7 +293,7 @@ static int build_brick_items(ppm_accum *a, const Geom &gm, int BE, int nb) {
     if (int rc = a->items.ensure(items.size())) return rc;
     HIPCHK(hipMemcpyAsync(a->items.p, items.data(), items.size() * sizeof(BrickItem), hipMemcpyHostToDevice, cur_stream()));
     HIPCHK(hipStreamSynchronize(cur_stream()));
-    a->n_items = (int)items.size(); a->items_cap = cap * 1000 + smax_env;
+    a->n_items = (int)items.size(); a->items_cap = cap;
     return 0;
 }
 
@@ -313,71 +313,60 @@ static int launch_prep(DevBuf<float2> &spill /* the calling handle's scratch */,
     P.Rm2_bg = (float)std::min(std::floor(Rm_px * Rm_px), 16777216.0);
     P.normalize = normalize; P.invert = invert; P.do_mask = do_mask; P.whiten = whiten;
     for (int k = 0; k < 4; k++) P.focus[k] = focus_px ? focus_px[k] : 0.f;
-    // LDS plan: L row pairs per row pass (L N <= 8 x threads: the next pass is prefetched into <= 8 register pairs per
-    // thread; L divides N/2) share their storage with the nc columns of one column chunk; the whole half spectrum goes
-    // through a global scratch between the two phases.  512 threads / 80 KB -> two blocks per CU.
-    // Block shape (A/B on one box, 100 k x 256^2 insertion workload, us per particle): 512 threads / 80 KB (233 VGPRs: ONE block per
-    // CU resident) 0.456; 512 threads held to 128 VGPRs for two blocks 0.646 (spills); 1024 threads / 160 KB 0.69; 256 threads /
-    // 52 KB at 233 VGPRs (two blocks) 0.399; 256 threads / 40 KB held to 168 VGPRs (three blocks, 252 B of scratch) 0.376 <- default.
-    // The FFT stages are barrier-bound: several small independent blocks overlap each other's barrier waits.
-    int PT = 256;
-    if (const char *e = getenv("PPM_PREP_PT")) { const int v = atoi(e); if (v == 512 || v == 1024 || v == 256) PT = v; }
-    // scratch-free path (N = 256): one 512-thread block per CU keeps the half spectrum in registers between the row and the column phase
-    // (A/B on one box, 100 k x 256^2: reconstruction 0.38 -> 0.29 us per particle, refinement 0.44 -> 0.37; PPM_PREP_INREG=0 selects the scratch path)
-    const bool inreg = gm.N == 256 && !getenv("PPM_PREP_GENERIC") && !getenv("PPM_PREP_PT") && !(getenv("PPM_PREP_INREG") && atoi(getenv("PPM_PREP_INREG")) == 0);
-    if (inreg) PT = 512;
-    // the same path with 1024 threads (16 waves per CU, 32 held values per thread) instead of 512 (8 waves, 64 values): PPM_PREP_INREG_PT=1024
-    if (inreg && getenv("PPM_PREP_INREG_PT") && atoi(getenv("PPM_PREP_INREG_PT")) == 1024) PT = 1024;
-    const int occ3 = !(getenv("PPM_PREP_OCC") && atoi(getenv("PPM_PREP_OCC")) == 2);
-    const size_t budget = (PT == 1024 ? 160 : (PT == 256 ? (getenv("PPM_PREP_LDS") ? atoi(getenv("PPM_PREP_LDS")) : (occ3 ? 40 : 52)) : 80)) * 1024;
-    const size_t lds_fixed = (size_t)(gm.B + 2) * 16 + 16 + 5 * (PT / 64) * sizeof(double) + (12 + PT / 64) * sizeof(float) + (size_t)gm.N * 12 + 16;
-    P.fast256 = (gm.N == 256 && !getenv("PPM_PREP_GENERIC")) ? 1 : 0;
-    P.inreg = inreg ? 1 : 0;
-    P.TS = P.fast256 ? 273 : gm.N + 1; P.WS = P.fast256 ? 272 : gm.N;
-    P.L = std::max(1, std::min(8 * PT / gm.N, gm.N / 2));
-    if (getenv("PPM_PREP_L")) P.L = std::max(1, std::min(atoi(getenv("PPM_PREP_L")), 8 * PT / gm.N));
-    while ((gm.N / 2) % P.L || (size_t)P.L * P.WS * sizeof(float2) + lds_fixed + P.TS * sizeof(float2) > budget / 2 + 8192) P.L--;     // the row pass walks the image 2 L rows at a time; leave about half of the LDS to the column chunk
-    if (P.L < 1) return fail(-12, "pre-processing kernel: row buffer does not fit the LDS");
-    {
-        const size_t wk = (size_t)P.L * P.WS * sizeof(float2);
-        const size_t left = budget - lds_fixed > wk ? budget - lds_fixed - wk : 0;
-        P.nc = std::max(1, std::min(gm.W, (int)(left / (P.TS * sizeof(float2)))));
-        P.nc = std::max(1, std::min(P.nc, 12 * PT / gm.N));        // k_prep prefetches one chunk into 12 registers pairs per thread
-    }
-    P.nchunks = (gm.W + P.nc - 1) / P.nc;
-    P.nc = (gm.W + P.nchunks - 1) / P.nchunks;       // even chunks
-    if (getenv("PPM_PREP_NCH")) { P.nchunks = std::max(P.nchunks, atoi(getenv("PPM_PREP_NCH"))); P.nc = (gm.W + P.nchunks - 1) / P.nchunks; P.nchunks = (gm.W + P.nc - 1) / P.nc; }
-    if (!inreg) if (int rc = spill.ensure((size_t)n_img * gm.N * gm.W)) return rc;
-    P.spill = spill.p;
     P.band_max = band_max;
     P.band = band; P.wring = wring; P.samples = samples; P.S_pad = S_pad; P.Il = Il; P.cw = cw;
     P.Wp = Wp; P.C2 = C2; P.nI = nI; P.Bs = gm.Bs; P.Hs = gm.Hs;
     P.r_s2 = (float)(gm.r_s * gm.r_s); P.r_lo2 = (float)(gm.r_lo * gm.r_lo);
-    size_t lds = ((size_t)P.nc * P.TS + (size_t)P.L * P.WS) * sizeof(float2) + lds_fixed;
-    if (inreg) {            // T (64 columns) and the row buffer (64 row pairs) share one 140 KB region
+    // Two block shapes, one per path of k_prep (ppm_kernels.h).  The FFT stages are barrier-bound: several small independent blocks
+    // overlap each other's barrier waits.  A/B on one box, 100 k x 256^2 insertion workload, us per particle (CHANGELOG.md, Round 2):
+    // 512 threads / 80 KB (233 VGPRs: ONE block per CU resident) 0.456; 512 threads held to 128 VGPRs for two blocks 0.646 (spills);
+    // 1024 threads / 160 KB 0.69; 256 threads / 52 KB at 233 VGPRs (two blocks) 0.399; 256 threads / 40 KB held to 168 VGPRs (three
+    // blocks, 252 B of scratch) 0.376 <- every box but 256.
+    // Box 256 is scratch-free: one 512-thread block per CU keeps the half spectrum in registers between the row and the column phase
+    // (same workload: reconstruction 0.38 -> 0.29 us per particle, refinement 0.44 -> 0.37)
+    const bool scratch_free = gm.N == 256;
+    const int PT = scratch_free ? 512 : 256;
+    // behind the two buffers: ring sums and weights, reduction slots, statistics, twiddles and staging positions (k_prep's carve-up)
+    const size_t lds_fixed = (size_t)(gm.B + 2) * 16 + 16 + 5 * (PT / 64) * sizeof(double) + (12 + PT / 64) * sizeof(float) + (size_t)gm.N * 12 + 16;
+    size_t lds;
+    if (scratch_free) {     // T (64 columns) and the row buffer (64 row pairs) share one 140 KB region; strides spread over the banks
+        P.fast256 = 1; P.inreg = 1;
+        P.TS = 273; P.WS = 272;
         P.L = 64; P.nc = 64; P.nchunks = (std::min(gm.W, 128) + 63) / 64;
+        P.spill = nullptr;      // never dereferenced on this path
         lds = (size_t)64 * P.TS * sizeof(float2) + lds_fixed;
         if (lds > (size_t)160 * 1024) return fail(-12, "pre-processing kernel: LDS plan exceeds 160 KB");
-    } else
-    if (lds > budget) return fail(-12, "pre-processing kernel: LDS plan exceeds its budget");
+    } else {
+        // L row pairs per row pass (L N <= 8 x threads: the next pass is prefetched into <= 8 register pairs per thread; L divides
+        // N/2) and the nc columns of one column chunk; the whole half spectrum goes through a global scratch between the two phases
+        constexpr size_t budget = 40 * 1024;
+        P.fast256 = 0; P.inreg = 0;
+        P.TS = gm.N + 1; P.WS = gm.N;
+        P.L = std::max(1, std::min(8 * PT / gm.N, gm.N / 2));
+        while ((gm.N / 2) % P.L || (size_t)P.L * P.WS * sizeof(float2) + lds_fixed + P.TS * sizeof(float2) > budget / 2 + 8192) P.L--;     // the row pass walks the image 2 L rows at a time; leave about half of the LDS to the column chunk
+        if (P.L < 1) return fail(-12, "pre-processing kernel: row buffer does not fit the LDS");
+        const size_t wk = (size_t)P.L * P.WS * sizeof(float2);
+        const size_t left = budget - lds_fixed > wk ? budget - lds_fixed - wk : 0;
+        P.nc = std::max(1, std::min(gm.W, (int)(left / (P.TS * sizeof(float2)))));
+        P.nc = std::max(1, std::min(P.nc, 12 * PT / gm.N));        // k_prep prefetches one chunk into 12 registers pairs per thread
+        P.nchunks = (gm.W + P.nc - 1) / P.nc;
+        P.nc = (gm.W + P.nchunks - 1) / P.nchunks;       // even chunks
+        if (int rc = spill.ensure((size_t)n_img * gm.N * gm.W)) return rc;
+        P.spill = spill.p;
+        lds = ((size_t)P.nc * P.TS + (size_t)P.L * P.WS) * sizeof(float2) + lds_fixed;
+        if (lds > budget) return fail(-12, "pre-processing kernel: LDS plan exceeds its budget");
+    }
     static bool attr_set = false;
     std::unique_lock<std::mutex> lk_attr(g_mu);
     if (!attr_set) {
         HIPCHK(hipFuncSetAttribute((const void *)k_prep<512, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHK(hipFuncSetAttribute((const void *)k_prep<512, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-        HIPCHK(hipFuncSetAttribute((const void *)k_prep<1024, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHK(hipFuncSetAttribute((const void *)k_prep<256, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
         HIPCHK(hipFuncSetAttribute((const void *)k_prep<256, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
         attr_set = true;
     }
     lk_attr.unlock();
-    const bool two_blocks = getenv("PPM_PREP_OCC") && atoi(getenv("PPM_PREP_OCC")) == 4;
     ProfScope ps(PPM_K_PREP);
-    if (PT == 512 && two_blocks && !inreg) hipLaunchKernelGGL((k_prep<512, 4>), dim3(n_img), dim3(512), lds, cur_stream(), P);
-    else if (PT == 512) hipLaunchKernelGGL((k_prep<512, 2>), dim3(n_img), dim3(512), lds, cur_stream(), P);
-    else if (PT == 256 && occ3) hipLaunchKernelGGL((k_prep<256, 3>), dim3(n_img), dim3(256), lds, cur_stream(), P);
-    else if (PT == 256) hipLaunchKernelGGL((k_prep<256, 2>), dim3(n_img), dim3(256), lds, cur_stream(), P);
-    else hipLaunchKernelGGL((k_prep<1024, 1>), dim3(n_img), dim3(1024), lds, cur_stream(), P);
+    if (scratch_free) hipLaunchKernelGGL((k_prep<512, 2>), dim3(n_img), dim3(512), lds, cur_stream(), P);
+    else hipLaunchKernelGGL((k_prep<256, 3>), dim3(n_img), dim3(256), lds, cur_stream(), P);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -392,8 +381,7 @@ static int launch_global_k(const GlobP &P, int n_img, size_t lds) {
 }
 template <int R>
 static int launch_global_r(const GlobP &P, int n_img, bool half, size_t lds) {
-    // search bands of at most 32 pixels: two slices per wave (k_global<.., TWO>); PPM_GLOBAL_TWO=0 keeps one
-    const bool two = P.Bs <= 31 && !(getenv("PPM_GLOBAL_TWO") && atoi(getenv("PPM_GLOBAL_TWO")) == 0);
+    const bool two = P.Bs <= 31;        // search bands of at most 32 pixels: two slices per wave (k_global<.., TWO>)
     if (two) return half ? launch_global_k<R, true, true>(P, n_img, lds) : launch_global_k<R, false, true>(P, n_img, lds);
     return half ? launch_global_k<R, true, false>(P, n_img, lds) : launch_global_k<R, false, false>(P, n_img, lds);
 }
@@ -779,7 +767,6 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
     if (gm.B > (ref->B + 1) / ref->pad - 1) return fail(-22, "high-resolution limit exceeds the band the reference was prepared for");
     if (cfg->global_search && gm.Bs + 1 > 64)
         return fail(-22, "global search band wider than 64 Fourier pixels is not supported; lower the 'resolution limit for search'");
-    if (!cfg->global_search && !cfg->local_refine) { /* score only */ }
     int K = cfg->top_hits > 0 ? cfg->top_hits : 20;
     if (K > PPM_MAX_TOP_HITS) K = PPM_MAX_TOP_HITS;
     if (K > gm.n_orient) K = gm.n_orient;
@@ -796,8 +783,6 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
     SampleList sl; build_samples(gm, sl);
     const int S_pad = (int)sl.packed.size();
     const int nrings = gm.B + 2;
-    int ring_s = (int)std::ceil(gm.r_s); if (ring_s > gm.B + 1) ring_s = gm.B + 1;
-    (void)ring_s;
     if (int rc = ref->samples.ensure(S_pad)) return rc;
     HIPCHK(hipMemcpyAsync(ref->samples.p, sl.packed.data(), S_pad * sizeof(uint32_t), hipMemcpyHostToDevice, cur_stream()));
 
@@ -969,15 +954,11 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
     LP.tabR = cube_tab_radius(gm.B, cv.scale);
     // tap addresses from LDS tables (ppm_dev.h) unless the tables would crowd the ring sums out of a CU (PPM_LOCAL_TABLES=0: arithmetic)
     const bool local_tab = !(getenv("PPM_LOCAL_TABLES") && atoi(getenv("PPM_LOCAL_TABLES")) == 0) && cube_tab_bytes(LP.tabR) <= 16 * 1024;
-    const int final_threads = (getenv("PPM_LOCAL_FINAL_THREADS") && atoi(getenv("PPM_LOCAL_FINAL_THREADS")) == 128) ? 128 : 256;      // A/B knob
+    constexpr int kFinalThreads = 256;       // block of the final (one pose per particle) k_local launch
     auto launch_local = [&](unsigned grid, int threads) {
         const size_t ring = ring_lds_bytes8(threads / 64, kMaxCand, LP.nr);
         const bool tab = local_tab && ring + cube_tab_bytes(LP.tabR) + 2048 <= (size_t)64 * 1024;      // with the kernel's static LDS inside the 64 KB a launch may ask for (box 512 at the full band: arithmetic)
-        size_t lds = ring + (tab ? cube_tab_bytes(LP.tabR) : 0);
-        if (const char *e = getenv("PPM_LOCAL_BLOCKS_PER_CU")) {      // A/B knob: fewer blocks per CU through a larger LDS request (scripts/ab_local.sh)
-            const int bpc = atoi(e);
-            if (bpc > 0 && bpc < 8) lds = std::min((size_t)63 * 1024, std::max(lds, (size_t)(160 * 1024 / (bpc + 1) + 1024) & ~(size_t)1023));
-        }
+        const size_t lds = ring + (tab ? cube_tab_bytes(LP.tabR) : 0);
         if (tab) hipLaunchKernelGGL(k_local<true>, dim3(grid), dim3(threads), lds, cur_stream(), LP);
         else hipLaunchKernelGGL(k_local<false>, dim3(grid), dim3(threads), lds, cur_stream(), LP);
     };
@@ -998,14 +979,13 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
     const int nfree = (cfg->refine_psi != 0) + (cfg->refine_theta != 0) + (cfg->refine_phi != 0) + (cfg->refine_x != 0) + (cfg->refine_y != 0);
     const int per_iter = nfree ? 2 * nfree + 2 : 0;     // centre + 2 per free parameter + trial
     if (Tb + Tc > kMaxIters) return fail(-22, "too many compass iterations requested");
-    auto fill_schedule = [&](double ha, double hs, int t0, int T, double rcap, double mult) {
+    auto fill_schedule = [&](double ha, double hs, int T, double rcap, double mult) {
         for (int t = 0; t < T; t++) {
             double rb = iter_band(ha, hs, rcap);
             LP.rmax2_it[t] = (float)(rb * rb); LP.S_it[t] = prefix_of(rb);
             sample_evals += mult * per_iter * std::floor(kPi * rb * rb / 2);
             ha *= 0.5; hs *= 0.5;
         }
-        (void)t0;
     };
     LP.rmax2_final = (float)(gm.r_hi * gm.r_hi); LP.S_final = S_pad;
     // answer 22: LOGP / SIGMA over r_lo .. r_cls; without a defocus refinement the final k_local launch scores it, with one k_defocus does
@@ -1076,12 +1056,12 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
             if (Tb > 0) {
                 LP.states = ref->states.p; LP.T = Tb; LP.final_rescore = 0;
                 LP.nr = std::min(nrings, (int)std::ceil(gm.r_s) + 1);
-                fill_schedule(0.5 * gm.dstep, gm.step, 0, Tb, gm.r_s, (double)K);
+                fill_schedule(0.5 * gm.dstep, gm.step, Tb, gm.r_s, (double)K);
                 ProfScope ps(PPM_K_LOCAL);
                 // small blocks for the hit stage: one wave up to 1 024 samples per sweep (no cross-wave steps, 64-sample granularity: k_local
-                // 83.9 -> 80.9 ms per 28 672 particles against two waves, 93.2 with four; scripts/ab_hit_threads.sh), two waves above; 256 threads below
-                const int hit_threads = getenv("PPM_LOCAL_HIT_THREADS") ? atoi(getenv("PPM_LOCAL_HIT_THREADS")) : (LP.S_it[0] <= 1024 ? 64 : 128);
-                launch_local((unsigned)(nb * K), hit_threads == 64 || hit_threads == 256 ? hit_threads : 128);
+                // 83.9 -> 80.9 ms per 28 672 particles against two waves, 93.2 with four; CHANGELOG.md, Round 5, "one-wave blocks for the hit
+                // stage"), two waves above; 256 threads below
+                launch_local((unsigned)(nb * K), LP.S_it[0] <= 1024 ? 64 : 128);
             }
             {
                 ProfScope ps(PPM_K_TOPK);
@@ -1089,20 +1069,20 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
             }
             {
                 LP.states = ref->states2.p; LP.T = cfg->local_refine ? Tc : 0; LP.final_rescore = 1; LP.nr = nrings;
-                fill_schedule(0.5 * gm.dstep / (double)(1 << Tb), gm.step / (double)(1 << Tb), Tb, LP.T, gm.r_hi, 1.0);
+                fill_schedule(0.5 * gm.dstep / (double)(1 << Tb), gm.step / (double)(1 << Tb), LP.T, gm.r_hi, 1.0);
                 sample_evals += std::floor(kPi * gm.r_hi * gm.r_hi / 2);
                 ProfScope ps(PPM_K_LOCAL);
-                launch_local((unsigned)nb, final_threads);
+                launch_local((unsigned)nb, kFinalThreads);
             }
         } else {
             double ha0 = cfg->local_angle_step > 0 ? cfg->local_angle_step : 2.5, hs0 = cfg->local_shift_step > 0 ? cfg->local_shift_step : 2.0;
             hipLaunchKernelGGL(k_states_from_rows, dim3((nb + 255) / 256), dim3(256), 0, cur_stream(), ref->rows_in.p, ref->states2.p, nb, gm.a, ha0, hs0);
             sample_evals = 0;
             LP.states = ref->states2.p; LP.T = cfg->local_refine ? Tb + Tc : 0; LP.final_rescore = 1; LP.nr = nrings;
-            fill_schedule(ha0, hs0, 0, LP.T, gm.r_hi, 1.0);
+            fill_schedule(ha0, hs0, LP.T, gm.r_hi, 1.0);
             sample_evals += std::floor(kPi * gm.r_hi * gm.r_hi / 2);
             ProfScope ps(PPM_K_LOCAL);
-            launch_local((unsigned)nb, final_threads);
+            launch_local((unsigned)nb, kFinalThreads);
         }
         const float *d_ddef = nullptr;
         if (ndef > 0) {                                 // defocus offsets at the final pose
@@ -1752,14 +1732,14 @@ extern "C" int ppm_csp_refine(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const p
     EP.cv.cube = ref->cube; EP.cv.NBX = ref->NBX; EP.cv.NBY = ref->NBY; EP.cv.LB = ref->LB; EP.cv.off = ref->B + 1; EP.cv.scale = (float)ref->pad;
     EP.samples = ref->samples.p; EP.Il = Il.p; EP.cw = cw.p; EP.S_pad = S_pad; EP.N = gm.N; EP.nr = nrings;
     EP.tabR = cube_tab_radius(gm.B, EP.cv.scale);
-    // threads per block of k_csp_eval by the samples of a sweep (PPM_CSP_THREADS = 64 / 128 / 256 forces one)
-    auto csp_threads = [](int S_used) {
-        if (const char *e = getenv("PPM_CSP_THREADS")) { const int v = atoi(e); if (v == 64 || v == 128 || v == 256) return v; }
-        return 256;
-    };
-    const int csp_bpc = getenv("PPM_CSP_BLOCKS_PER_CU") ? atoi(getenv("PPM_CSP_BLOCKS_PER_CU")) : 0;      // blocks of k_csp_eval per CU through the LDS request (0: what registers and LDS allow)
     const bool csp_tab = !(getenv("PPM_LOCAL_TABLES") && atoi(getenv("PPM_LOCAL_TABLES")) == 0) && cube_tab_bytes(EP.tabR) <= 16 * 1024 &&
                          ring_lds_bytes8(4, kMaxCand, nrings) + cube_tab_bytes(EP.tabR) + 2048 <= (size_t)64 * 1024;
+    auto launch_csp_eval = [&](size_t n_rows) {     // one block of 256 threads per evaluation row
+        ProfScope ps(PPM_K_LOCAL);
+        const size_t lds = ring_lds_bytes8(4, kMaxCand, nrings) + (csp_tab ? cube_tab_bytes(EP.tabR) : 0);
+        if (csp_tab) hipLaunchKernelGGL(k_csp_eval<true>, dim3((unsigned)n_rows), dim3(256), lds, cur_stream(), EP);
+        else hipLaunchKernelGGL(k_csp_eval<false>, dim3((unsigned)n_rows), dim3(256), lds, cur_stream(), EP);
+    };
     EP.rlo2 = (float)(gm.r_lo * gm.r_lo); EP.ring_signed = (float)std::min(gm.ring_signed, 1e30);
     EP.kind = kind; EP.eval_rows = d_eval.p; EP.row_part = d_rp.p; EP.row_tilt = d_rt.p; EP.unit_slot = d_slot.p;
     EP.Nmat = d_N.p; EP.pshift = d_p.p; EP.tl = d_tl.p; EP.delta = d_delta.p; EP.s0 = d_s0.p; EP.g0 = d_g0.p; EP.out = d_out.p;
@@ -1786,16 +1766,7 @@ extern "C" int ppm_csp_refine(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const p
             if (ncand > 1) for (int i = 0; i < 3; i++) nrot_c += en[i] ? 2 : 0;
             acct_gathers += (double)rows_list.size() * EP.S_used * (1 + nrot_c); acct_sweeps++;
         }
-        {
-            ProfScope ps(PPM_K_LOCAL);
-            {
-                const int thr = csp_threads(EP.S_used);
-                size_t lds = ring_lds_bytes8(thr / 64, kMaxCand, nrings) + (csp_tab ? cube_tab_bytes(EP.tabR) : 0);
-                if (csp_bpc > 0 && csp_bpc < 8) lds = std::min((size_t)63 * 1024, std::max(lds, (size_t)(160 * 1024 / (csp_bpc + 1) + 1024) & ~(size_t)1023));
-                if (csp_tab) hipLaunchKernelGGL(k_csp_eval<true>, dim3((unsigned)rows_list.size()), dim3(thr), lds, cur_stream(), EP);
-                else hipLaunchKernelGGL(k_csp_eval<false>, dim3((unsigned)rows_list.size()), dim3(thr), lds, cur_stream(), EP);
-            }
-        }
+        launch_csp_eval(rows_list.size());
         if (means) {
             const int nm = (int)active.size() * ncand;
             hipLaunchKernelGGL(k_csp_unit_means, dim3((nm + 255) / 256), dim3(256), 0, cur_stream(), d_out.p, ref->c_uoff.p, (int)active.size(), ncand, ref->c_mean.p);
@@ -1844,14 +1815,7 @@ extern "C" int ppm_csp_refine(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const p
         auto eval_async = [&](const double *delta, int nc, double rband, double *means) {
             EP.delta = delta; EP.ncand = nc; EP.S_used = prefix_of(rband); EP.rmax2 = (float)(rband * rband);
             acct_gathers += (double)eval_rows.size() * EP.S_used * (nc > 1 ? 1 + nrot_c : 1); acct_sweeps++;
-            {
-                ProfScope ps(PPM_K_LOCAL);
-                const int thr = csp_threads(EP.S_used);
-                size_t lds = ring_lds_bytes8(thr / 64, kMaxCand, nrings) + (csp_tab ? cube_tab_bytes(EP.tabR) : 0);
-                if (csp_bpc > 0 && csp_bpc < 8) lds = std::min((size_t)63 * 1024, std::max(lds, (size_t)(160 * 1024 / (csp_bpc + 1) + 1024) & ~(size_t)1023));
-                if (csp_tab) hipLaunchKernelGGL(k_csp_eval<true>, dim3((unsigned)eval_rows.size()), dim3(thr), lds, cur_stream(), EP);
-                else hipLaunchKernelGGL(k_csp_eval<false>, dim3((unsigned)eval_rows.size()), dim3(thr), lds, cur_stream(), EP);
-            }
+            launch_csp_eval(eval_rows.size());
             const int nm = na * nc;
             hipLaunchKernelGGL(k_csp_unit_means, dim3((nm + 255) / 256), dim3(256), 0, cur_stream(), d_out.p, ref->c_uoff.p, na, nc, means);
         };
@@ -2212,26 +2176,28 @@ static int sva_align_impl(ppm_ref_t *ref, ppm_accum_t *avg, const ppm_sva_cfg *c
             EP.vmap = vm ? d_vmap.p : nullptr;
             return 0;
         };
+        // one evaluation of `nc` candidates per state (nr_ of them rotated: 0 or 6) at band rb: k_sva_eval + k_sva_finish -> out
+        auto launch_eval = [&](int ns_, int nc, int nr_, double rb, const double *delta, double *out) -> int {
+            EP.delta = delta; EP.ncand = nc; EP.nrot = nr_; EP.S_used = prefix_of(rb); EP.rmax2 = (float)(rb * rb);
+            acct_gathers += (double)ns_ * EP.S_used * (1 + nr_); acct_sweeps++;
+            ProfScope ps(PPM_K_LOCAL);
+            // A compass sweep runs best at TWO blocks per CU (8 waves): the seven rotations of a sample patch touch almost the same lines of the
+            // reference, and with 16-20 patches in flight per CU the 32 KB L1 keeps none of them (9.6 L2 requests per load instruction;
+            // search 0.084 ms per sub-volume at 4-5 blocks, 0.080 at 3, 0.075 at 2, 0.113 at 1: CHANGELOG.md, Round 4, "k_sva_eval").  The
+            // blocks per CU are set through the size of the dynamic LDS request: more than a third of the CU's 160 KB.
+            size_t tab_lds = cube_tab_bytes(EP.tabR);
+            if (nr_ == 6) tab_lds = std::max(tab_lds, (size_t)(160 * 1024 / 3 + 1024) & ~(size_t)1023);
+            if (tab_lds > (size_t)64 * 1024) tab_lds = (size_t)64 * 1024;
+            if (nr_ == 0) hipLaunchKernelGGL(k_sva_eval<0>, dim3(ns_, kSvaParts), dim3(256), tab_lds, cur_stream(), EP);
+            else if (nr_ == 6) hipLaunchKernelGGL(k_sva_eval<6>, dim3(ns_, kSvaParts), dim3(256), tab_lds, cur_stream(), EP);
+            else return fail(-22, "ppm_sva_align: a sweep has 0 or 6 rotated candidates");
+            hipLaunchKernelGGL(k_sva_finish, dim3((unsigned)((ns_ * nc + 255) / 256)), dim3(256), 0, cur_stream(), EP.partial, ns_, nc, nr_, out);
+            return 0;
+        };
+        // the same with the candidates in `hdelta` and the scores brought back to `hout`
         auto sweep = [&](int ns_, int nc, int nr_, double rb) -> int {
             HIPCHK(hipMemcpyAsync(d_delta.p, hdelta.data(), (size_t)ns_ * nc * 6 * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
-            EP.ncand = nc; EP.nrot = nr_; EP.S_used = prefix_of(rb); EP.rmax2 = (float)(rb * rb);
-            acct_gathers += (double)ns_ * EP.S_used * (1 + nr_); acct_sweeps++;
-            {
-                ProfScope ps(PPM_K_LOCAL);
-                // A compass sweep runs best at TWO blocks per CU (8 waves): the seven rotations of a sample patch touch almost the same lines of the
-                // reference, and with 16-20 patches in flight per CU the 32 KB L1 keeps none of them (9.6 L2 requests per load instruction;
-                // search 0.084 ms per sub-volume at 4-5 blocks, 0.080 at 3, 0.075 at 2, 0.113 at 1: scripts/ab_sva.sh).  The blocks per CU are
-                // set through the size of the dynamic LDS request (PPM_SVA_BLOCKS_PER_CU overrides; 0 = whatever the registers allow).
-                int bpc = nr_ == 6 ? 2 : 0;
-                if (const char *e = getenv("PPM_SVA_BLOCKS_PER_CU")) bpc = atoi(e);
-                size_t tab_lds = cube_tab_bytes(EP.tabR);
-                if (bpc > 0 && bpc < 8) tab_lds = std::max(tab_lds, (size_t)(160 * 1024 / (bpc + 1) + 1024) & ~(size_t)1023);      // more than a (bpc + 1)-th of the CU's LDS
-                if (tab_lds > (size_t)64 * 1024) tab_lds = (size_t)64 * 1024;
-                if (nr_ == 0) hipLaunchKernelGGL(k_sva_eval<0>, dim3(ns_, kSvaParts), dim3(256), tab_lds, cur_stream(), EP);
-                else if (nr_ == 6) hipLaunchKernelGGL(k_sva_eval<6>, dim3(ns_, kSvaParts), dim3(256), tab_lds, cur_stream(), EP);
-                else return fail(-22, "ppm_sva_align: a sweep has 0 or 6 rotated candidates");
-                hipLaunchKernelGGL(k_sva_finish, dim3((unsigned)((ns_ * nc + 255) / 256)), dim3(256), 0, cur_stream(), EP.partial, ns_, nc, nr_, d_out.p);
-            }
+            if (int rc = launch_eval(ns_, nc, nr_, rb, d_delta.p, d_out.p)) return rc;
             HIPCHK(hipGetLastError());
             hout.resize((size_t)ns_ * nc);
             HIPCHK(hipMemcpyAsync(hout.data(), d_out.p, hout.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
@@ -2240,21 +2206,6 @@ static int sva_align_impl(ppm_ref_t *ref, ppm_accum_t *avg, const ppm_sva_cfg *c
         };
         // `Tn` compass iterations of all states at once, steps halved after each: state and decisions on the device (k_csp_step_*), six
         // launches per iteration enqueued back to back, the poses come back once at the end
-        auto launch_eval = [&](int ns_, int nc, int nr_, double rb, const double *delta, double *out) -> int {
-            EP.delta = delta; EP.ncand = nc; EP.nrot = nr_; EP.S_used = prefix_of(rb); EP.rmax2 = (float)(rb * rb);
-            acct_gathers += (double)ns_ * EP.S_used * (1 + nr_); acct_sweeps++;
-            ProfScope ps(PPM_K_LOCAL);
-            int bpc = nr_ == 6 ? 2 : 0;                                    // two blocks per CU for a compass sweep (see `sweep`)
-            if (const char *e = getenv("PPM_SVA_BLOCKS_PER_CU")) bpc = atoi(e);
-            size_t tab_lds = cube_tab_bytes(EP.tabR);
-            if (bpc > 0 && bpc < 8) tab_lds = std::max(tab_lds, (size_t)(160 * 1024 / (bpc + 1) + 1024) & ~(size_t)1023);
-            if (tab_lds > (size_t)64 * 1024) tab_lds = (size_t)64 * 1024;
-            if (nr_ == 0) hipLaunchKernelGGL(k_sva_eval<0>, dim3(ns_, kSvaParts), dim3(256), tab_lds, cur_stream(), EP);
-            else if (nr_ == 6) hipLaunchKernelGGL(k_sva_eval<6>, dim3(ns_, kSvaParts), dim3(256), tab_lds, cur_stream(), EP);
-            else return fail(-22, "ppm_sva_align: a sweep has 0 or 6 rotated candidates");
-            hipLaunchKernelGGL(k_sva_finish, dim3((unsigned)((ns_ * nc + 255) / 256)), dim3(256), 0, cur_stream(), EP.partial, ns_, nc, nr_, out);
-            return 0;
-        };
         auto compass = [&](std::vector<CUnit> &S_, const std::vector<int> *vm, const int *en_, const double *tol_, double &ha, double &hs, int Tn) -> int {
             const int ns_ = (int)S_.size();
             const int nrot_ = en_[0] ? 6 : 0, nsh_ = en_[3] ? 6 : 0, nc_ = 1 + nrot_ + nsh_;

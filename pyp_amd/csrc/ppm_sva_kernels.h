@@ -385,11 +385,6 @@ constexpr int kSvaParts = 4;
 // condition around a fetch; tap addresses come from the LDS tables of ppm_dev.h; the sub-volume's sample is turned by the conjugate
 // phase of the shift once (the rotated candidates keep the unit's shift: checked per block) so that a score term is two instructions
 // on the raw interpolated value.  128 registers instead of 208: four waves per SIMD instead of two.
-#ifdef PPM_SVA_SERIAL        // A/B probe: one rotation's taps at a time (the next rotation finds the lines of this one in L1 if few waves share the CU)
-constexpr bool kSvaSerial = true;
-#else
-constexpr bool kSvaSerial = false;
-#endif
 #ifndef PPM_SVA_EVAL_MINW
 #define PPM_SVA_EVAL_MINW 4      // blocks of 256 threads per CU the register allocation leaves room for
 #endif
@@ -476,8 +471,7 @@ __global__ void __launch_bounds__(256, PPM_SVA_EVAL_MINW) k_sva_eval(SvaEvalP P)
 #define PPM_SVA_GROUP(K, CUR, NXT)                                                                                          \
         if constexpr ((K) < NC) {                                                                                           \
             constexpr int C = C0 + (K);                                                                                     \
-            if constexpr (!kSvaSerial && (K) + 1 < NC) { NXT = fetch(C + 1); __builtin_amdgcn_sched_barrier(0); }           \
-            if constexpr (kSvaSerial && (K) > 0) { CUR = fetch(C); __builtin_amdgcn_sched_barrier(0); }                     \
+            if constexpr ((K) + 1 < NC) { NXT = fetch(C + 1); __builtin_amdgcn_sched_barrier(0); }                          \
             float bx = b0x, by = b0y;                                                                                       \
             if constexpr (C > 0 && !SAME) turned(C, bx, by);                                                                \
             const float2 p = cube_interp(CUR);                                                                              \
