@@ -1,0 +1,390 @@
+// host_csp.h — constrained refinement (ppm_csp_refine).
+#pragma once
+
+// ------------------------------------------------------------------------------ constrained refinement (csp)
+namespace {
+struct CUnit { double N[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, p[3] = { 0, 0, 0 }, tl[4] = { 0, 0, 0, 0 }, acc[6] = { 0, 0, 0, 0, 0, 0 }; };
+
+// a unit's pose <-> 12 doubles (N row-major, then the shift): the layout of ppm_sva_align's poses and of the device's state rows
+inline void pose_pack(const CUnit &u, double *q) { std::memcpy(q, u.N, 9 * sizeof(double)); std::memcpy(q + 9, u.p, 3 * sizeof(double)); }
+inline void pose_unpack(const double *q, CUnit &u) { std::memcpy(u.N, q, 9 * sizeof(double)); std::memcpy(u.p, q + 9, 3 * sizeof(double)); }
+
+// host tables of one ppm_csp_refine call: rows -> units (csp_build_units)
+struct CspUnits {
+    std::vector<int> row_part, row_tilt;            // [n_proj] unit indices of a row
+    std::vector<unsigned char> usable;              // [n_proj] the row takes part in the search
+    std::vector<CUnit> parts, tls;
+    std::vector<double> s0, g0;                     // [n_proj][2] row shift (pixels) and geometric shift at the start
+    std::vector<TiltRot> trot;                      // one set of rotations per tilt instead of four sin / cos pairs per row
+    int nu_all = 0;                                 // units of the refined kind
+    std::vector<std::vector<int>> urows;            // rows of every unit
+    std::vector<unsigned char> refined;
+    std::vector<int> unit_slot, active;             // active: refined units with at least one usable row
+    std::vector<int> eval_rows, final_rows;         // usable rows of the active units, grouped by unit; all rows of the refined units
+    int n_slots = 0;
+};
+// free parameters and step schedule of the compass search
+struct CspSearch { int en[6] = { 0, 0, 0, 0, 0, 0 }; double tol[6] = { 0, 0, 0, 0, 0, 0 }; int nfree = 0, T = 0; double ha0 = 0, hs0 = 0; };
+// what the stages of a call share
+struct CspRun {
+    ppm_ref *ref = nullptr; const ppm_refine_cfg *cfg = nullptr; const ppm_csp_cfg *cc = nullptr;
+    Geom gm; SampleList sl; int S_pad = 0, nrings = 0; double rm_px = 0;
+    int kind = 0, n_proj = 0, n_part = 0, n_tilt = 0;
+    CspEvalP EP; bool tab = false;
+    std::vector<double> hN, hp, htl;                // the units as the device holds them
+    double acct_gathers = 0; long acct_sweeps = 0;  // for the roofline (ppm_refine_last_counts)
+    double bf() const { return cfg->band_factor == 0 ? 3.0 : cfg->band_factor; }
+    int prefix_of(double rband) const { int rg = (int)std::ceil(rband); if (rg > gm.B + 1) rg = gm.B + 1; return sl.ring_off[rg]; }
+};
+}  // namespace
+
+// device first: sample list and the prepared spectra of all rows are enqueued before the host builds its unit tables, which then
+// happens while the device works (20 k rows: ~1.5 ms of hash maps and poses against ~3 ms of pre-processing).
+// The scratch of the constrained search lives in the reference handle (grown on demand, freed with it): allocating and freeing
+// several hundred MB per call cost a third of a call on a 20 k-projection series
+static int csp_prepare_spectra(CspRun &c, const void *images, int images_on_device, const double *rows, bool mode4) {
+    ppm_ref *ref = c.ref; const ppm_refine_cfg *cfg = c.cfg; const Geom &gm = c.gm; const int n_proj = c.n_proj, S_pad = c.S_pad;
+    const size_t NN = (size_t)gm.N * gm.N, HW = (size_t)gm.H * gm.W;
+    if (int rc = ref->samples.ensure(S_pad)) return rc;
+    HIPCHK(hipMemcpyAsync(ref->samples.p, c.sl.packed.data(), S_pad * sizeof(uint32_t), hipMemcpyHostToDevice, cur_stream()));
+    const int CH = (int)std::min<size_t>((size_t)n_proj, std::max<size_t>(64, ((size_t)2 << 30) / (NN * 4 + HW * 8)));
+    if (int rc = ref->c_Il.ensure((size_t)n_proj * S_pad)) return rc;
+    if (int rc = ref->c_cw.ensure((size_t)n_proj * S_pad)) return rc;
+    if (int rc = ref->c_band.ensure((size_t)CH * HW)) return rc;
+    if (int rc = ref->c_rows.ensure((size_t)n_proj * PPM_NCOL)) return rc;
+    if (mode4) if (int rc = ref->c_wring.ensure((size_t)n_proj * (gm.B + 2))) return rc;
+    if (!images_on_device) if (int rc = ref->c_img.ensure((size_t)CH * NN)) return rc;
+    HIPCHK(hipMemcpyAsync(ref->c_rows.p, rows, (size_t)n_proj * PPM_NCOL * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    const double fall = cfg->mask_falloff > 0 ? cfg->mask_falloff : 20.0;
+    for (int c0 = 0; c0 < n_proj; c0 += CH) {
+        const int nb = std::min(CH, n_proj - c0);
+        const float *d_img = (const float *)images + (size_t)c0 * NN;
+        if (!images_on_device) {
+            HIPCHK(hipMemcpyAsync(ref->c_img.p, (const float *)images + (size_t)c0 * NN, (size_t)nb * NN * sizeof(float), hipMemcpyHostToDevice, cur_stream()));
+            d_img = ref->c_img.p;
+        }
+        if (int rc = launch_prep(ref->spill, d_img, ref->c_rows.p + (size_t)c0 * PPM_NCOL, nb, gm, c.rm_px, (float)(fall / gm.a), cfg->normalize, cfg->invert, 1, 1,
+                                 ref->c_band.p, mode4 ? ref->c_wring.p + (size_t)c0 * (gm.B + 2) : nullptr, ref->samples.p, S_pad, ref->c_Il.p + (size_t)c0 * S_pad,
+                                 ref->c_cw.p + (size_t)c0 * S_pad, nullptr, nullptr, nullptr)) return rc;
+        if (!images_on_device) HIPCHK(hipStreamSynchronize(cur_stream()));     // the staging buffer is reused by the next chunk
+    }
+    return 0;
+}
+
+// rows -> units: the particles' and tilts' start state, every row's two units and start shifts, the refined units and their rows
+static int csp_build_units(const CspRun &c, const double *rows, const double *particles, const double *tilts, CspUnits &U) {
+    const ppm_csp_cfg *cc = c.cc; const Geom &gm = c.gm; const int kind = c.kind, n_proj = c.n_proj, n_part = c.n_part, n_tilt = c.n_tilt;
+    std::unordered_map<long, int> pmap, tmap;          // tilt key: (TIND, RIND) folded into one integer
+    pmap.reserve((size_t)n_part * 2); tmap.reserve((size_t)n_tilt * 2);
+    auto tkey = [](long tind, long rind) { return tind * 1000003L + rind; };
+    for (int i = 0; i < n_part; i++) pmap[(long)particles[(size_t)i * PPM_NPCOL]] = i;
+    for (int i = 0; i < n_tilt; i++) tmap[tkey((long)tilts[(size_t)i * PPM_NTCOL], (long)tilts[(size_t)i * PPM_NTCOL + 1])] = i;
+    U.row_part.resize(n_proj); U.row_tilt.resize(n_proj); U.usable.resize(n_proj);
+    U.parts.assign(n_part, CUnit()); U.tls.assign(n_tilt, CUnit());
+    for (int i = 0; i < n_part; i++) {
+        const double *P = particles + (size_t)i * PPM_NPCOL;
+        euler_matrix(-P[4], -P[5], -P[6], U.parts[i].N);
+        U.parts[i].p[0] = P[1]; U.parts[i].p[1] = P[2]; U.parts[i].p[2] = P[3];
+    }
+    for (int i = 0; i < n_tilt; i++) {
+        const double *T = tilts + (size_t)i * PPM_NTCOL;
+        U.tls[i].tl[0] = T[4]; U.tls[i].tl[1] = T[5]; U.tls[i].tl[2] = T[2]; U.tls[i].tl[3] = T[3];
+    }
+    U.s0.resize((size_t)2 * n_proj); U.g0.resize((size_t)2 * n_proj);
+    U.trot.resize(n_tilt);
+    for (int i = 0; i < n_tilt; i++) tilt_rotations(U.tls[i].tl[0], U.tls[i].tl[1], U.trot[i]);
+    for (int j = 0; j < n_proj; j++) {
+        const double *row = rows + (size_t)j * PPM_NCOL;
+        auto ip = pmap.find((long)row[PPM_PIND]); auto it = tmap.find(tkey((long)row[PPM_TIND], (long)row[28]));
+        if (ip == pmap.end() || it == tmap.end()) return fail(-22, "csp: row " + std::to_string(j + 1) + " refers to a particle or tilt missing from the extended parameters");
+        U.row_part[j] = ip->second; U.row_tilt[j] = it->second;
+        const long tind = (long)row[PPM_TIND];
+        U.usable[j] = row[PPM_OCC] > 0 && tind >= cc->tind_min && (cc->tind_max < 0 || tind <= cc->tind_max);
+        U.s0[2 * j] = row[PPM_XSHIFT] / gm.a; U.s0[2 * j + 1] = row[PPM_YSHIFT] / gm.a;
+        double M[9];
+        const CUnit &pu = U.parts[U.row_part[j]], &tu = U.tls[U.row_tilt[j]];
+        csp_row_pose(pu.N, pu.p, U.trot[U.row_tilt[j]], tu.tl[2], tu.tl[3], M, &U.g0[2 * j]);
+    }
+    const int nu_all = U.nu_all = kind == PPM_CSP_PARTICLES ? n_part : n_tilt;
+    U.urows.assign(nu_all, std::vector<int>());
+    for (int j = 0; j < n_proj; j++) U.urows[kind == PPM_CSP_PARTICLES ? U.row_part[j] : U.row_tilt[j]].push_back(j);
+    U.unit_slot.assign(nu_all, -1); U.active.clear();
+    U.refined.assign(nu_all, 0);
+    for (int u = 0; u < nu_all; u++) {
+        const long id = (long)(kind == PPM_CSP_PARTICLES ? particles[(size_t)u * PPM_NPCOL] : tilts[(size_t)u * PPM_NTCOL]);
+        if (id < cc->first || (cc->last >= 0 && id > cc->last)) continue;
+        U.refined[u] = 1;
+        int nus = 0; for (int j : U.urows[u]) nus += U.usable[j];
+        if (nus) { U.unit_slot[u] = (int)U.active.size(); U.active.push_back(u); }
+    }
+    for (int u : U.active) for (int j : U.urows[u]) if (U.usable[j]) U.eval_rows.push_back(j);
+    for (int u = 0; u < nu_all; u++) if (U.refined[u]) for (int j : U.urows[u]) U.final_rows.push_back(j);
+    // units without usable rows still need a slot for the final scoring of their rows (zero displacement)
+    U.n_slots = (int)U.active.size();
+    for (int u = 0; u < nu_all; u++) if (U.refined[u] && U.unit_slot[u] < 0) U.unit_slot[u] = U.n_slots++;
+    // in the other kind's lookups (a particle sweep reads the tilt of a row and vice versa) no slot is needed
+    return 0;
+}
+
+static CspSearch csp_search_plan(const ppm_csp_cfg *cc, int kind, bool any_active) {
+    CspSearch P;
+    int *en = P.en; double *tol = P.tol;
+    if (kind == PPM_CSP_PARTICLES) {
+        for (int k = 0; k < 3; k++) { en[k] = cc->refine_rotation != 0; tol[k] = cc->tol_angle[k]; en[3 + k] = cc->refine_translation != 0; tol[3 + k] = cc->tol_shift; }
+    } else {
+        en[0] = en[1] = cc->refine_rotation != 0; tol[0] = cc->tol_angle[0]; tol[1] = cc->tol_angle[1];
+        en[3] = en[4] = cc->refine_translation != 0; tol[3] = tol[4] = cc->tol_shift;
+    }
+    for (int k = 0; k < 6; k++) { if (!(tol[k] > 0)) en[k] = 0; P.nfree += en[k]; }
+    for (int k = 0; k < 3; k++) if (en[k] && 0.5 * tol[k] > P.ha0) P.ha0 = 0.5 * tol[k];
+    for (int k = 3; k < 6; k++) if (en[k] && 0.5 * tol[k] > P.hs0) P.hs0 = 0.5 * tol[k];
+    const double steptol = cc->step_tolerance > 0 ? cc->step_tolerance : 0.01;
+    P.T = cc->max_iterations;
+    if (P.T <= 0) P.T = compass_iterations(P.ha0, P.hs0, steptol, 1);
+    if (!P.nfree || !any_active) P.T = 0;
+    return P;
+}
+
+// csp mode 4: every row's score for every defocus offset in one sweep (k_defocus), averaged per tilt on the host
+static int csp_defocus_sweep(CspRun &c, const CspUnits &U, double *rows) {
+    ppm_ref *ref = c.ref; const ppm_csp_cfg *cc = c.cc; const Geom &gm = c.gm; const int n_proj = c.n_proj;
+    const double step = cc->defocus_step > 0 ? cc->defocus_step : 50.0;
+    int nt = 0;
+    if (cc->defocus_range >= step) nt = std::min((int)std::floor(cc->defocus_range / step + 1e-6), PPM_MAX_DEFOCUS_STEPS);
+    const int Tn = 2 * nt + 1;
+    if (int rc = ref->c_states.ensure(n_proj)) return rc;
+    if (int rc = ref->c_out.ensure((size_t)n_proj * Tn)) return rc;
+    hipLaunchKernelGGL(k_states_from_rows, dim3((n_proj + 255) / 256), dim3(256), 0, cur_stream(), ref->c_rows.p, ref->c_states.p, n_proj, gm.a, 1.0, 1.0);
+    launch_defocus(cube_view(ref), gm, ref->samples.p, c.S_pad, ref->c_Il.p, ref->c_wring.p, ref->c_rows.p, ref->c_states.p, n_proj, nt, (float)step,
+                   nullptr, ref->c_out.p, 0.f);
+    HIPCHK(hipGetLastError());
+    std::vector<double> sc((size_t)n_proj * Tn);
+    HIPCHK(hipMemcpyAsync(sc.data(), ref->c_out.p, sc.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipStreamSynchronize(cur_stream()));
+    for (int u = 0; u < c.n_tilt; u++) {
+        if (!U.refined[u]) continue;
+        double best = -1e300; int bt = nt;
+        for (int pass = 0; pass < 2; pass++)
+            for (int t = (pass ? 0 : nt); t < (pass ? Tn : nt + 1); t++) {
+                if (pass && t == nt) continue;
+                double ssum = 0; int sn = 0;
+                for (int j : U.urows[u]) if (U.usable[j]) { ssum += sc[(size_t)j * Tn + t]; sn++; }
+                if (sn && ssum / sn > best) { best = ssum / sn; bt = t; }
+            }
+        for (int j : U.urows[u]) {
+            double *row = rows + (size_t)j * PPM_NCOL;
+            row[PPM_DF1] += (bt - nt) * step; row[PPM_DF2] += (bt - nt) * step;
+            score_columns(sc[(size_t)j * Tn + bt], gm.r_lo, gm.r_hi, &row[PPM_SCORE], &row[PPM_SIGMA], &row[PPM_LOGP]);
+        }
+    }
+    return 0;
+}
+
+// the units' state -> device (from U.parts / U.tls through the staging vectors of the run)
+static int csp_upload_units(CspRun &c, const CspUnits &U) {
+    ppm_ref *ref = c.ref;
+    for (int i = 0; i < c.n_part; i++) { std::memcpy(&c.hN[(size_t)9 * i], U.parts[i].N, 9 * sizeof(double)); std::memcpy(&c.hp[(size_t)3 * i], U.parts[i].p, 3 * sizeof(double)); }
+    for (int i = 0; i < c.n_tilt; i++) std::memcpy(&c.htl[(size_t)4 * i], U.tls[i].tl, 4 * sizeof(double));
+    HIPCHK(hipMemcpyAsync(ref->c_N.p, c.hN.data(), c.hN.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->c_p.p, c.hp.data(), c.hp.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->c_tl.p, c.htl.data(), c.htl.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipStreamSynchronize(cur_stream()));
+    return 0;
+}
+
+// static tables of the search on the device, the evaluation parameters (c.EP) and the units' start state
+static int csp_upload_tables(CspRun &c, const CspUnits &U, int ncand_max) {
+    ppm_ref *ref = c.ref; const Geom &gm = c.gm; const int n_proj = c.n_proj, n_part = c.n_part, n_tilt = c.n_tilt, n_slots = U.n_slots;
+    if (int rc = ref->c_rp.ensure(n_proj)) return rc;
+    if (int rc = ref->c_rt.ensure(n_proj)) return rc;
+    if (int rc = ref->c_slot.ensure(U.nu_all)) return rc;
+    if (int rc = ref->c_s0.ensure((size_t)2 * n_proj)) return rc;
+    if (int rc = ref->c_g0.ensure((size_t)2 * n_proj)) return rc;
+    if (int rc = ref->c_N.ensure((size_t)9 * n_part)) return rc;
+    if (int rc = ref->c_p.ensure((size_t)3 * n_part)) return rc;
+    if (int rc = ref->c_tl.ensure((size_t)4 * n_tilt)) return rc;
+    if (ncand_max > kMaxCand) return fail(-22, "csp: too many free parameters");
+    if (int rc = ref->c_delta.ensure((size_t)std::max(n_slots, 1) * ncand_max * 6)) return rc;
+    if (int rc = ref->c_eval.ensure(std::max(U.eval_rows.size(), U.final_rows.size()))) return rc;
+    if (int rc = ref->c_out.ensure(std::max(U.eval_rows.size() * ncand_max, U.final_rows.size()))) return rc;
+    HIPCHK(hipMemcpyAsync(ref->c_rp.p, U.row_part.data(), n_proj * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->c_rt.p, U.row_tilt.data(), n_proj * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->c_slot.p, U.unit_slot.data(), U.nu_all * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->c_s0.p, U.s0.data(), U.s0.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->c_g0.p, U.g0.data(), U.g0.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    c.hN.resize((size_t)9 * n_part); c.hp.resize((size_t)3 * n_part); c.htl.resize((size_t)4 * n_tilt);
+    CspEvalP &EP = c.EP;
+    EP.cv = cube_view(ref);
+    EP.samples = ref->samples.p; EP.Il = ref->c_Il.p; EP.cw = ref->c_cw.p; EP.S_pad = c.S_pad; EP.N = gm.N; EP.nr = c.nrings;
+    EP.tabR = cube_tab_radius(gm.B, EP.cv.scale);
+    c.tab = local_tables_wanted(EP.tabR) && tables_fit_lds(ring_lds_bytes8(4, kMaxCand, c.nrings), EP.tabR);
+    EP.rlo2 = (float)(gm.r_lo * gm.r_lo); EP.ring_signed = (float)std::min(gm.ring_signed, 1e30);
+    EP.kind = c.kind; EP.eval_rows = ref->c_eval.p; EP.row_part = ref->c_rp.p; EP.row_tilt = ref->c_rt.p; EP.unit_slot = ref->c_slot.p;
+    EP.Nmat = ref->c_N.p; EP.pshift = ref->c_p.p; EP.tl = ref->c_tl.p; EP.delta = ref->c_delta.p; EP.s0 = ref->c_s0.p; EP.g0 = ref->c_g0.p; EP.out = ref->c_out.p;
+    // evaluation list of the search (the usable rows of the active units, grouped by unit) and the units' offsets in it: uploaded once
+    std::vector<int> uoff(U.active.size() + 1, 0);
+    for (size_t a = 0; a < U.active.size(); a++) { int n = 0; for (int j : U.urows[U.active[a]]) n += U.usable[j] ? 1 : 0; uoff[a + 1] = uoff[a] + n; }
+    if (int rc = ref->c_uoff.ensure(uoff.size())) return rc;
+    if (int rc = ref->c_mean.ensure(std::max<size_t>(U.active.size() * ncand_max, 1))) return rc;
+    HIPCHK(hipMemcpyAsync(ref->c_uoff.p, uoff.data(), uoff.size() * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    return csp_upload_units(c, U);      // (its synchronisation also covers `uoff`)
+}
+
+// one block of 256 threads per evaluation row
+static void launch_csp_eval(const CspRun &c, size_t n_rows) {
+    ProfScope ps(PPM_K_LOCAL);
+    const size_t lds = ring_lds_bytes8(4, kMaxCand, c.nrings) + (c.tab ? cube_tab_bytes(c.EP.tabR) : 0);
+    if (c.tab) hipLaunchKernelGGL(k_csp_eval<true>, dim3((unsigned)n_rows), dim3(256), lds, cur_stream(), c.EP);
+    else hipLaunchKernelGGL(k_csp_eval<false>, dim3((unsigned)n_rows), dim3(256), lds, cur_stream(), c.EP);
+}
+
+// The compass search: state and decisions on the device (ppm_csp_kernels.h), the iterations enqueued back to back — six launches
+// each (candidates, unit means, trial step, its score, its means, accept) and no host wait until the units come back at the end.
+// The bands follow from the step schedule alone, so the host knows them up front.
+static int csp_compass(CspRun &c, CspUnits &U, const CspSearch &P, int ncand_max) {
+    ppm_ref *ref = c.ref; const Geom &gm = c.gm; CspEvalP &EP = c.EP; const int n_slots = U.n_slots;
+    const int na = (int)U.active.size();
+    DevBuf<double> &d_acc = ref->c_acc, &d_dtrial = ref->c_dtrial, &d_fpm = ref->c_fpm, &d_delta = ref->c_delta, &d_delta_t = ref->c_delta_t, &d_tmean = ref->c_tmean;
+    DevBuf<int> &d_active = ref->c_active;
+    if (int rc = d_acc.ensure((size_t)na * 6)) return rc;
+    if (int rc = d_dtrial.ensure((size_t)na * 6)) return rc;
+    if (int rc = d_fpm.ensure((size_t)na * 12)) return rc;
+    if (int rc = d_delta_t.ensure((size_t)std::max(n_slots, 1) * 6)) return rc;
+    if (int rc = d_tmean.ensure((size_t)na)) return rc;
+    if (int rc = d_active.ensure((size_t)na)) return rc;
+    HIPCHK(hipMemcpyAsync(d_active.p, U.active.data(), (size_t)na * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->c_eval.p, U.eval_rows.data(), U.eval_rows.size() * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemsetAsync(d_delta.p, 0, (size_t)std::max(n_slots, 1) * ncand_max * 6 * sizeof(double), cur_stream()));      // slots of units without usable rows stay zero
+    HIPCHK(hipMemsetAsync(d_delta_t.p, 0, (size_t)std::max(n_slots, 1) * 6 * sizeof(double), cur_stream()));
+    int ncand = 1;
+    for (int i = 0; i < 6; i++) ncand += P.en[i] ? 2 : 0;
+    CspStepP SP;
+    SP.kind = c.kind; SP.n_active = na; SP.ncand = ncand; SP.active = d_active.p; SP.unit_slot = ref->c_slot.p;
+    for (int i = 0; i < 6; i++) { SP.en[i] = P.en[i]; SP.tol[i] = P.tol[i]; }
+    SP.mean = ref->c_mean.p; SP.tmean = d_tmean.p; SP.acc = d_acc.p; SP.dtrial = d_dtrial.p; SP.fpm = d_fpm.p;
+    SP.delta_c = d_delta.p; SP.delta_t = d_delta_t.p; SP.Nmat = ref->c_N.p; SP.pshift = ref->c_p.p; SP.tl = ref->c_tl.p; SP.nstride = 9; SP.pstride = 3;
+    HIPCHK(hipMemsetAsync(d_acc.p, 0, (size_t)na * 6 * sizeof(double), cur_stream()));
+    const unsigned gstep = (unsigned)((na + 127) / 128);
+    int nrot_c = 0;         // accounting: gathers = samples x rotations that differ (shift candidates share the centre's)
+    for (int i = 0; i < 3; i++) nrot_c += P.en[i] ? 2 : 0;
+    auto eval_async = [&](const double *delta, int nc, double rband, double *means) {
+        EP.delta = delta; EP.ncand = nc; EP.S_used = c.prefix_of(rband); EP.rmax2 = (float)(rband * rband);
+        c.acct_gathers += (double)U.eval_rows.size() * EP.S_used * (nc > 1 ? 1 + nrot_c : 1); c.acct_sweeps++;
+        launch_csp_eval(c, U.eval_rows.size());
+        const int nm = na * nc;
+        hipLaunchKernelGGL(k_csp_unit_means, dim3((nm + 255) / 256), dim3(256), 0, cur_stream(), ref->c_out.p, ref->c_uoff.p, na, nc, means);
+    };
+    const bool any_ang = P.en[0] || P.en[1] || P.en[2], any_sh = P.en[3] || P.en[4] || P.en[5];
+    double ha = P.ha0, hs = P.hs0;
+    SP.ha = ha; SP.hs = hs; SP.ha_next = ha; SP.hs_next = hs;
+    hipLaunchKernelGGL(k_csp_step_init, dim3(gstep), dim3(128), 0, cur_stream(), SP);
+    for (int it = 0; it < P.T; it++) {
+        const double rband = march_band(c.bf(), gm.N, c.rm_px, ha, hs, any_ang, any_sh, gm.r_hi);
+        SP.ha = ha; SP.hs = hs; SP.ha_next = 0.5 * ha; SP.hs_next = 0.5 * hs;
+        eval_async(d_delta.p, ncand, rband, ref->c_mean.p);
+        hipLaunchKernelGGL(k_csp_step_trial, dim3(gstep), dim3(128), 0, cur_stream(), SP);
+        eval_async(d_delta_t.p, 1, rband, d_tmean.p);
+        hipLaunchKernelGGL(k_csp_step_accept, dim3(gstep), dim3(128), 0, cur_stream(), SP);
+        ha *= 0.5; hs *= 0.5;
+    }
+    HIPCHK(hipGetLastError());
+    // the units as the search left them
+    HIPCHK(hipMemcpyAsync(c.hN.data(), ref->c_N.p, c.hN.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipMemcpyAsync(c.hp.data(), ref->c_p.p, c.hp.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipMemcpyAsync(c.htl.data(), ref->c_tl.p, c.htl.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipStreamSynchronize(cur_stream()));
+    for (int i = 0; i < c.n_part; i++) { std::memcpy(U.parts[i].N, &c.hN[(size_t)9 * i], 9 * sizeof(double)); std::memcpy(U.parts[i].p, &c.hp[(size_t)3 * i], 3 * sizeof(double)); }
+    for (int i = 0; i < c.n_tilt; i++) std::memcpy(U.tls[i].tl, &c.htl[(size_t)4 * i], 4 * sizeof(double));
+    EP.delta = d_delta.p;
+    return 0;
+}
+
+// scores of every row of the refined units at the full band, at the units' current state (zero displacement) -> hout[final row]
+static int csp_final_scores(CspRun &c, const CspUnits &U, std::vector<double> &hout) {
+    ppm_ref *ref = c.ref; const Geom &gm = c.gm; CspEvalP &EP = c.EP;
+    HIPCHK(hipMemsetAsync(ref->c_delta.p, 0, (size_t)U.n_slots * 6 * sizeof(double), cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->c_eval.p, U.final_rows.data(), U.final_rows.size() * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    EP.ncand = 1; EP.S_used = c.prefix_of(gm.r_hi); EP.rmax2 = (float)(gm.r_hi * gm.r_hi);
+    c.acct_gathers += (double)U.final_rows.size() * EP.S_used; c.acct_sweeps++;
+    launch_csp_eval(c, U.final_rows.size());
+    HIPCHK(hipGetLastError());
+    hout.resize(U.final_rows.size());
+    HIPCHK(hipMemcpyAsync(hout.data(), ref->c_out.p, hout.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipStreamSynchronize(cur_stream()));
+    return 0;
+}
+
+// the refined units -> particles / tilts, and every row of theirs: pose, shifts and the score columns
+static void csp_write_back(const CspRun &c, CspUnits &U, const std::vector<double> &hout, double *rows, double *particles, double *tilts) {
+    const Geom &gm = c.gm; const int kind = c.kind;
+    std::vector<double> row_score(c.n_proj, 0.0);
+    for (size_t q = 0; q < U.final_rows.size(); q++) row_score[U.final_rows[q]] = hout[q];
+    for (int i = 0; i < c.n_tilt; i++) tilt_rotations(U.tls[i].tl[0], U.tls[i].tl[1], U.trot[i]);       // the tilts may have moved
+    const std::vector<CUnit> &units = kind == PPM_CSP_PARTICLES ? U.parts : U.tls;
+    for (int u = 0; u < U.nu_all; u++) {
+        if (!U.refined[u]) continue;
+        if (kind == PPM_CSP_PARTICLES) {
+            double *P = particles + (size_t)u * PPM_NPCOL, a1, a2, a3;
+            angles_from_matrix(units[u].N, a1, a2, a3);
+            P[4] = -a1; P[5] = -a2; P[6] = -a3; P[1] = units[u].p[0]; P[2] = units[u].p[1]; P[3] = units[u].p[2];
+        } else {
+            double *Tt = tilts + (size_t)u * PPM_NTCOL;
+            Tt[4] = units[u].tl[0]; Tt[5] = units[u].tl[1]; Tt[2] = units[u].tl[2]; Tt[3] = units[u].tl[3];
+        }
+        double ssum = 0; int sn = 0;
+        for (int j : U.urows[u]) {
+            double *row = rows + (size_t)j * PPM_NCOL, M[9], gq[2];
+            const CUnit &pu = U.parts[U.row_part[j]], &tu = U.tls[U.row_tilt[j]];
+            csp_row_pose(pu.N, pu.p, U.trot[U.row_tilt[j]], tu.tl[2], tu.tl[3], M, gq);
+            angles_from_matrix(M, row[PPM_PSI], row[PPM_THETA], row[PPM_PHI]);
+            row[PPM_XSHIFT] = (U.s0[2 * j] + gq[0] - U.g0[2 * j]) * gm.a; row[PPM_YSHIFT] = (U.s0[2 * j + 1] + gq[1] - U.g0[2 * j + 1]) * gm.a;
+            score_columns(row_score[j], gm.r_lo, gm.r_hi, &row[PPM_SCORE], &row[PPM_SIGMA], &row[PPM_LOGP]);
+            if (U.usable[j]) { ssum += row[PPM_SCORE]; sn++; }
+        }
+        if (kind == PPM_CSP_PARTICLES) particles[(size_t)u * PPM_NPCOL + 10] = sn ? ssum / sn : -1.0;
+    }
+}
+
+extern "C" int ppm_csp_refine(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const ppm_csp_cfg *cc, const void *images, int images_on_device,
+                              int n_proj, double *rows, double *particles, int n_part, double *tilts, int n_tilt) {
+    if (!g.inited) return fail(-1, "ppm_init has not been called");
+    if (!ref || !cfg || !cc || !images || !rows || !particles || !tilts) return fail(-22, "null argument");
+    StreamScope ss_(ref->stream, ref->copy);
+    if (cc->unit != PPM_CSP_PARTICLES && cc->unit != PPM_CSP_MICROGRAPHS) return fail(-22, "csp: unit must be particles (1) or micrographs (2)");
+    if (n_proj <= 0) return 0;
+    if (n_part <= 0 || n_tilt <= 0) return fail(-22, "csp: the extended parameters hold no particles or no tilts");
+    CspRun c; c.ref = ref; c.cfg = cfg; c.cc = cc; c.kind = cc->unit; c.n_proj = n_proj; c.n_part = n_part; c.n_tilt = n_tilt;
+    const Geom &gm = c.gm;
+    ppm_refine_cfg c2 = *cfg; c2.global_search = 0;
+    std::string err;
+    if (!geom_init(c.gm, c2, err)) return fail(-22, err);
+    if (gm.N != ref->N) return fail(-22, "particle box differs from the reference box");
+    if (gm.B > (ref->B + 1) / ref->pad - 1) return fail(-22, "high-resolution limit exceeds the band the reference was prepared for");
+    const Trace trace_("ppm_csp_refine");
+    c.rm_px = cfg->mask_radius / gm.a;
+    build_samples(gm, c.sl);
+    c.S_pad = (int)c.sl.packed.size(); c.nrings = gm.B + 2;
+    const bool mode4 = cc->refine_defocus != 0;
+    if (mode4 && c.kind != PPM_CSP_MICROGRAPHS) return fail(-22, "csp: defocus refinement works on tilts (unit = micrographs)");
+    if (int rc = csp_prepare_spectra(c, images, images_on_device, rows, mode4)) return rc;
+    CspUnits U;
+    if (int rc = csp_build_units(c, rows, particles, tilts, U)) return rc;
+    if (U.final_rows.empty()) return 0;
+    const CspSearch P = csp_search_plan(cc, c.kind, !U.active.empty());
+    trace_.mark("host tables");
+    if (mode4) return csp_defocus_sweep(c, U, rows);
+    const int ncand_max = 1 + 2 * P.nfree;
+    if (int rc = csp_upload_tables(c, U, ncand_max)) return rc;
+    trace_.mark("spectra prepared, units uploaded");
+    if (P.T > 0) if (int rc = csp_compass(c, U, P, ncand_max)) return rc;
+    trace_.mark("searched");
+    std::vector<double> hout;
+    if (int rc = csp_final_scores(c, U, hout)) return rc;
+    trace_.mark("final scores");
+    csp_write_back(c, U, hout, rows, particles, tilts);
+    // ppm_refine_last_counts after a constrained refinement: 0, sweeps (k_csp_eval launches), in-band samples of the full band, gathered
+    // samples per projection summed over the sweeps
+    ref->last_counts[0] = 0; ref->last_counts[1] = c.acct_sweeps; ref->last_counts[2] = (long)std::floor(kPi * gm.r_hi * gm.r_hi / 2);
+    ref->last_counts[3] = (long)(c.acct_gathers / std::max(n_proj, 1));
+    return 0;
+}

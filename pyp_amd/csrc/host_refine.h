@@ -1,0 +1,754 @@
+// host_refine.h — references, matching projections and ppm_refine_batch: pre-processing, grid search and local refinement launches.
+#pragma once
+
+// ------------------------------------------------------------------------------ pre-processing launch
+static int launch_prep(DevBuf<float2> &spill /* the calling handle's scratch */, const float *d_images, const double *d_rows, int n_img, const Geom &gm, double Rm_px, float fall_px,
+                       int normalize, int invert, int do_mask, int whiten, float2 *band, float *wring,
+                       const uint32_t *samples, int S_pad, float2 *Il, float *cw, float2 *Wp, float *C2, float *nI,
+                       unsigned *band_max = nullptr /* insertion: receives the chunk's largest |band| component */,
+                       const float *focus_px = nullptr /* focus mask: sphere centre and radius in pixels, or null */) {
+    if (int rc = ensure_plan(gm.N)) return rc;
+    PrepP P;
+    P.images = d_images; P.rows = d_rows; P.plan = g.plans[gm.N].plan;
+    P.N = gm.N; P.B = gm.B; P.W = gm.W; P.H = gm.H;
+    P.r_hi2 = (float)(gm.r_hi * gm.r_hi); P.Rm = (float)Rm_px; P.wfall = fall_px; P.a = (float)gm.a;
+    // background pixels: r^2 > Rm^2 taken in double (an integer r^2 exceeds the double Rm^2 exactly when it exceeds its floor); a
+    // float Rm^2 rounds radii like 0.4 N px / px onto the integer r^2 of a pixel ring and drops that ring from the statistics
+    P.Rm2_bg = (float)std::min(std::floor(Rm_px * Rm_px), 16777216.0);
+    P.normalize = normalize; P.invert = invert; P.do_mask = do_mask; P.whiten = whiten;
+    for (int k = 0; k < 4; k++) P.focus[k] = focus_px ? focus_px[k] : 0.f;
+    P.band_max = band_max;
+    P.band = band; P.wring = wring; P.samples = samples; P.S_pad = S_pad; P.Il = Il; P.cw = cw;
+    P.Wp = Wp; P.C2 = C2; P.nI = nI; P.Bs = gm.Bs; P.Hs = gm.Hs;
+    P.r_s2 = (float)(gm.r_s * gm.r_s); P.r_lo2 = (float)(gm.r_lo * gm.r_lo);
+    // Two block shapes, one per path of k_prep (ppm_kernels.h).  The FFT stages are barrier-bound: several small independent blocks
+    // overlap each other's barrier waits.  A/B on one box, 100 k x 256^2 insertion workload, us per particle (CHANGELOG.md, Round 2):
+    // 512 threads / 80 KB (233 VGPRs: ONE block per CU resident) 0.456; 512 threads held to 128 VGPRs for two blocks 0.646 (spills);
+    // 1024 threads / 160 KB 0.69; 256 threads / 52 KB at 233 VGPRs (two blocks) 0.399; 256 threads / 40 KB held to 168 VGPRs (three
+    // blocks, 252 B of scratch) 0.376 <- every box but 256.
+    // Box 256 is scratch-free: one 512-thread block per CU keeps the half spectrum in registers between the row and the column phase
+    // (same workload: reconstruction 0.38 -> 0.29 us per particle, refinement 0.44 -> 0.37)
+    const bool scratch_free = gm.N == 256;
+    const int PT = scratch_free ? 512 : 256;
+    // behind the two buffers: ring sums and weights, reduction slots, statistics, twiddles and staging positions (k_prep's carve-up)
+    const size_t lds_fixed = (size_t)(gm.B + 2) * 16 + 16 + 5 * (PT / 64) * sizeof(double) + (12 + PT / 64) * sizeof(float) + (size_t)gm.N * 12 + 16;
+    size_t lds;
+    if (scratch_free) {     // T (64 columns) and the row buffer (64 row pairs) share one 140 KB region; strides spread over the banks
+        P.fast256 = 1; P.inreg = 1;
+        P.TS = 273; P.WS = 272;
+        P.L = 64; P.nc = 64; P.nchunks = (std::min(gm.W, 128) + 63) / 64;
+        P.spill = nullptr;      // never dereferenced on this path
+        lds = (size_t)64 * P.TS * sizeof(float2) + lds_fixed;
+        if (lds > (size_t)160 * 1024) return fail(-12, "pre-processing kernel: LDS plan exceeds 160 KB");
+    } else {
+        // L row pairs per row pass (L N <= 8 x threads: the next pass is prefetched into <= 8 register pairs per thread; L divides
+        // N/2) and the nc columns of one column chunk; the whole half spectrum goes through a global scratch between the two phases
+        constexpr size_t budget = 40 * 1024;
+        P.fast256 = 0; P.inreg = 0;
+        P.TS = gm.N + 1; P.WS = gm.N;
+        P.L = std::max(1, std::min(8 * PT / gm.N, gm.N / 2));
+        while ((gm.N / 2) % P.L || (size_t)P.L * P.WS * sizeof(float2) + lds_fixed + P.TS * sizeof(float2) > budget / 2 + 8192) P.L--;     // the row pass walks the image 2 L rows at a time; leave about half of the LDS to the column chunk
+        if (P.L < 1) return fail(-12, "pre-processing kernel: row buffer does not fit the LDS");
+        const size_t wk = (size_t)P.L * P.WS * sizeof(float2);
+        const size_t left = budget - lds_fixed > wk ? budget - lds_fixed - wk : 0;
+        P.nc = std::max(1, std::min(gm.W, (int)(left / (P.TS * sizeof(float2)))));
+        P.nc = std::max(1, std::min(P.nc, 12 * PT / gm.N));        // k_prep prefetches one chunk into 12 registers pairs per thread
+        P.nchunks = (gm.W + P.nc - 1) / P.nc;
+        P.nc = (gm.W + P.nchunks - 1) / P.nchunks;       // even chunks
+        if (int rc = spill.ensure((size_t)n_img * gm.N * gm.W)) return rc;
+        P.spill = spill.p;
+        lds = ((size_t)P.nc * P.TS + (size_t)P.L * P.WS) * sizeof(float2) + lds_fixed;
+        if (lds > budget) return fail(-12, "pre-processing kernel: LDS plan exceeds its budget");
+    }
+    static bool attr_set = false;
+    std::unique_lock<std::mutex> lk_attr(g_mu);
+    if (!attr_set) {
+        HIPCHK(hipFuncSetAttribute((const void *)k_prep<512, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIPCHK(hipFuncSetAttribute((const void *)k_prep<256, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
+        attr_set = true;
+    }
+    lk_attr.unlock();
+    ProfScope ps(PPM_K_PREP);
+    if (scratch_free) hipLaunchKernelGGL((k_prep<512, 2>), dim3(n_img), dim3(512), lds, cur_stream(), P);
+    else hipLaunchKernelGGL((k_prep<256, 3>), dim3(n_img), dim3(256), lds, cur_stream(), P);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+template <int R, bool HALF, bool TWO>
+static int launch_global_k(const GlobP &P, int n_img, size_t lds) {
+    static bool set = false;
+    { std::lock_guard<std::mutex> lk_attr(g_mu); if (!set) { HIPCHK(hipFuncSetAttribute((const void *)k_global<R, HALF, TWO>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } }
+    hipLaunchKernelGGL((k_global<R, HALF, TWO>), dim3((n_img + global_particles(R) - 1) / global_particles(R)), dim3(global_threads(R)), lds, cur_stream(), P);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+template <int R>
+static int launch_global_r(const GlobP &P, int n_img, bool half, size_t lds) {
+    const bool two = P.Bs <= 31;        // search bands of at most 32 pixels: two slices per wave (k_global<.., TWO>)
+    if (two) return half ? launch_global_k<R, true, true>(P, n_img, lds) : launch_global_k<R, false, true>(P, n_img, lds);
+    return half ? launch_global_k<R, true, false>(P, n_img, lds) : launch_global_k<R, false, false>(P, n_img, lds);
+}
+
+static int launch_global(GlobP &P, int n_img, bool half, int R) {
+    size_t lds = (size_t)P.HsP * 64 * sizeof(float2) * global_particles(R);
+    P.n = n_img;
+    if (lds < 1024) lds = 1024;
+    // the top-K pass re-uses the block's LDS for a copy of the particle's n_orient scores when they fit (160 KB = 40 928
+    // orientations, e.g. 8 deg at C1); finer grids select on the global scratch instead
+    const size_t lds_topk = (size_t)(32 + P.n_orient) * sizeof(float);
+    P.topk_lds = lds_topk <= (size_t)160 * 1024 ? 1 : 0;
+    if (P.topk_lds && lds_topk > lds) lds = lds_topk;
+    ProfScope ps(PPM_K_GLOBAL);
+    switch (R) {
+        case 1: return launch_global_r<1>(P, n_img, half, lds);
+        case 2: return launch_global_r<2>(P, n_img, half, lds);
+        case 3: return launch_global_r<3>(P, n_img, half, lds);
+        case 4: return launch_global_r<4>(P, n_img, half, lds);
+        case 5: return launch_global_r<5>(P, n_img, half, lds);
+        default: return launch_global_r<6>(P, n_img, half, lds);      // wider windows: k_gfft, or tiles of this one (ppm_refine_batch)
+    }
+}
+
+// Full-window correlation (ppm_gfft.h): LDS plan and launch.  Returns -1 when the search grid is outside what the kernel is built
+// for (Ns = 16 .. 128), in which case the caller keeps the tiled k_global.
+struct GfftPlan { int LN = 0, L = 0, RC = 0, nchunk = 1; size_t t_bytes = 0, lds = 0; int topk_lds = 0; };
+static bool gfft_plan(const Geom &gm, GfftPlan &pl) {
+    int LN = 0; while ((1 << LN) < gm.Ns) LN++;
+    if ((1 << LN) != gm.Ns || LN < 4 || LN > 7) return false;
+    pl.LN = LN; pl.L = gm.Ns / 2;
+    const int L = pl.L, G = gfft_slices_per_pass(L), NR = 2 * gm.RSy + 1;
+    const size_t row = (size_t)G * 2 * gfft_row_stride(L) * sizeof(float2), fixed = (size_t)L * L * sizeof(float4) + gfft_small_bytes(L);
+    const size_t room = (size_t)160 * 1024 - fixed;
+    int RC = NR;
+    if (const char *e = getenv("PPM_GFFT_ROWS")) { const int v = atoi(e); if (v > 0 && v < RC) RC = v; }       // tests: force several row chunks
+    if ((size_t)RC * row > room) RC = (int)(room / row);
+    if (RC > 2 * L) RC = 2 * L;
+    pl.RC = RC; pl.nchunk = (NR + RC - 1) / RC;
+    pl.RC = (NR + pl.nchunk - 1) / pl.nchunk;        // even chunks
+    pl.t_bytes = std::max((size_t)pl.RC * row, (size_t)G * L * L * sizeof(float4));        // T doubles as the staging area of the bank slice(s) of a pass
+    const size_t topk = (size_t)gm.n_orient * sizeof(float);
+    pl.topk_lds = 0;
+    if (topk <= pl.t_bytes) pl.topk_lds = 1;
+    else if (fixed + topk <= (size_t)160 * 1024) { pl.topk_lds = 1; pl.t_bytes = (topk + 15) & ~(size_t)15; }
+    pl.lds = fixed + pl.t_bytes;
+    return true;
+}
+template <int LN, bool CHUNKED>
+static int launch_gfft_k(const GfftP &P, int n_img, size_t lds) {
+    static bool set = false;
+    { std::lock_guard<std::mutex> lk_attr(g_mu); if (!set) { HIPCHK(hipFuncSetAttribute((const void *)k_gfft<LN, CHUNKED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } }
+    hipLaunchKernelGGL((k_gfft<LN, CHUNKED>), dim3(n_img), dim3(256), lds, cur_stream(), P);
+    HIPCHK(hipGetLastError());
+#ifdef PPM_GFFT_STAMPS
+    {   // diagnostic build: cycles per phase and wave of blocks 0 .. 3 (ppm_gfft.h)
+        float st[4 * 4 * 12];
+        HIPCHK(hipStreamSynchronize(cur_stream()));
+        HIPCHK(hipMemcpy(st, P.cc, sizeof(st), hipMemcpyDeviceToHost));
+        const char *names[12] = { "products", "fft", "stores", "barrier A", "row tail", "barrier B", "twiddles", "loop", "row reads + pairs", "row fft", "row max", "-" };
+        const int nsl = P.n_dir * P.npsi_store;
+        for (int b = 0; b < 4 && b < n_img; b++) for (int w = 0; w < 4; w++) {
+            fprintf(stderr, "k_gfft stamps block %d wave %d (cycles per slice):", b, w);
+            for (int i = 0; i < 11; i++) fprintf(stderr, " | %s %.0f", names[i], st[(b * 4 + w) * 12 + i] / nsl);
+            fprintf(stderr, "\n");
+        }
+    }
+#endif
+    return 0;
+}
+static int launch_gfft(GfftP &P, int n_img, const GfftPlan &pl) {
+    P.n = n_img; P.RC = pl.RC; P.nchunk = pl.nchunk; P.t_bytes = (int)pl.t_bytes; P.topk_lds = pl.topk_lds;
+    ProfScope ps(PPM_K_GLOBAL);
+    if (pl.nchunk > 1) {
+        switch (pl.LN) {
+            case 4: return launch_gfft_k<4, true>(P, n_img, pl.lds);
+            case 5: return launch_gfft_k<5, true>(P, n_img, pl.lds);
+            case 6: return launch_gfft_k<6, true>(P, n_img, pl.lds);
+            default: return launch_gfft_k<7, true>(P, n_img, pl.lds);
+        }
+    }
+    switch (pl.LN) {
+        case 4: return launch_gfft_k<4, false>(P, n_img, pl.lds);
+        case 5: return launch_gfft_k<5, false>(P, n_img, pl.lds);
+        case 6: return launch_gfft_k<6, false>(P, n_img, pl.lds);
+        default: return launch_gfft_k<7, false>(P, n_img, pl.lds);
+    }
+}
+
+// ------------------------------------------------------------------------------ refine
+// k_defocus: the offsets -nt .. +nt (steps of `step` Angstrom) about every row's defocus, scored at the pose in `states`.  With `ddef`
+// the kernel chooses per particle (rcls2 > 0: the choice is scored once more over the classification band); with `all_scores` every
+// offset's score is written out and nothing is chosen (constrained search, mode 4).
+static void launch_defocus(const CubeView &cv, const Geom &gm, const uint32_t *samples, int S_pad, const float2 *Il, const float *wring, const double *rows,
+                           LState *states, int n, int nt, float step, float *ddef, double *all_scores, float rcls2) {
+    const int nrings = gm.B + 2;
+    DefocusP DP;
+    DP.cv = cv; DP.samples = samples; DP.Il = Il; DP.wring = wring; DP.S_pad = S_pad; DP.nrings = nrings; DP.N = gm.N; DP.B = gm.B;
+    DP.rlo2 = (float)(gm.r_lo * gm.r_lo); DP.rmax2 = (float)(gm.r_hi * gm.r_hi); DP.ring_signed = (float)std::min(gm.ring_signed, 1e30); DP.a = (float)gm.a;
+    DP.rows = rows; DP.states = states; DP.ddef = ddef; DP.nt = nt; DP.step = step; DP.all_scores = all_scores; DP.rcls2 = rcls2;
+    DP.tchunk = std::max(1, std::min(2 * nt + 1, (int)(60000 / (16 * (size_t)nrings))));      // per-wave ring tables of one pass stay below 64 KB
+    ProfScope ps(PPM_K_LOCAL);
+    hipLaunchKernelGGL(k_defocus, dim3(n), dim3(256), ring_lds_bytes(4, DP.tchunk, nrings), cur_stream(), DP);
+}
+
+namespace {
+// what a ppm_refine_batch call works out before its chunk loop, shared by its stages
+struct RefineRun {
+    ppm_ref *ref = nullptr; const ppm_refine_cfg *cfg = nullptr;
+    Geom gm; SampleList sl; CubeView cv;
+    int S_pad = 0, nrings = 0, CH = 0;
+    int K = 0, Tb = 0, Tc = 0;          // top hits kept; compass iterations of every hit (Tb) and of the best one at the full band (Tc)
+    double Rm_px = 0; float fall_px = 0;
+    bool focus_on = false, sep_search = false; float focus_px[4] = { 0, 0, 0, 0 };
+    // grid search: the window's path and, for k_global, its tiles
+    GfftPlan gpl; bool use_fft = false;
+    int Rtx = 0, Rty = 0, Rwin = 0, HsP = 0, nslices = 0; std::vector<int> cxs, cys;
+    // local refinement
+    LocalP LP; bool local_tab = false;
+    double bf = 3.0; bool any_ang = false, any_sh = false;
+    int ndef = 0;                       // defocus offsets tried on either side of the row's values
+    int per_iter = 0; bool cls_on = false;
+    double sample_evals = 0;            // in-band samples summed over all local score evaluations of one particle
+
+    int ntiles() const { return (int)(cxs.size() * cys.size()); }
+    size_t HS() const { return (size_t)gm.Hs * 64; }
+    int prefix_of(double rband) const { int rg = (int)std::ceil(rband); if (rg > gm.B + 1) rg = gm.B + 1; return sl.ring_off[rg]; }
+};
+constexpr int kTileR = 6;               // k_global keeps its shift window in registers: up to kTileR steps either side without scratch
+constexpr int kFinalThreads = 256;      // block of the final (one pose per particle) k_local launch
+}  // namespace
+
+static void refine_notes(ppm_ref *ref, const ppm_refine_cfg *cfg, const Geom &gm) {
+    ref->note.clear();
+    if (gm.r_s_asked > gm.r_s) {
+        char b[256];
+        std::snprintf(b, sizeof(b), "NOTE: global search band lowered from %.1f to %.1f Fourier pixels (%.2f A instead of %.2f A): the grid-search "
+                      "kernel covers 64 pixels; the top hits are refined up to the high-resolution limit as asked", gm.r_s_asked, gm.r_s,
+                      gm.N * gm.a / gm.r_s, gm.N * gm.a / gm.r_s_asked);
+        ref->note = b;
+    }
+    if (cfg->global_search && gm.range_capped) {
+        char b[320];
+        std::snprintf(b, sizeof(b), "%sNOTE: shift window of the grid search: +-%.0f x +-%.0f pixels (%d x %d search-grid steps of %.1f pixels, the most the "
+                      "search grid of %d points holds; asked: %.0f pixels); the refinement of the hits is not limited to it", ref->note.empty() ? "" : "\n",
+                      gm.RSx * gm.step, gm.RSy * gm.step, gm.RSx, gm.RSy, gm.step, gm.Ns, gm.range_asked_px);
+        ref->note += b;
+    }
+}
+
+// iteration counts, masks, the sample list (uploaded), the grid search's window path and tiles, the chunk size
+static int refine_plan(RefineRun &r, int n_img) {
+    ppm_ref *ref = r.ref; const ppm_refine_cfg *cfg = r.cfg; const Geom &gm = r.gm;
+    r.K = cfg->top_hits > 0 ? cfg->top_hits : 20;
+    if (r.K > PPM_MAX_TOP_HITS) r.K = PPM_MAX_TOP_HITS;
+    if (r.K > gm.n_orient) r.K = gm.n_orient;
+    // answers 36 / 37 (ppm.h): a global search always refines its top hits (Tb iterations each); answer 37 decides whether the
+    // best hit continues at the full band (Tc iterations).  iters_hit < 0: hits stay at their grid points (test hook).
+    r.Tb = cfg->iters_hit > 0 ? cfg->iters_hit : (cfg->iters_hit < 0 ? 0 : 2); r.Tc = cfg->iters_final > 0 ? cfg->iters_final : 7;
+    const double fall = cfg->mask_falloff > 0 ? cfg->mask_falloff : 20.0;
+    r.fall_px = (float)(fall / gm.a);
+    r.Rm_px = cfg->mask_radius / gm.a;
+    r.focus_on = cfg->focus[3] > 0.f;     // a focus mask replaces the centred masks of both stages
+    for (int k = 0; k < 4; k++) r.focus_px[k] = (float)(cfg->focus[k] / gm.a);
+    r.sep_search = !r.focus_on && cfg->global_search && cfg->search_mask_radius > 0 && cfg->search_mask_radius != cfg->mask_radius;
+
+    build_samples(gm, r.sl);
+    r.S_pad = (int)r.sl.packed.size();
+    r.nrings = gm.B + 2;
+    if (int rc = ref->samples.ensure(r.S_pad)) return rc;
+    HIPCHK(hipMemcpyAsync(ref->samples.p, r.sl.packed.data(), r.S_pad * sizeof(uint32_t), hipMemcpyHostToDevice, cur_stream()));
+
+    // shift window: the kernel searches +-PPM_MAX_SHIFT_STEPS steps; a wider window is covered by overlapping tiles of that
+    // half-width whose union is exactly [-RS, RS] (centres cxs / cys, in steps)
+    // k_global keeps its shift window in registers: up to kTileR steps either side without scratch.  Anything wider — PYP's default
+    // "search range 0 = mask radius" is +-41 steps at a 256 box and 4 A — goes to the full-window transform (k_gfft, ppm_gfft.h);
+    // PPM_GLOBAL_PATH=tiles keeps the tiled k_global (A/B runs and the tests that hold one path against the other), =fft forces
+    // the transform for narrow windows too.
+    r.use_fft = false;
+    if (cfg->global_search && gfft_plan(gm, r.gpl)) {
+        const char *gp = getenv("PPM_GLOBAL_PATH");
+        const bool force_fft = gp && !strcmp(gp, "fft"), force_tiles = gp && !strcmp(gp, "tiles");
+        r.use_fft = force_fft || (!force_tiles && std::max(gm.RSx, gm.RSy) > kTileR);
+    }
+    r.Rtx = std::min(gm.RSx, kTileR); r.Rty = std::min(gm.RSy, kTileR);
+    auto tile_centres = [](int RS, int Rt) {
+        const int T = (2 * RS + 1 + 2 * Rt) / (2 * Rt + 1);
+        std::vector<int> c(T, 0);
+        for (int i = 0; i < T && T > 1; i++) c[i] = -RS + Rt + (int)(((long)i * 2 * (RS - Rt)) / (T - 1));
+        return c;
+    };
+    r.cxs = tile_centres(gm.RSx, r.Rtx); r.cys = tile_centres(gm.RSy, r.Rty);
+    r.Rwin = std::max(r.Rtx, r.Rty);
+    // bank rows per slice in the paired order of k_global: row 0 = ky 0, row 1 = empty, rows 2t / 2t+1 = ky +t / -t
+    r.HsP = ((2 * (gm.Bs + 1) + 2 * global_unroll(r.Rwin) - 1) / (2 * global_unroll(r.Rwin))) * (2 * global_unroll(r.Rwin));   // k_global walks 2 U rows per trip
+    r.nslices = gm.n_dir * gm.npsi_store;
+    // chunk so that the scratch stays well inside HBM
+    const size_t NN = (size_t)gm.N * gm.N, HW = (size_t)gm.H * gm.W;
+    size_t per = NN * 4 + HW * 8 + (size_t)r.S_pad * 12 + 2 * PPM_NCOL * 8 + (gm.B + 2) * 4;
+    if (cfg->global_search) per += r.HS() * 12 + (size_t)r.nslices * 4 + (size_t)gm.n_orient * 8 + (size_t)r.K * (sizeof(Hit) + sizeof(LState)) + sizeof(LState);
+    int CH = (int)std::min<size_t>((size_t)n_img, std::max<size_t>(64, ((size_t)4 << 30) / per));
+    CH = std::min(CH, 8192);
+    if (CH >= 2048) CH &= ~1023;        // whole rounds of blocks: 256 CUs x 1 (k_global) and x 4 (k_local, one block per particle)
+    if (const char *e = std::getenv("PPM_CHUNK")) { int v = std::atoi(e); if (v > 0) CH = std::min(CH, v); }   // tests: force several chunks
+    r.CH = CH;
+    return 0;
+}
+
+// per-chunk workspaces of every call
+static int ensure_chunk_buffers(RefineRun &r, bool images_on_device) {
+    ppm_ref *ref = r.ref; const Geom &gm = r.gm; const int CH = r.CH;
+    const size_t NN = (size_t)gm.N * gm.N, HW = (size_t)gm.H * gm.W;
+    if (int rc = ref->rows_in.ensure((size_t)CH * PPM_NCOL)) return rc;
+    if (int rc = ref->rows_out.ensure((size_t)CH * PPM_NCOL)) return rc;
+    if (!images_on_device) if (int rc = ref->images.ensure((size_t)2 * CH * NN)) return rc;     // double-buffered staging
+    if (int rc = ref->band.ensure((size_t)CH * HW)) return rc;
+    if (int rc = ref->wring.ensure((size_t)CH * (gm.B + 2))) return rc;
+    if (int rc = ref->Il.ensure((size_t)CH * r.S_pad)) return rc;
+    if (int rc = ref->cw.ensure((size_t)CH * r.S_pad)) return rc;
+    if (int rc = ref->states2.ensure(CH)) return rc;
+    return 0;
+}
+
+// grid search: per-chunk workspaces; slice bank, twiddles and direction tables (rebuilt only when the grid / band changes)
+static int ensure_search_tables(RefineRun &r) {
+    ppm_ref *ref = r.ref; const Geom &gm = r.gm; const int CH = r.CH, K = r.K, nslices = r.nslices, HsP = r.HsP;
+    const size_t HS = r.HS(), HSP = (size_t)HsP * 64;
+    if (int rc = ref->Wp.ensure((size_t)CH * HS)) return rc;
+    if (int rc = ref->C2.ensure((size_t)CH * HS)) return rc;
+    if (int rc = ref->nP.ensure((size_t)CH * nslices)) return rc;
+    if (int rc = ref->nI.ensure(CH)) return rc;
+    if (int rc = ref->cc.ensure((size_t)CH * gm.n_orient)) return rc;
+    if (int rc = ref->sh.ensure((size_t)CH * gm.n_orient)) return rc;
+    if (int rc = ref->hits.ensure((size_t)CH * K)) return rc;
+    if (int rc = ref->states.ensure((size_t)CH * K)) return rc;
+    char key[160];
+    std::snprintf(key, sizeof(key), "%d/%.6f/%.6f/%d/%d/%d/%.3f/%.3f", gm.N, gm.r_s, gm.dstep, gm.Ns, gm.npsi_store, HsP, gm.phi_max, gm.theta_max);
+    if (ref->bank_key == key) return 0;
+    std::vector<float> mats((size_t)nslices * 6);
+    std::vector<double> dth(gm.n_dir), dph(gm.n_dir);
+    for (int d = 0; d < gm.n_dir; d++) {
+        grid_direction(gm, d, dth[d], dph[d]);
+        for (int k = 0; k < gm.npsi_store; k++) {
+            double M[9]; euler_matrix(k * gm.dpsi, dth[d], dph[d], M);
+            float *m = &mats[((size_t)d * gm.npsi_store + k) * 6];
+            m[0] = (float)M[0]; m[1] = (float)M[1]; m[2] = (float)M[3]; m[3] = (float)M[4]; m[4] = (float)M[6]; m[5] = (float)M[7];
+        }
+    }
+    std::vector<float2> tw(gm.Ns);
+    for (int t = 0; t < gm.Ns; t++) tw[t] = make_float2((float)std::cos(2.0 * kPi * t / gm.Ns), (float)std::sin(2.0 * kPi * t / gm.Ns));
+    if (int rc = ref->mats.ensure(mats.size())) return rc;
+    if (int rc = ref->dir_theta.ensure(gm.n_dir)) return rc;
+    if (int rc = ref->dir_phi.ensure(gm.n_dir)) return rc;
+    if (int rc = ref->twN.ensure(gm.Ns)) return rc;
+    if (int rc = ref->bank.ensure((size_t)nslices * HSP)) return rc;
+    HIPCHK(hipMemcpyAsync(ref->mats.p, mats.data(), mats.size() * sizeof(float), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->dir_theta.p, dth.data(), dth.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->dir_phi.p, dph.data(), dph.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->twN.p, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, cur_stream()));
+    // row twiddles of the shift window (scalar loads in k_global)
+    {
+        std::vector<float4> rt((size_t)kRowTwRows * PPM_MAX_SHIFT_STEPS, make_float4(1.f, 1.f, 0.f, 0.f));
+        for (int tp = 0; tp <= gm.Bs && tp < kRowTwRows; tp++) for (int j = 1; j <= PPM_MAX_SHIFT_STEPS; j++) {
+            int t = ((tp * j) % gm.Ns + gm.Ns) % gm.Ns;
+            const float c = (float)std::cos(2.0 * kPi * t / gm.Ns), sn = (float)std::sin(2.0 * kPi * t / gm.Ns);
+            rt[(size_t)tp * PPM_MAX_SHIFT_STEPS + j - 1] = make_float4(c, c, sn, sn);
+        }
+        if (int rc = ref->rowtw.ensure(rt.size())) return rc;
+        HIPCHK(hipMemcpyAsync(ref->rowtw.p, rt.data(), rt.size() * sizeof(float4), hipMemcpyHostToDevice, cur_stream()));
+        HIPCHK(hipStreamSynchronize(cur_stream()));
+    }
+    BankP BP; BP.cv = r.cv; BP.mats = ref->mats.p; BP.bank = ref->bank.p; BP.nslices = nslices; BP.Bs = gm.Bs; BP.Hs = HsP;
+    BP.r_s2 = (float)(gm.r_s * gm.r_s);
+    {
+        ProfScope ps(PPM_K_BANK);
+        size_t tot = (size_t)nslices * HSP;
+        hipLaunchKernelGGL(k_bank, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, cur_stream(), BP);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(cur_stream()));   // host vectors go out of scope
+    ref->bank_key = key;
+    return 0;
+}
+
+// full-window correlation (k_gfft): the bank in the column pass's layout, the twiddle tables of the search grid and the column penalties
+static int ensure_gfft_tables(RefineRun &r) {
+    ppm_ref *ref = r.ref; const Geom &gm = r.gm; const int nslices = r.nslices;
+    const int L = r.gpl.L;
+    if (int rc = ref->part.ensure((size_t)r.CH * gm.n_orient * 2)) return rc;
+    char key[200];
+    std::snprintf(key, sizeof(key), "%s/L%d", ref->bank_key.c_str(), L);
+    if (ref->bank4_key != key) {
+        if ((size_t)nslices * L * L * sizeof(float4) >= ((size_t)1 << 32)) return fail(-22, "slice bank of the grid search exceeds 4 GB: use a coarser angular step or a narrower search band");
+        if (int rc = ref->bank4.ensure((size_t)nslices * L * L)) return rc;
+        Bank4P BP; BP.cv = r.cv; BP.mats = ref->mats.p; BP.bank4 = ref->bank4.p; BP.nslices = nslices; BP.Bs = gm.Bs; BP.L = L; BP.r_s2 = (float)(gm.r_s * gm.r_s);
+        ProfScope ps(PPM_K_BANK);
+        const size_t tot = (size_t)nslices * L * L;
+        hipLaunchKernelGGL(k_bank4, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, cur_stream(), BP);
+        HIPCHK(hipGetLastError());
+        ref->bank4_key = key;
+    }
+    if (ref->gtw_ns != gm.Ns || ref->gtw_rsx != gm.RSx) {
+        // twiddle tables of the in-register transforms (ppm_fft_reg.h), (cos, sin) pairs: the butterfly table of the L-point transform
+        // (8 floats per entry: w^k, w^2k, w^3k, padding), then the line table w^0 .. w^(L-1) of the Ns-point grid
+        const int nb = fr::bfly_entries(L);
+        std::vector<float> tw((size_t)fr::tw_table_floats(L) + gm.Ns, 0.f);
+        auto put = [&](float *d, double ang) { d[0] = (float)std::cos(ang); d[1] = (float)std::sin(ang); };
+        for (int M = L; M >= 8; M /= 4)
+            for (int k = 1; k < M / 4; k++)
+                for (int j = 1; j <= 3; j++) put(&tw[(size_t)fr::bfly_entry(L, M, k) * 8 + (j - 1) * 2], 2.0 * kPi * j * k / M);
+        for (int t = 0; t < L; t++) put(&tw[(size_t)nb * 8 + (size_t)t * 2], 2.0 * kPi * t / gm.Ns);
+        // column penalties of the row pass, in the order the L-point transform leaves its outputs: position p holds the columns
+        // j = 2 f, 2 f + 1 (f = freq_at(L, p)), column j is the shift sx = j (j < L) or j - Ns
+        for (int pp = 0; pp < L; pp++)
+            for (int h = 0; h < 2; h++) {
+                const int j = 2 * fr::freq_at(L, pp) + h, sx = j < L ? j : j - gm.Ns;
+                tw[(size_t)fr::tw_table_floats(L) + 2 * pp + h] = std::abs(sx) <= gm.RSx ? 0.f : -3.0e38f;
+            }
+        if (int rc = ref->gtw.ensure(tw.size())) return rc;
+        HIPCHK(hipMemcpyAsync(ref->gtw.p, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice, cur_stream()));
+        HIPCHK(hipStreamSynchronize(cur_stream()));       // the host vector goes out of scope
+        ref->gtw_ns = gm.Ns; ref->gtw_rsx = gm.RSx;
+    }
+    return 0;
+}
+
+// LocalP but for its per-launch fields (states, T, nr, schedule): band constants, free parameters, priors, the classification band
+static int local_setup(RefineRun &r) {
+    ppm_ref *ref = r.ref; const ppm_refine_cfg *cfg = r.cfg; const Geom &gm = r.gm; LocalP &LP = r.LP;
+    r.bf = cfg->band_factor == 0 ? 3.0 : cfg->band_factor;
+    r.any_ang = cfg->refine_psi || cfg->refine_theta || cfg->refine_phi; r.any_sh = cfg->refine_x || cfg->refine_y;
+    r.sample_evals = 0;
+    r.ndef = 0;
+    if (cfg->refine_defocus && cfg->defocus_step > 0 && cfg->defocus_range >= cfg->defocus_step)
+        r.ndef = std::min((int)std::floor(cfg->defocus_range / cfg->defocus_step + 1e-6), PPM_MAX_DEFOCUS_STEPS);
+    LP.cv = r.cv; LP.samples = ref->samples.p; LP.Il = ref->Il.p; LP.cw = ref->cw.p; LP.S_pad = r.S_pad; LP.nrings = r.nrings; LP.N = gm.N;
+    LP.tabR = cube_tab_radius(gm.B, r.cv.scale);
+    r.local_tab = local_tables_wanted(LP.tabR);
+    LP.rlo2 = (float)(gm.r_lo * gm.r_lo); LP.ring_signed = (float)std::min(gm.ring_signed, 1e30);
+    LP.en[0] = cfg->refine_psi; LP.en[1] = cfg->refine_theta; LP.en[2] = cfg->refine_phi; LP.en[3] = cfg->refine_x; LP.en[4] = cfg->refine_y;
+    LP.use_priors = 0;
+    for (int i = 0; i < 5; i++) { LP.pmean[i] = 0; LP.pw[i] = 0; }
+    if (cfg->use_priors) {          // Gaussian restraint on the refined parameters (include/ppm.h; same numbers as the oracle's prior_init)
+        const double ns = kPi * (gm.r_hi * gm.r_hi - gm.r_lo * gm.r_lo);
+        for (int i = 0; i < 5; i++) {
+            double var = cfg->prior_var[i], mean = cfg->prior_mean[i];
+            if (i >= 3) { mean /= gm.a; var /= gm.a * gm.a; }
+            LP.pmean[i] = mean;
+            if (LP.en[i] && var > 0 && ns > 0) { LP.pw[i] = 1.0 / (2.0 * var * ns); LP.use_priors = 1; }
+        }
+    }
+    const int nfree = (cfg->refine_psi != 0) + (cfg->refine_theta != 0) + (cfg->refine_phi != 0) + (cfg->refine_x != 0) + (cfg->refine_y != 0);
+    r.per_iter = nfree ? 2 * nfree + 2 : 0;     // centre + 2 per free parameter + trial
+    if (r.Tb + r.Tc > kMaxIters) return fail(-22, "too many compass iterations requested");
+    LP.rmax2_final = (float)(gm.r_hi * gm.r_hi); LP.S_final = r.S_pad;
+    // answer 22: LOGP / SIGMA over r_lo .. r_cls; without a defocus refinement the final k_local launch scores it, with one k_defocus does
+    r.cls_on = gm.r_cls < gm.r_hi;
+    LP.rmax2_class = (float)(gm.r_cls * gm.r_cls); LP.S_class = (r.cls_on && r.ndef == 0) ? r.prefix_of(gm.r_cls) : 0;
+    return 0;
+}
+
+static void launch_local(const RefineRun &r, unsigned grid, int threads) {
+    const LocalP &LP = r.LP;
+    const size_t ring = ring_lds_bytes8(threads / 64, kMaxCand, LP.nr);
+    const bool tab = r.local_tab && tables_fit_lds(ring, LP.tabR);
+    const size_t lds = ring + (tab ? cube_tab_bytes(LP.tabR) : 0);
+    if (tab) hipLaunchKernelGGL(k_local<true>, dim3(grid), dim3(threads), lds, cur_stream(), LP);
+    else hipLaunchKernelGGL(k_local<false>, dim3(grid), dim3(threads), lds, cur_stream(), LP);
+}
+
+// bands and sample-list prefixes of T compass iterations from the steps (ha, hs), halved after each; `mult` poses per particle run them
+static void fill_schedule(RefineRun &r, double ha, double hs, int T, double rcap, double mult) {
+    for (int t = 0; t < T; t++) {
+        double rb = march_band(r.bf, r.gm.N, r.Rm_px, ha, hs, r.any_ang, r.any_sh, rcap);
+        r.LP.rmax2_it[t] = (float)(rb * rb); r.LP.S_it[t] = r.prefix_of(rb);
+        r.sample_evals += mult * r.per_iter * std::floor(kPi * rb * rb / 2);
+        ha *= 0.5; hs *= 0.5;
+    }
+}
+
+// grid search of one chunk: slice norms -> k_gfft | one k_global tile | tiles + merge -> states from the hits -> refinement of
+// every hit over the search band -> the best hit, refined at the full band into states2
+static int global_stage(RefineRun &r, int nb) {
+    ppm_ref *ref = r.ref; const ppm_refine_cfg *cfg = r.cfg; const Geom &gm = r.gm; LocalP &LP = r.LP;
+    const int K = r.K, Tb = r.Tb, Tc = r.Tc, HsP = r.HsP, nslices = r.nslices, ntiles = r.ntiles();
+    GlobP GP;
+    GP.bank = ref->bank.p; GP.Wp = ref->Wp.p; GP.nP = ref->nP.p; GP.nI = ref->nI.p; GP.twN = ref->twN.p; GP.rowtw = ref->rowtw.p;
+    GP.cc = ref->cc.p; GP.sh = ref->sh.p; GP.hits = ref->hits.p;
+    GP.Bs = gm.Bs; GP.Hs = gm.Hs; GP.HsP = HsP; GP.Ns = gm.Ns; GP.RSx = r.Rtx; GP.RSy = r.Rty;
+    GP.n_dir = gm.n_dir; GP.n_psi = gm.n_psi; GP.npsi_store = gm.npsi_store; GP.n_orient = gm.n_orient; GP.K = K;
+    {
+        ProfScope ps(PPM_K_NORMS);
+        NormP NP; NP.C2 = ref->C2.p; NP.bank = ref->bank.p; NP.nP = ref->nP.p; NP.n = nb; NP.nslices = nslices; NP.Bs = gm.Bs; NP.Hs = gm.Hs; NP.HsP = HsP;
+        hipLaunchKernelGGL(k_slice_norms, dim3((nb + 127) / 128, (nslices + 127) / 128), dim3(256), 0, cur_stream(), NP);
+    }
+    if (r.use_fft) {
+        GfftP FP;
+        FP.bank4 = ref->bank4.p; FP.bank4_bytes = (unsigned)((size_t)nslices * r.gpl.L * r.gpl.L * sizeof(float4)); FP.Wp = ref->Wp.p; FP.nP = ref->nP.p; FP.nI = ref->nI.p; FP.tw = ref->gtw.p;
+        FP.part = ref->part.p; FP.cc = ref->cc.p; FP.hits = ref->hits.p;
+        FP.Bs = gm.Bs; FP.Hs = gm.Hs; FP.RSx = gm.RSx; FP.RSy = gm.RSy;
+        FP.n_dir = gm.n_dir; FP.n_psi = gm.n_psi; FP.npsi_store = gm.npsi_store; FP.n_orient = gm.n_orient; FP.K = K;
+        if (int rc = launch_gfft(FP, nb, r.gpl)) return rc;
+    } else if (ntiles == 1) {
+        if (int rc = launch_global(GP, nb, gm.half != 0, r.Rwin)) return rc;
+    } else {
+        // tiles of the shift window: ramp the search tables to the tile's centre, search, keep the tile's top-K; then merge
+        if (int rc = ref->hits_t.ensure((size_t)ntiles * nb * K)) return rc;
+        if (int rc = ref->tile_c.ensure((size_t)2 * ntiles)) return rc;
+        std::vector<int> tc(2 * ntiles);
+        for (int ty = 0, t = 0; ty < (int)r.cys.size(); ty++) for (int tx = 0; tx < (int)r.cxs.size(); tx++, t++) { tc[t] = r.cxs[tx]; tc[ntiles + t] = r.cys[ty]; }
+        HIPCHK(hipMemcpyAsync(ref->tile_c.p, tc.data(), tc.size() * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+        int px = 0, py = 0;
+        const size_t tot = (size_t)nb * r.HS();
+        for (int t = 0; t < ntiles; t++) {
+            const int dcx = tc[t] - px, dcy = tc[ntiles + t] - py;
+            if (dcx || dcy) hipLaunchKernelGGL(k_wp_ramp, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, cur_stream(), ref->Wp.p, tot, gm.Bs, gm.Ns, dcx, dcy, ref->twN.p);
+            px = tc[t]; py = tc[ntiles + t];
+            GP.hits = ref->hits_t.p + (size_t)t * nb * K;
+            if (int rc = launch_global(GP, nb, gm.half != 0, r.Rwin)) return rc;
+        }
+        GP.hits = ref->hits.p;
+        hipLaunchKernelGGL(k_merge_hits, dim3((nb + 127) / 128), dim3(128), 0, cur_stream(), ref->hits_t.p, ref->hits.p, nb, K, ntiles, ref->tile_c.p, ref->tile_c.p + ntiles);
+        HIPCHK(hipStreamSynchronize(cur_stream()));      // the host vector of the centres goes out of scope
+    }
+    {
+        ProfScope ps(PPM_K_TOPK);
+        hipLaunchKernelGGL(k_states_from_hits, dim3((nb * K + 255) / 256), dim3(256), 0, cur_stream(), ref->hits.p, ref->states.p, nb, K,
+                           ref->dir_theta.p, ref->dir_phi.p, gm.n_psi, gm.dpsi, gm.step, 0.5 * gm.dstep, gm.step);
+    }
+    r.sample_evals = 0;
+    if (Tb > 0) {
+        LP.states = ref->states.p; LP.T = Tb; LP.final_rescore = 0;
+        LP.nr = std::min(r.nrings, (int)std::ceil(gm.r_s) + 1);
+        fill_schedule(r, 0.5 * gm.dstep, gm.step, Tb, gm.r_s, (double)K);
+        ProfScope ps(PPM_K_LOCAL);
+        // small blocks for the hit stage: one wave up to 1 024 samples per sweep (no cross-wave steps, 64-sample granularity: k_local
+        // 83.9 -> 80.9 ms per 28 672 particles against two waves, 93.2 with four; CHANGELOG.md, Round 5, "one-wave blocks for the hit
+        // stage"), two waves above; 256 threads below
+        launch_local(r, (unsigned)(nb * K), LP.S_it[0] <= 1024 ? 64 : 128);
+    }
+    {
+        ProfScope ps(PPM_K_TOPK);
+        hipLaunchKernelGGL(k_select_best, dim3((nb + 255) / 256), dim3(256), 0, cur_stream(), ref->states.p, ref->states2.p, nb, K);
+    }
+    LP.states = ref->states2.p; LP.T = cfg->local_refine ? Tc : 0; LP.final_rescore = 1; LP.nr = r.nrings;
+    fill_schedule(r, 0.5 * gm.dstep / (double)(1 << Tb), gm.step / (double)(1 << Tb), LP.T, gm.r_hi, 1.0);
+    r.sample_evals += std::floor(kPi * gm.r_hi * gm.r_hi / 2);
+    ProfScope ps(PPM_K_LOCAL);
+    launch_local(r, (unsigned)nb, kFinalThreads);
+    return 0;
+}
+
+// no grid search: the rows' own poses, refined at the full band into states2
+static void rows_stage(RefineRun &r, int nb) {
+    ppm_ref *ref = r.ref; const ppm_refine_cfg *cfg = r.cfg; const Geom &gm = r.gm; LocalP &LP = r.LP;
+    double ha0 = cfg->local_angle_step > 0 ? cfg->local_angle_step : 2.5, hs0 = cfg->local_shift_step > 0 ? cfg->local_shift_step : 2.0;
+    hipLaunchKernelGGL(k_states_from_rows, dim3((nb + 255) / 256), dim3(256), 0, cur_stream(), ref->rows_in.p, ref->states2.p, nb, gm.a, ha0, hs0);
+    r.sample_evals = 0;
+    LP.states = ref->states2.p; LP.T = cfg->local_refine ? r.Tb + r.Tc : 0; LP.final_rescore = 1; LP.nr = r.nrings;
+    fill_schedule(r, ha0, hs0, LP.T, gm.r_hi, 1.0);
+    r.sample_evals += std::floor(kPi * gm.r_hi * gm.r_hi / 2);
+    ProfScope ps(PPM_K_LOCAL);
+    launch_local(r, (unsigned)nb, kFinalThreads);
+}
+
+// defocus offsets at the final pose (states2), then the output rows
+static int finish_chunk(RefineRun &r, int nb) {
+    ppm_ref *ref = r.ref; const Geom &gm = r.gm;
+    const float *d_ddef = nullptr;
+    if (r.ndef > 0) {
+        if (int rc = ref->ddef.ensure(r.CH)) return rc;
+        launch_defocus(r.cv, gm, ref->samples.p, r.S_pad, ref->Il.p, ref->wring.p, ref->rows_in.p, ref->states2.p, nb, r.ndef, r.cfg->defocus_step,
+                       ref->ddef.p, nullptr, r.cls_on ? (float)(gm.r_cls * gm.r_cls) : 0.f);
+        d_ddef = ref->ddef.p;
+    }
+    hipLaunchKernelGGL(k_rows_out, dim3((nb + 255) / 256), dim3(256), 0, cur_stream(), ref->states2.p, ref->rows_in.p, ref->rows_out.p, nb, gm.a, gm.r_cls, gm.r_lo, d_ddef);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// evaluation counts per particle, for the roofline's algorithmic bytes (ppm_refine_last_counts)
+static void refine_counts(RefineRun &r) {
+    const ppm_refine_cfg *cfg = r.cfg; const Geom &gm = r.gm;
+    long nl;
+    if (cfg->global_search) nl = (long)r.K * r.Tb * r.per_iter + (cfg->local_refine ? (long)r.Tc * r.per_iter : 0) + 1;
+    else nl = 1 + (cfg->local_refine ? (long)(r.Tb + r.Tc) * r.per_iter : 0);
+    r.ref->last_counts[0] = cfg->global_search ? gm.n_orient : 0;
+    nl += 2L * r.ndef + (r.cls_on ? 1 : 0);
+    if (r.cls_on) r.sample_evals += std::floor(kPi * gm.r_cls * gm.r_cls / 2);
+    r.sample_evals += 2.0 * r.ndef * std::floor(kPi * gm.r_hi * gm.r_hi / 2);
+    r.ref->last_counts[1] = nl;
+    r.ref->last_counts[2] = (long)std::floor(kPi * gm.r_s * gm.r_s / 2);
+    r.ref->last_counts[3] = (long)r.sample_evals;      // sum over the local evaluations of their in-band sample counts
+}
+
+extern "C" {
+
+// ------------------------------------------------------------------------------ reference
+ppm_ref_t *ppm_reference_create_weighted(const float *vol, int n, float max_band_px, int pad, const float *ring_weight, int n_weight) {
+    if (!g.inited) { fail(-1, "ppm_init has not been called"); return nullptr; }
+    if (!vol || !box_ok(n) || !(max_band_px > 0)) { fail(-22, "reference box must be even, 32..512, with prime factors 2, 3, 5, 7, and the band positive"); return nullptr; }
+    if ((pad != 1 && pad != 2 && pad != 4) || n * pad > 512) { fail(-22, "padding factor must be 1, 2 or 4 with padded box <= 512"); return nullptr; }
+    if (max_band_px > n / 2) max_band_px = (float)(n / 2);
+    const int np = n * pad;
+    int B = (int)std::ceil((double)max_band_px * pad) - 1;
+    if (B > np / 2 - 1) B = np / 2 - 1;
+    size_t n3 = (size_t)n * n * n, np3 = (size_t)np * np * np;
+    std::unique_ptr<ppm_ref, void (*)(ppm_ref_t *)> guard(new ppm_ref(), ppm_reference_destroy);     // freed on every error return
+    ppm_ref *r = guard.get();
+    HIPCHKP(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
+    HIPCHKP(hipStreamCreateWithFlags(&r->copy, hipStreamNonBlocking));
+    StreamScope ss_(r->stream, r->copy);          // the preparation runs on the new handle's own stream: references may be made concurrently
+    DevTmp<float> t_vol, t_w; DevTmp<float2> t_f;
+    HIPCHKP(t_vol.alloc(n3));
+    HIPCHKP(t_f.alloc(np3));
+    float *d_vol = t_vol.p; float2 *d_f = t_f.p;
+    HIPCHKP(hipMemcpy(d_vol, vol, n3 * sizeof(float), hipMemcpyHostToDevice));
+    if (pad > 1) HIPCHKP(hipMemsetAsync(d_f, 0, np3 * sizeof(float2), cur_stream()));
+    float *d_w = nullptr;
+    if (ring_weight && n_weight > 0) {
+        HIPCHKP(t_w.alloc((size_t)n_weight));
+        d_w = t_w.p;
+        HIPCHKP(hipMemcpyAsync(d_w, ring_weight, (size_t)n_weight * sizeof(float), hipMemcpyHostToDevice, cur_stream()));
+    }
+    r->N = n; r->pad = pad; r->B = B; r->CX = B + 2; r->CY = 2 * B + 3;
+    size_t cube_n = (size_t)r->CX * r->CY * r->CY;
+    r->NBX = (r->CX + 3) / 4; r->NBY = (r->CY + 1) / 2;
+    const size_t copy_n = (size_t)r->NBX * r->NBY * r->NBY * 16;         // blocked layout, two copies (ppm_dev.h)
+    if (2 * copy_n * sizeof(float2) >= ((size_t)1 << 32)) {        // byte offsets of the buffer loads are 32-bit
+    fail(-22, "reference cube too large"); return nullptr; }
+    r->LB = (unsigned)copy_n;
+    if (hipMalloc(&r->cube, 2 * copy_n * sizeof(float2)) != hipSuccess) { r->cube = nullptr; fail(-12, "out of device memory for the reference cube"); return nullptr; }
+    HIPCHKP(hipMemsetAsync(r->cube, 0, 2 * copy_n * sizeof(float2), cur_stream()));
+    {
+        ProfScope ps(PPM_K_BANK);
+        hipLaunchKernelGGL(k_ref_load, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, cur_stream(), d_vol, d_f, n, np);
+        if (fft3d(d_f, np, false)) return nullptr;
+        hipLaunchKernelGGL(k_ref_crop, dim3((unsigned)((cube_n + 255) / 256)), dim3(256), 0, cur_stream(), d_f, r->cube, np, n, B, r->CX, r->CY, r->NBX, r->NBY, r->LB, d_w, n_weight);
+    }
+    if (hipStreamSynchronize(cur_stream()) != hipSuccess || hipGetLastError() != hipSuccess) { fail(-5, "reference preparation failed on the device"); return nullptr; }
+    return guard.release();
+}
+
+ppm_ref_t *ppm_reference_create_padded(const float *vol, int n, float max_band_px, int pad) { return ppm_reference_create_weighted(vol, n, max_band_px, pad, nullptr, 0); }
+ppm_ref_t *ppm_reference_create(const float *vol, int n, float max_band_px) { return ppm_reference_create_weighted(vol, n, max_band_px, 1, nullptr, 0); }
+
+void ppm_reference_destroy(ppm_ref_t *r) {
+    if (!r) return;
+    if (r->cube) (void)hipFree(r->cube);
+    r->rows_in.release(); r->rows_out.release(); r->dir_theta.release(); r->dir_phi.release();
+    r->images.release(); r->wring.release(); r->cw.release(); r->C2.release(); r->nP.release(); r->nI.release();
+    r->s_f.release(); r->s_g.release(); r->s_F.release(); r->s_vols.release(); r->s_plan.samples.release(); r->s_plan.pos.release(); r->s_plan.bandw.release(); r->s_plan.Fw.release();
+    r->c_Il.release(); r->c_band.release(); r->c_cw.release(); r->c_img.release(); r->c_wring.release(); r->c_rows.release(); r->c_N.release(); r->c_p.release(); r->c_tl.release();
+    r->c_delta.release(); r->c_s0.release(); r->c_g0.release(); r->c_out.release(); r->c_eval.release(); r->c_rp.release(); r->c_rt.release(); r->c_slot.release(); r->c_states.release(); r->c_uoff.release(); r->c_mean.release(); r->c_active.release(); r->c_tmean.release(); r->c_acc.release(); r->c_dtrial.release(); r->c_fpm.release(); r->c_delta_t.release(); r->cc.release(); r->mats.release(); r->ddef.release();
+    r->band.release(); r->spill.release(); r->Il.release(); r->Wp.release(); r->bank.release(); r->twN.release(); r->rowtw.release(); r->sh.release(); r->samples.release();
+    r->hits.release(); r->states.release(); r->states2.release();
+    r->hits_t.release(); r->tile_c.release(); r->bank4.release(); r->part.release(); r->gtw.release();
+    if (r->stream) (void)hipStreamDestroy(r->stream);
+    if (r->copy) (void)hipStreamDestroy(r->copy);
+    delete r;
+}
+
+// ------------------------------------------------------------------------------ matching projections
+int ppm_match_projections(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const double *rows, int n_rows, float *out) {
+    if (!g.inited) return fail(-1, "ppm_init has not been called");
+    if (!ref || !cfg || !rows || !out) return fail(-22, "null argument");
+    StreamScope ss_(ref->stream, ref->copy);
+    if (n_rows <= 0) return 0;
+    ppm_refine_cfg c2 = *cfg; c2.global_search = 0;          // only box, pixel size and the high-resolution limit matter here
+    Geom gm; std::string err;
+    if (!geom_init(gm, c2, err)) return fail(-22, err);
+    if (gm.N != ref->N) return fail(-22, "particle box differs from the reference box");
+    if (gm.B > (ref->B + 1) / ref->pad - 1) return fail(-22, "high-resolution limit exceeds the band the reference was prepared for");
+    const size_t NN = (size_t)gm.N * gm.N;
+    const int CH = (int)std::min<size_t>((size_t)n_rows, std::max<size_t>(1, ((size_t)1 << 30) / (NN * 12)));
+    DevTmp<float2> d_f; DevTmp<float> d_o; DevTmp<MatchRow> d_rows;
+    HIPCHK(d_f.alloc(NN * CH)); HIPCHK(d_o.alloc(NN * CH)); HIPCHK(d_rows.alloc(CH));
+    MatchP MP;
+    MP.cv = cube_view(ref);
+    MP.rows = d_rows.p; MP.f = d_f.p; MP.N = gm.N; MP.B = gm.B; MP.r_hi2 = (float)(gm.r_hi * gm.r_hi);
+    std::vector<MatchRow> hr(CH);
+    const float scale = (cfg->invert ? -1.f : 1.f) / (float)gm.N;     // cube = FFT / N: the unnormalised inverse transform needs 1 / N more
+    for (int c0 = 0; c0 < n_rows; c0 += CH) {
+        const int nb = std::min(CH, n_rows - c0);
+        for (int i = 0; i < nb; i++) {
+            const double *row = rows + (size_t)(c0 + i) * PPM_NCOL;
+            double M[9]; euler_matrix(row[PPM_PSI], row[PPM_THETA], row[PPM_PHI], M);
+            MatchRow &q = hr[i];
+            q.m[0] = (float)M[0]; q.m[1] = (float)M[1]; q.m[2] = (float)M[3]; q.m[3] = (float)M[4]; q.m[4] = (float)M[6]; q.m[5] = (float)M[7];
+            q.sx = (float)(row[PPM_XSHIFT] / gm.a); q.sy = (float)(row[PPM_YSHIFT] / gm.a);
+            q.ctf = ctf_from_row(row, gm.N, gm.a);
+        }
+        HIPCHK(hipMemcpyAsync(d_rows.p, hr.data(), (size_t)nb * sizeof(MatchRow), hipMemcpyHostToDevice, cur_stream()));
+        MP.n = nb;
+        hipLaunchKernelGGL(k_match_fill, dim3((unsigned)((NN * nb + 255) / 256)), dim3(256), 0, cur_stream(), MP);
+        if (int rc = fft2d_batch(d_f.p, gm.N, nb, true)) return rc;
+        hipLaunchKernelGGL(k_match_real, dim3((unsigned)((NN * nb + 255) / 256)), dim3(256), 0, cur_stream(), d_f.p, d_o.p, NN * nb, scale);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out + (size_t)c0 * NN, d_o.p, NN * nb * sizeof(float), hipMemcpyDeviceToHost, cur_stream()));
+        HIPCHK(hipStreamSynchronize(cur_stream()));            // `hr` is reused by the next chunk
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------ refine
+int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *images, int images_on_device,
+                     int n_img, const double *rows_in, double *rows_out) {
+    if (!g.inited) return fail(-1, "ppm_init has not been called");
+    if (!ref || !cfg || !images || !rows_in || !rows_out) return fail(-22, "null argument");
+    StreamScope ss_(ref->stream, ref->copy);
+    if (n_img <= 0) return 0;
+    RefineRun r; r.ref = ref; r.cfg = cfg;
+    const Geom &gm = r.gm; std::string err;
+    if (!geom_init(r.gm, *cfg, err)) return fail(-22, err);
+    if (gm.N != ref->N) return fail(-22, "particle box differs from the reference box");
+    refine_notes(ref, cfg, gm);
+    if (gm.B > (ref->B + 1) / ref->pad - 1) return fail(-22, "high-resolution limit exceeds the band the reference was prepared for");
+    if (cfg->global_search && gm.Bs + 1 > 64)
+        return fail(-22, "global search band wider than 64 Fourier pixels is not supported; lower the 'resolution limit for search'");
+    if (int rc = refine_plan(r, n_img)) return rc;
+    if (int rc = ensure_chunk_buffers(r, images_on_device != 0)) return rc;
+    r.cv = cube_view(ref);
+    if (cfg->global_search) if (int rc = ensure_search_tables(r)) return rc;
+    if (r.use_fft) if (int rc = ensure_gfft_tables(r)) return rc;
+    HIPCHK(hipStreamSynchronize(cur_stream()));
+    if (int rc = local_setup(r)) return rc;
+
+    const int CH = r.CH;
+    const size_t NN = (size_t)gm.N * gm.N;
+    const ChunkStager stage{ (const float *)images, ref->images.p, images_on_device != 0, n_img, CH, NN };
+    if (int rc = stage.prime()) return rc;
+    for (int c0 = 0, ci = 0; c0 < n_img; c0 += CH, ci++) {
+        const int nb = std::min(CH, n_img - c0);
+        HIPCHK(hipMemcpyAsync(ref->rows_in.p, rows_in + (size_t)c0 * PPM_NCOL, (size_t)nb * PPM_NCOL * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+        const float *d_img = stage.chunk_ptr(c0, ci);
+        // refinement spectra (+ search tables when the same mask serves both)
+        if (int rc = launch_prep(ref->spill, d_img, ref->rows_in.p, nb, gm, r.Rm_px, r.fall_px, cfg->normalize, cfg->invert, 1, 1, ref->band.p, ref->wring.p,
+                                 ref->samples.p, r.S_pad, ref->Il.p, ref->cw.p,
+                                 (cfg->global_search && !r.sep_search) ? ref->Wp.p : nullptr, ref->C2.p, ref->nI.p, nullptr, r.focus_on ? r.focus_px : nullptr)) return rc;
+        if (r.sep_search)
+            if (int rc = launch_prep(ref->spill, d_img, ref->rows_in.p, nb, gm, cfg->search_mask_radius / gm.a, r.fall_px, cfg->normalize, cfg->invert, 1, 1,
+                                     ref->band.p, nullptr, nullptr, 0, nullptr, nullptr, ref->Wp.p, ref->C2.p, ref->nI.p)) return rc;
+        if (cfg->global_search) { if (int rc = global_stage(r, nb)) return rc; }
+        else rows_stage(r, nb);
+        if (int rc = finish_chunk(r, nb)) return rc;
+        if (int rc = stage.prefetch_next(c0, ci)) return rc;     // next chunk's images travel while this chunk computes
+        HIPCHK(hipMemcpyAsync(rows_out + (size_t)c0 * PPM_NCOL, ref->rows_out.p, (size_t)nb * PPM_NCOL * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
+        if (int rc = stage.sync()) return rc;
+    }
+    refine_counts(r);
+    return 0;
+}
+
+
+const char *ppm_refine_note(ppm_ref_t *ref) { return ref ? ref->note.c_str() : ""; }
+
+int ppm_refine_last_counts(ppm_ref_t *ref, long *n_global, long *n_local, long *samples_global, long *samples_local) {
+    if (!ref) return fail(-22, "null reference");
+    if (n_global) *n_global = ref->last_counts[0];
+    if (n_local) *n_local = ref->last_counts[1];
+    if (samples_global) *samples_global = ref->last_counts[2];
+    if (samples_local) *samples_local = ref->last_counts[3];
+    return 0;
+}
+
+}  // extern "C"

@@ -185,6 +185,33 @@ inline void csp_row_pose(const double N[9], const double p[3], double tilt, doub
     csp_row_pose(N, p, r, tsx, tsy, M, g);
 }
 
+// Frequency marching: band of one compass iteration from its probe displacement (angle step `ha` degrees at the mask radius `rm_px`,
+// shift step `hs` pixels).  Rings whose phase moves by more than about `bf` radians under the larger of the two carry no usable
+// gradient; bf < 0 or no probe at all leaves the cap.  The one rule of every search (refinement, csp, sub-tomograms, and the coarse
+// band of a rotation grid: ha = half the grid step, no shifts); it restates the oracle's iter_band, operand for operand.
+inline double march_band(double bf, int N, double rm_px, double ha, double hs, bool any_ang, bool any_sh, double rcap) {
+    if (bf < 0) return rcap;
+    double d = 0;
+    if (any_ang) d = rm_px * ha * kPi / 180.0;
+    if (any_sh && hs > d) d = hs;
+    if (!(d > 0)) return rcap;
+    double rit = bf * N / (2.0 * kPi * d);
+    if (rit < 4.0) rit = 4.0;
+    return rit < rcap ? rit : rcap;
+}
+// Compass iterations until the larger first step has halved below `steptol`: ceil(log2(max(ha, hs) / steptol)), min_iters .. 12
+inline int compass_iterations(double ha, double hs, double steptol, int min_iters) {
+    const double m = std::max(ha, hs);
+    const int T = m > steptol ? (int)std::ceil(std::log(m / steptol) / std::log(2.0)) : min_iters;
+    return std::min(12, std::max(min_iters, T));
+}
+// SCORE / SIGMA / LOGP columns of a row from its correlation over the band r_lo .. r_hi (Fourier pixels)
+inline void score_columns(double cc, double r_lo, double r_hi, double *score, double *sigma, double *logp) {
+    double res = 1.0 - cc * cc; if (res < 1e-6) res = 1e-6;
+    *score = 100.0 * cc; *sigma = std::sqrt(res);
+    *logp = -0.5 * (kPi * (r_hi * r_hi - r_lo * r_lo)) * (std::log(2.0 * kPi * res) + 1.0);
+}
+
 // Ring-ordered sample list of the half plane kx >= 0, 0 < k^2 < r_hi^2, ring = floor(|k|); every
 // ring padded to a multiple of 16 samples with weightless dummies so that a 16-lane group never
 // straddles two rings.  Packed: kx (9 bits) | ky+256 (10 bits) << 9 | alpha (2 bits) << 19 | ring << 21.

@@ -125,7 +125,7 @@ def test_finalize_is_reproducible(H, N):
 
 # ----------------------------------------------------------------------------------------------------------- leg B
 def prep_plan(N, B):
-    """The column-chunk plan launch_prep (pyp_amd/csrc/ppm_lib.hip) derives for box N and band half-width B on its default
+    """The column-chunk plan launch_prep (pyp_amd/csrc/host_refine.h) derives for box N and band half-width B on its default
     path (256 threads, 40 KB of LDS): row pairs L (divides N/2), chunk width nc, chunk count and the last chunk's width.
     lds_fixed = 16 (B + 2) + 16 + 5 x 4 x 8 + (12 + 4) x 4 + 12 N + 16 bytes; L = min(2048 / N, N / 2), lowered until it
     divides N/2 and L N 8 + lds_fixed + 8 (N + 1) <= 20 KB + 8 KB; nc = min(W, (40 KB - lds_fixed - L N 8) / (8 (N + 1)),
