@@ -21,44 +21,20 @@ static int launch_prep(DevBuf<float2> &spill /* the calling handle's scratch */,
     P.band = band; P.wring = wring; P.samples = samples; P.S_pad = S_pad; P.Il = Il; P.cw = cw;
     P.Wp = Wp; P.C2 = C2; P.nI = nI; P.Bs = gm.Bs; P.Hs = gm.Hs;
     P.r_s2 = (float)(gm.r_s * gm.r_s); P.r_lo2 = (float)(gm.r_lo * gm.r_lo);
-    // Two block shapes, one per path of k_prep (ppm_kernels.h).  The FFT stages are barrier-bound: several small independent blocks
-    // overlap each other's barrier waits.  A/B on one box, 100 k x 256^2 insertion workload, us per particle (CHANGELOG.md, Round 2):
-    // 512 threads / 80 KB (233 VGPRs: ONE block per CU resident) 0.456; 512 threads held to 128 VGPRs for two blocks 0.646 (spills);
-    // 1024 threads / 160 KB 0.69; 256 threads / 52 KB at 233 VGPRs (two blocks) 0.399; 256 threads / 40 KB held to 168 VGPRs (three
-    // blocks, 252 B of scratch) 0.376 <- every box but 256.
+    // Two block shapes, one per path of k_prep (ppm_kernels.h); prep_plan (ppm_geom.h) chooses and sizes them.  The FFT stages are
+    // barrier-bound: several small independent blocks overlap each other's barrier waits.  A/B on one box, 100 k x 256^2 insertion
+    // workload, us per particle (CHANGELOG.md, Round 2): 512 threads / 80 KB (233 VGPRs: ONE block per CU resident) 0.456; 512 threads
+    // held to 128 VGPRs for two blocks 0.646 (spills); 1024 threads / 160 KB 0.69; 256 threads / 52 KB at 233 VGPRs (two blocks) 0.399;
+    // 256 threads / 40 KB held to 168 VGPRs (three blocks, 252 B of scratch) 0.376 <- every box but 256.
     // Box 256 is scratch-free: one 512-thread block per CU keeps the half spectrum in registers between the row and the column phase
     // (same workload: reconstruction 0.38 -> 0.29 us per particle, refinement 0.44 -> 0.37)
-    const bool scratch_free = gm.N == 256;
-    const int PT = scratch_free ? 512 : 256;
-    // behind the two buffers: ring sums and weights, reduction slots, statistics, twiddles and staging positions (k_prep's carve-up)
-    const size_t lds_fixed = (size_t)(gm.B + 2) * 16 + 16 + 5 * (PT / 64) * sizeof(double) + (12 + PT / 64) * sizeof(float) + (size_t)gm.N * 12 + 16;
-    size_t lds;
-    if (scratch_free) {     // T (64 columns) and the row buffer (64 row pairs) share one 140 KB region; strides spread over the banks
-        P.fast256 = 1; P.inreg = 1;
-        P.TS = 273; P.WS = 272;
-        P.L = 64; P.nc = 64; P.nchunks = (std::min(gm.W, 128) + 63) / 64;
-        P.spill = nullptr;      // never dereferenced on this path
-        lds = (size_t)64 * P.TS * sizeof(float2) + lds_fixed;
-        if (lds > (size_t)160 * 1024) return fail(-12, "pre-processing kernel: LDS plan exceeds 160 KB");
-    } else {
-        // L row pairs per row pass (L N <= 8 x threads: the next pass is prefetched into <= 8 register pairs per thread; L divides
-        // N/2) and the nc columns of one column chunk; the whole half spectrum goes through a global scratch between the two phases
-        constexpr size_t budget = 40 * 1024;
-        P.fast256 = 0; P.inreg = 0;
-        P.TS = gm.N + 1; P.WS = gm.N;
-        P.L = std::max(1, std::min(8 * PT / gm.N, gm.N / 2));
-        while ((gm.N / 2) % P.L || (size_t)P.L * P.WS * sizeof(float2) + lds_fixed + P.TS * sizeof(float2) > budget / 2 + 8192) P.L--;     // the row pass walks the image 2 L rows at a time; leave about half of the LDS to the column chunk
-        if (P.L < 1) return fail(-12, "pre-processing kernel: row buffer does not fit the LDS");
-        const size_t wk = (size_t)P.L * P.WS * sizeof(float2);
-        const size_t left = budget - lds_fixed > wk ? budget - lds_fixed - wk : 0;
-        P.nc = std::max(1, std::min(gm.W, (int)(left / (P.TS * sizeof(float2)))));
-        P.nc = std::max(1, std::min(P.nc, 12 * PT / gm.N));        // k_prep prefetches one chunk into 12 registers pairs per thread
-        P.nchunks = (gm.W + P.nc - 1) / P.nc;
-        P.nc = (gm.W + P.nchunks - 1) / P.nchunks;       // even chunks
+    const PrepPlan pl = prep_plan(gm.N, gm.B, gm.W);
+    if (pl.err) return fail(-12, pl.err);
+    P.L = pl.L; P.nc = pl.nc; P.nchunks = pl.nchunks; P.TS = pl.TS; P.WS = pl.WS;
+    P.spill = nullptr;
+    if (!pl.scratch_free) {     // the whole half spectrum goes through a global scratch between the two phases
         if (int rc = spill.ensure((size_t)n_img * gm.N * gm.W)) return rc;
         P.spill = spill.p;
-        lds = ((size_t)P.nc * P.TS + (size_t)P.L * P.WS) * sizeof(float2) + lds_fixed;
-        if (lds > budget) return fail(-12, "pre-processing kernel: LDS plan exceeds its budget");
     }
     static bool attr_set = false;
     std::unique_lock<std::mutex> lk_attr(g_mu);
@@ -69,8 +45,8 @@ static int launch_prep(DevBuf<float2> &spill /* the calling handle's scratch */,
     }
     lk_attr.unlock();
     ProfScope ps(PPM_K_PREP);
-    if (scratch_free) hipLaunchKernelGGL((k_prep<512, 2>), dim3(n_img), dim3(512), lds, cur_stream(), P);
-    else hipLaunchKernelGGL((k_prep<256, 3>), dim3(n_img), dim3(256), lds, cur_stream(), P);
+    if (pl.scratch_free) hipLaunchKernelGGL((k_prep<512, 2>), dim3(n_img), dim3(512), pl.lds.total, cur_stream(), P);
+    else hipLaunchKernelGGL((k_prep<256, 3>), dim3(n_img), dim3(256), pl.lds.total, cur_stream(), P);
     HIPCHK(hipGetLastError());
     return 0;
 }

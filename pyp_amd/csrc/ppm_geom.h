@@ -1,5 +1,5 @@
 // ppm_geom.h — host-side derived geometry of a refinement call (band limits, shift grid,
-// orientation grid, ring-ordered sample list).  Plain C++, no device code.
+// orientation grid, ring-ordered sample list).  Plain C++, no HIP types; the constexpr prep_lds is also called by k_prep on the device.
 //
 // The quantities restate the numeric answers of the refine3d prompt script
 // (src/pyp/refine/frealign/frealign.py:3918-3994) in Fourier-pixel units; the grid is the
@@ -205,6 +205,91 @@ inline int compass_iterations(double ha, double hs, double steptol, int min_iter
     const int T = m > steptol ? (int)std::ceil(std::log(m / steptol) / std::log(2.0)) : min_iters;
     return std::min(12, std::max(min_iters, T));
 }
+// ---- launch plan of the pre-processing kernel (k_prep, ppm_kernels.h): block shape, row pairs per row pass, column chunks and the
+// carve-up of the block's dynamic LDS.  launch_prep (host_refine.h) launches from it and the kernel takes its pointers from the same
+// prep_lds, so the two cannot disagree; tests/test_prep_plan_cpu.py pins the Python restatement of the box sweep to it.
+struct LdsRegion { unsigned off, bytes, elem; };      // byte offset, extent, element size (= the alignment the region needs)
+struct PrepLds {
+    LdsRegion T;        // float2 [nc][TS]  column chunk
+    LdsRegion Wk;       // float2 [L][WS]   row work buffer; shares T's storage on the scratch-free path (the phases alternate)
+    LdsRegion ringq;    // u64 [B+2]        ring power sums, 64-bit fixed point
+    LdsRegion ringc;    // u32 [B+2]        ring sample counts
+    LdsRegion ringpw;   // float [B+2]      ring weights
+    LdsRegion red;      // double [5 waves] block reduction slots of the statistics, 16-byte aligned
+    LdsRegion stat;     // float [4 + waves] mean, scale, fixed-point scale, nI partials
+    LdsRegion fmask;    // float [8]        mask disc (centre, radius), beam-tilt coefficients
+    LdsRegion tw;       // float2 [N]       twiddles of the FFT plan
+    LdsRegion perm;     // u16 [N]          staging position of sample i   (scratch path only: the scratch-free path stages in
+    LdsRegion iperm;    // u16 [N]          sample staged at position d     natural order; both empty there)
+    unsigned total;     // bytes the launch asks for
+};
+constexpr int prep_threads(bool scratch_free) { return scratch_free ? 512 : 256; }
+// the regions in order; `total` is left to prep_lds
+constexpr PrepLds prep_lds_regions(bool scratch_free, int N, int B, int L, int nc, int TS, int WS) {
+    const unsigned waves = prep_threads(scratch_free) / 64, nb = (unsigned)(B + 2), n = (unsigned)N;
+    const unsigned tb = (unsigned)nc * (unsigned)TS * 8, wb = (unsigned)L * (unsigned)WS * 8;
+    PrepLds l = {};
+    l.T = { 0, tb, 8 };
+    l.Wk = { scratch_free ? 0 : tb, wb, 8 };
+    l.ringq = { scratch_free ? (tb > wb ? tb : wb) : tb + wb, nb * 8, 8 };
+    l.ringc = { l.ringq.off + l.ringq.bytes, nb * 4, 4 };
+    l.ringpw = { l.ringc.off + l.ringc.bytes, nb * 4, 4 };
+    l.red = { (l.ringpw.off + l.ringpw.bytes + 15) & ~15u, 5 * waves * 8, 16 };
+    l.stat = { l.red.off + l.red.bytes, (4 + waves) * 4, 4 };
+    l.fmask = { l.stat.off + l.stat.bytes, 8 * 4, 4 };
+    l.tw = { l.fmask.off + l.fmask.bytes, n * 8, 8 };
+    l.perm = { l.tw.off + l.tw.bytes, scratch_free ? 0 : n * 2, 2 };
+    l.iperm = { l.perm.off + l.perm.bytes, scratch_free ? 0 : n * 2, 2 };
+    return l;
+}
+// bytes budgeted behind the two buffers, known before L and nc are: the regions from ringq on as they lie behind empty buffers, 16 for
+// the alignment of `red` behind buffers that end on an odd multiple of 8, and 16 spare
+constexpr unsigned prep_lds_tail(bool scratch_free, int N, int B) {
+    const PrepLds l = prep_lds_regions(scratch_free, N, B, 0, 0, 0, 0);
+    return l.iperm.off + l.iperm.bytes + 16 + 16;
+}
+constexpr PrepLds prep_lds(bool scratch_free, int N, int B, int L, int nc, int TS, int WS) {
+    PrepLds l = prep_lds_regions(scratch_free, N, B, L, nc, TS, WS);
+    l.total = l.ringq.off + prep_lds_tail(scratch_free, N, B);
+    return l;
+}
+struct PrepPlan {
+    bool scratch_free;            // box 256: k_prep<512, 2>; every other box: k_prep<256, 3> through the global scratch
+    int threads, L, nc, nchunks;  // row pairs per row pass, columns per column chunk, chunks
+    int TS, WS;                   // line strides of T and Wk (float2)
+    PrepLds lds;
+    const char *err;              // null, or why box N / band B cannot be planned
+};
+inline PrepPlan prep_plan(int N, int B, int W) {
+    PrepPlan p = {};
+    p.scratch_free = N == 256; p.threads = prep_threads(p.scratch_free);
+    if (p.scratch_free) {     // T (64 columns) and the row buffer (64 row pairs) share one 140 KB region; strides spread over the banks
+        p.TS = 273; p.WS = 272;
+        p.L = 64; p.nc = 64; p.nchunks = (std::min(W, 128) + 63) / 64;
+        p.lds = prep_lds(true, N, B, p.L, p.nc, p.TS, p.WS);
+        if (p.lds.total > 160u * 1024) p.err = "pre-processing kernel: LDS plan exceeds 160 KB";
+        return p;
+    }
+    // L row pairs per row pass (L N <= 8 x threads: the next pass is prefetched into <= 8 register pairs per thread; L divides
+    // N/2) and the nc columns of one column chunk; the whole half spectrum goes through a global scratch between the two phases
+    constexpr size_t budget = 40 * 1024;
+    const size_t tail = prep_lds_tail(false, N, B);
+    p.TS = N + 1; p.WS = N;
+    p.L = std::max(1, std::min(8 * p.threads / N, N / 2));
+    // the row pass walks the image 2 L rows at a time; leave about half of the LDS to the column chunk
+    while (p.L >= 1 && ((N / 2) % p.L || (size_t)p.L * p.WS * 8 + tail + (size_t)p.TS * 8 > budget / 2 + 8192)) p.L--;
+    if (p.L < 1) { p.err = "pre-processing kernel: row buffer does not fit the LDS"; return p; }
+    const size_t wk = (size_t)p.L * p.WS * 8;
+    const size_t left = budget - tail > wk ? budget - tail - wk : 0;
+    p.nc = std::max(1, std::min(W, (int)(left / ((size_t)p.TS * 8))));
+    p.nc = std::max(1, std::min(p.nc, 12 * p.threads / N));      // k_prep prefetches one chunk into 12 register pairs per thread
+    p.nchunks = (W + p.nc - 1) / p.nc;
+    p.nc = (W + p.nchunks - 1) / p.nchunks;                      // even chunks
+    p.lds = prep_lds(false, N, B, p.L, p.nc, p.TS, p.WS);
+    if (p.lds.total > budget) p.err = "pre-processing kernel: LDS plan exceeds its budget";
+    return p;
+}
+
 // SCORE / SIGMA / LOGP columns of a row from its correlation over the band r_lo .. r_hi (Fourier pixels)
 inline void score_columns(double cc, double r_lo, double r_hi, double *score, double *sigma, double *logp) {
     double res = 1.0 - cc * cc; if (res < 1e-6) res = 1e-6;

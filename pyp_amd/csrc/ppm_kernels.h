@@ -12,6 +12,7 @@
 //   finalise         shell statistics, Wiener division, mask and gridding correction
 #pragma once
 #include "ppm_dev.h"
+#include "ppm_geom.h"
 
 namespace ppm {
 
@@ -99,13 +100,11 @@ struct PrepP {
     float Rm2_bg;     // background statistics: pixels with integer r^2 > Rm2_bg = floor(Rm^2 in double), as the oracle's double test
     float focus[4];   // focus mask: sphere centre (pixels from the box centre) and radius in the reference; radius <= 0: centred mask of radius Rm
     int normalize, invert, do_mask, whiten;
-    int nc, nchunks, L;
+    int nc, nchunks, L;   // prep_plan (ppm_geom.h): columns per column chunk, chunks, row pairs per row pass
+    int TS, WS;           // prep_plan: line strides of the column buffer T and of the row work buffer Wk; prep_lds places both
     float2 *band;  // [n][H*W] unscaled band spectrum (scratch; the final result for insertion)
-    int TS, WS;    // line strides of the column buffer T and of the row work buffer Wk (>= 272 on the 256 fast path)
-    int fast256;   // N == 256: register-level 16 x 16 FFT (lds_fft256), natural-order staging
-    int inreg;     // N == 256 (k_prep<512, 2>): the half spectrum stays in registers between the two phases (no global scratch)
     unsigned *band_max; // may be null: bits of max |re|, |im| over the band images of the launch (atomicMax; floats >= 0)
-    float2 *spill; // [n][N][W] row-transformed half spectrum (global scratch between the row and the column phase)
+    float2 *spill; // [n][N][W] row-transformed half spectrum (global scratch between the row and the column phase); null and never read by k_prep<512, 2>
     float *wring;  // [n][B+2] ring weights 1/sqrt(mean power), may be null
     // ring-ordered list outputs (may be null)
     const uint32_t *samples; int S_pad; float2 *Il; float *cw;
@@ -113,55 +112,39 @@ struct PrepP {
     float2 *Wp; float *C2; float *nI; int Bs, Hs; float r_s2, r_lo2;
 };
 
-// Two shapes (launch_prep, ppm_lib.hip), PT threads and MINW waves per SIMD the register allocation has to leave room for:
-//   k_prep<512, 2>  N = 256, the scratch-free path: one block per CU holds the half spectrum in registers between the row and
-//                   the column phase, 16 x 16 register FFTs (lds_fft256), natural-order staging;
-//   k_prep<256, 3>  every other box, the scratch path: the half spectrum goes through a global scratch, mixed-radix FFTs on the
-//                   plan's staging order; <= 40 KB of LDS and 168 VGPRs make three blocks per CU resident, so that one block's
-//                   barrier and global-memory waits overlap the others' FFT work.
-// The path is still taken from P.inreg / P.fast256 at run time (both are "N == 256"); the body is the one the shapes were tuned with.
-template <int PT, int MINW>
-__global__ void __launch_bounds__(PT, MINW) k_prep(PrepP P) {
-    static_assert((PT == 512 && MINW == 2) || (PT == 256 && MINW == 3), "the two shapes launch_prep plans for");
-    constexpr int PW = PT / 64;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, N = P.N, B = P.B, W = P.W, H = P.H;
-    const int p = blockIdx.x;
-    const int TS = P.TS, WS = P.WS;                   // padded line strides (bank spread)
-    float2 *T = (float2 *)smem;                       // [nc][TS] column chunk, followed by
-    constexpr bool kInreg = PT == 512;                // the instantiation that carries the scratch-free path
-    constexpr int HR = PT / 128, NIT = 64 / (HR > 0 ? HR : 1);   // scratch-free path: thread t holds column t & 127 of the rows (t >> 7) + HR it, it < NIT, of every row pass
-    const bool inreg = kInreg && P.inreg;
-    float2 *Wk = inreg ? T : T + (size_t)P.nc * TS;   // [L][WS]  the row work buffer (shares T's storage on the scratch-free path)
-    // ring power sums in 64-bit fixed point and integer counts: a ds_add_f32 costs ~190 LDS cycles per wave-instruction on
-    // gfx950, ds_add_u64 / ds_add_u32 ~8 / ~5 (scripts/micro/lds_atomic_bench.hip)
-    const size_t regionA = inreg ? ((size_t)P.nc * TS > (size_t)P.L * WS ? (size_t)P.nc * TS : (size_t)P.L * WS) : (size_t)P.nc * TS + (size_t)P.L * WS;
-    unsigned long long *ringq = (unsigned long long *)(T + regionA);  // [B+2]
-    unsigned *ringc = (unsigned *)(ringq + (B + 2));  // [B+2]
-    float *ringpw = (float *)(ringc + (B + 2));       // [B+2] ring weights
-    double *red = (double *)(((uintptr_t)(ringpw + (B + 2)) + 15) & ~(uintptr_t)15);  // [PW*4 + PW]
-    float *stat = (float *)(red + PW * 5);            // mu, scale, fixed-point scale, nI partials
-    float *fmask = stat + 4 + PW;                     // mask disc of this particle: centre (pixels from the box centre) and radius; [4], [5]: beam-tilt phase coefficients
-    float2 *tw_s = (float2 *)(stat + 12 + PW);        // [N] twiddles and [N] staging positions of the FFT plan, kept in LDS
-    unsigned short *perm_s = (unsigned short *)(tw_s + N);
-    unsigned short *iperm_s = perm_s + N;             // inverse: the sample that is staged at LDS position d
-    for (int i = tid; i < N; i += PT) {
-        tw_s[i] = P.plan.tw[i];
-        const unsigned short q = P.fast256 ? (unsigned short)i : P.plan.perm[i];
-        perm_s[i] = q; iperm_s[q] = (unsigned short)i;
-    }
-    __syncthreads();
-    const float *img = P.images + (size_t)p * N * N;
+// One block of k_prep = one particle: what its stages share, and the stages.
+template <int PT>
+struct PrepBlock {
+    static constexpr int PW = PT / 64;
+    static constexpr bool kScratchFree = PT == 512;       // the instantiation is the path: <512, 2> scratch-free, <256, 3> scratch
+    const PrepP &P;
+    const int tid, p, N, B, W, H, TS, WS;                 // TS, WS: padded line strides of T and Wk (bank spread)
+    const float *img; float2 *bandp;
+    // LDS regions, placed by prep_lds (ppm_geom.h) as on the host.  Ring power sums in 64-bit fixed point and integer counts: a ds_add_f32
+    // costs ~190 LDS cycles per wave-instruction on gfx950, ds_add_u64 / ds_add_u32 ~8 / ~5 (scripts/micro/lds_atomic_bench.hip)
+    float2 *T, *Wk; unsigned long long *ringq; unsigned *ringc; float *ringpw; double *red; float *stat, *fmask; float2 *tw_s;
+    unsigned short *perm_s, *iperm_s;                     // scratch path only
+    double s1 = 0, s2 = 0, cnt = 0, t1 = 0, t2 = 0;       // partial sums of the statistics: background (sum, squares, count), whole image
+    float mu = 0.f, sc = 1.f, qscale = 1.f, oscale = 1.f; // mean and scale of the pixels, fixed-point scale of the ring sums, scale of the band output
+    float mcx = 0.f, mcy = 0.f, mrad = 0.f, wf;           // mask disc and falloff width
+    float btx = 0.f, bty = 0.f; bool beam_tilt = false;
+    float omax = 0.f;                                     // largest |band| component this thread wrote
 
-    // ---- statistics of the background (outside the mask radius); whole image if that is empty
-    double s1 = 0, s2 = 0, cnt = 0, t1 = 0, t2 = 0;
-    const float Rm2 = P.Rm2_bg;
-    // scratch-free path without a mask: (x - mu) sc only changes the DC term (never used) and the scale, so the statistics are
-    // gathered while the pixels are staged for the row transforms and the scale is applied to the band output: one image read
-    const bool fold = inreg && !P.do_mask;
-    if (!fold) {
+    __device__ __forceinline__ PrepBlock(const PrepP &P_, char *smem)
+        : P(P_), tid(threadIdx.x), p(blockIdx.x), N(P_.N), B(P_.B), W(P_.W), H(P_.H), TS(P_.TS), WS(P_.WS),
+          img(P_.images + (size_t)blockIdx.x * P_.N * P_.N), bandp(P_.band + (size_t)blockIdx.x * P_.H * P_.W), wf(P_.wfall < 1e-3f ? 1e-3f : P_.wfall) {
+        const PrepLds l = prep_lds(kScratchFree, N, B, P.L, P.nc, TS, WS);
+        T = (float2 *)(smem + l.T.off); Wk = (float2 *)(smem + l.Wk.off);
+        ringq = (unsigned long long *)(smem + l.ringq.off); ringc = (unsigned *)(smem + l.ringc.off); ringpw = (float *)(smem + l.ringpw.off);
+        red = (double *)(smem + l.red.off); stat = (float *)(smem + l.stat.off); fmask = (float *)(smem + l.fmask.off);
+        tw_s = (float2 *)(smem + l.tw.off); perm_s = (unsigned short *)(smem + l.perm.off); iperm_s = (unsigned short *)(smem + l.iperm.off);
+    }
+
+    // ---- statistics of the background (outside the mask radius); whole image if that is empty: one pass over the image
+    __device__ __forceinline__ void background_stats() {
+        const float Rm2 = P.Rm2_bg;
         const float invNf = 1.0f / (float)N;
-        const float4 *img4 = (const float4 *)img;          // N even: N^2 is a multiple of 4, every image starts 16-byte aligned
+        const float4 *img4 = (const float4 *)img;        // N even: N^2 is a multiple of 4, every image starts 16-byte aligned
         constexpr int UR = 8;                              // independent 16-byte loads in flight per thread
         const bool rows4 = (N & 3) == 0;                   // then the 4 pixels of a 16-byte load share their image row
         for (int b4 = tid; b4 < N * N / 4; b4 += PT * UR) {
@@ -189,17 +172,18 @@ __global__ void __launch_bounds__(PT, MINW) k_prep(PrepP P) {
             s1 += (double)f1; s2 += (double)f2; cnt += (double)fc; t1 += (double)g1; t2 += (double)g2;
         }
     }
-    auto finish_stats = [&]() {     // block reduction of the partial sums -> stat[0..2] (mean, scale, fixed-point scale) and the mask / beam-tilt constants
-    s1 = wave_sum_d(s1); s2 = wave_sum_d(s2); cnt = wave_sum_d(cnt); t1 = wave_sum_d(t1); t2 = wave_sum_d(t2);
-    if ((tid & 63) == 0) { int w = tid >> 6; red[w * 4] = s1; red[w * 4 + 1] = s2; red[w * 4 + 2] = cnt; red[w * 4 + 3] = t1; }
-    __syncthreads();
-    if (tid == 0) {
-        double a1 = 0, a2 = 0, ac = 0, b1 = 0;
-        for (int w = 0; w < PW; w++) { a1 += red[w * 4]; a2 += red[w * 4 + 1]; ac += red[w * 4 + 2]; b1 += red[w * 4 + 3]; }
-        red[0] = a1; red[1] = a2; red[2] = ac; red[3] = b1;
-    }
-    __syncthreads();
-    {
+
+    // block reduction of the partial sums -> stat[0..2] (mean, scale, fixed-point scale) and fmask (mask disc, beam-tilt constants)
+    __device__ __forceinline__ void finish_stats() {
+        s1 = wave_sum_d(s1); s2 = wave_sum_d(s2); cnt = wave_sum_d(cnt); t1 = wave_sum_d(t1); t2 = wave_sum_d(t2);
+        if ((tid & 63) == 0) { int w = tid >> 6; red[w * 4] = s1; red[w * 4 + 1] = s2; red[w * 4 + 2] = cnt; red[w * 4 + 3] = t1; }
+        __syncthreads();
+        if (tid == 0) {
+            double a1 = 0, a2 = 0, ac = 0, b1 = 0;
+            for (int w = 0; w < PW; w++) { a1 += red[w * 4]; a2 += red[w * 4 + 1]; ac += red[w * 4 + 2]; b1 += red[w * 4 + 3]; }
+            red[0] = a1; red[1] = a2; red[2] = ac; red[3] = b1;
+        }
+        __syncthreads();
         double a1 = red[0], a2 = red[1], ac = red[2], b1 = red[3];
         __syncthreads();
         if ((tid & 63) == 0) red[PW * 4 + (tid >> 6)] = t2;
@@ -239,20 +223,25 @@ __global__ void __launch_bounds__(PT, MINW) k_prep(PrepP P) {
         }
         __syncthreads();
     }
-    };
-    if (!fold) finish_stats();
-    float mu = fold ? 0.f : stat[0], sc = fold ? 1.f : stat[1], qscale = fold ? 1.f : stat[2], oscale = 1.f;    // fold: set after the row passes
-    float mcx = fold ? 0.f : fmask[0], mcy = fold ? 0.f : fmask[1], mrad = fold ? 0.f : fmask[2];
-    float btx = fold ? 0.f : fmask[4], bty = fold ? 0.f : fmask[5];
-    bool beam_tilt = btx != 0.f || bty != 0.f;
-    for (int i = tid; i < B + 2; i += PT) { ringq[i] = 0ull; ringc[i] = 0u; }
 
-    const float wf = P.wfall < 1e-3f ? 1e-3f : P.wfall;
-    float2 *bandp = P.band + (size_t)p * H * W;
-    float2 *sp = P.spill + (size_t)p * N * W;         // [N][W] half spectrum after the row pass (global scratch, L2-resident)
-    float omax = 0.f;
+    // the background pass and its reduction; the pixels are then centred, scaled and masked while they are staged for the row transforms
+    __device__ __forceinline__ void stats_up_front() {
+        background_stats();
+        finish_stats();
+        mu = stat[0]; sc = stat[1]; qscale = stat[2];
+        mcx = fmask[0]; mcy = fmask[1]; mrad = fmask[2];
+        btx = fmask[4]; bty = fmask[5]; beam_tilt = btx != 0.f || bty != 0.f;
+    }
+
+    // weight of pixel (x, y) under the soft-edged mask disc
+    __device__ __forceinline__ float mask_weight(int x, int y) {
+        const float dx = (float)(x - N / 2) - mcx, dy = (float)(y - N / 2) - mcy;
+        const float r = sqrtf(dx * dx + dy * dy);
+        return r >= mrad + 0.5f * wf ? 0.f : (r > mrad - 0.5f * wf ? 0.5f * (1.f + cosf(kPiF * (r - mrad + 0.5f * wf) / wf)) : 1.f);
+    }
+
     // band output of `ncol` transformed columns starting at c0 (in T): origin to the box centre, 1 / N, beam-tilt phase, ring power sums
-    auto emit = [&](int c0, int ncol) {
+    __device__ __forceinline__ void emit(int c0, int ncol) {
         const float inv_ncol = 1.0f / (float)ncol, invN = 1.f / (float)N;
         for (int i = tid; i < ncol * H; i += PT) {
             const int row = fast_div(i, ncol, inv_ncol), c = i - row * ncol, ky = row - B, kx = c0 + c;
@@ -262,7 +251,7 @@ __global__ void __launch_bounds__(PT, MINW) k_prep(PrepP P) {
                 float2 v = T[c * TS + (ky < 0 ? ky + N : ky)];
                 float sg = ((kx + ky) & 1) ? -invN * oscale : invN * oscale;
                 o = make_float2(v.x * sg, v.y * sg);
-                if (beam_tilt) {                                 // remove the beam-tilt phase error: x exp(-i phi)
+                if (beam_tilt) {                               // remove the beam-tilt phase error: x exp(-i phi)
                     float sn, cs;
                     sincosf(k2 * ((float)kx * btx + (float)ky * bty), &sn, &cs);
                     o = make_float2(o.x * cs + o.y * sn, o.y * cs - o.x * sn);
@@ -277,265 +266,289 @@ __global__ void __launch_bounds__(PT, MINW) k_prep(PrepP P) {
             }
             bandp[row * W + kx] = o;
         }
-    };
-    auto mask_px = [&](int x, int y) {
-        const float dx = (float)(x - N / 2) - mcx, dy = (float)(y - N / 2) - mcy;
-        const float r = sqrtf(dx * dx + dy * dy);
-        return r >= mrad + 0.5f * wf ? 0.f : (r > mrad - 0.5f * wf ? 0.5f * (1.f + cosf(kPiF * (r - mrad + 0.5f * wf) / wf)) : 1.f);
-    };
-    bool done = false;
-    if constexpr (kInreg) {
-        if (inreg) {
-            // ---- scratch-free path (N = 256, 512 threads): two row passes of 64 row pairs through LDS; thread t then HOLDS column
-            // t & 127 of the half spectrum for the rows 128 pass + 2 ((t >> 7) + 4 it) + {0, 1}: 64 complex values in registers.
-            // The column pass assembles 64 columns at a time in LDS from those registers.  kx = 128 (and everything beyond the
-            // band) is zero in the output, so 128 columns are all that is ever held.
-            float2 holdA[NIT][2], holdB[NIT][2];     // pass 0 / pass 1 (two arrays: each small enough to be promoted to registers)
+    }
+
+    // ---- scratch-free row + column phase (N = 256, 512 threads): two row passes of 64 row pairs through LDS; thread t then HOLDS column
+    // t & 127 of the half spectrum for the rows 128 pass + 2 ((t >> 7) + 4 it) + {0, 1}: 64 complex values in registers.  The column
+    // pass assembles 64 columns at a time in LDS from those registers.  kx = 128 (and everything beyond the band) is zero in the output,
+    // so 128 columns are all that is ever held.
+    // Without a mask (`fold`), (x - mu) sc only changes the DC term (never used) and the scale, so the statistics are gathered while the
+    // pixels are staged for the row transforms and the scale is applied to the band output: one image read.
+    __device__ __forceinline__ void scratch_free_phases(const bool fold) {
+        constexpr int HR = PT / 128, NIT = 64 / HR;       // thread t holds column t & 127 of the rows (t >> 7) + HR it, it < NIT, of every row pass
+        const float Rm2 = P.Rm2_bg;
+        float2 holdA[NIT][2], holdB[NIT][2];              // pass 0 / pass 1 (two arrays: each small enough to be promoted to registers)
 #pragma unroll
-            for (int pass = 0; pass < 2; pass++) {
-                const int y0 = 128 * pass;
-                lds_barrier();                                   // the previous pass has been read out
+        for (int pass = 0; pass < 2; pass++) {
+            const int y0 = 128 * pass;
+            lds_barrier();                                   // the previous pass has been read out
 #pragma unroll 2
-                for (int k = 0; k < 4096 / PT; k++) {            // 64 row pairs x 64 float4 = 4096 pairs of loads over the block's threads
-                    const int i4 = tid + k * PT, l = i4 >> 6, x = 4 * (i4 & 63), ya = y0 + 2 * l, yb = ya + 1;
-                    const float4 qa = *(const float4 *)(img + ya * N + x), qb = *(const float4 *)(img + yb * N + x);
-                    const float ra[4] = { qa.x, qa.y, qa.z, qa.w }, rb[4] = { qb.x, qb.y, qb.z, qb.w };
-                    float f1 = 0.f, f2 = 0.f, fc = 0.f, g1 = 0.f, g2 = 0.f;
+            for (int k = 0; k < 4096 / PT; k++) {            // 64 row pairs x 64 float4 = 4096 pairs of loads over the block's threads
+                const int i4 = tid + k * PT, l = i4 >> 6, x = 4 * (i4 & 63), ya = y0 + 2 * l, yb = ya + 1;
+                const float4 qa = *(const float4 *)(img + ya * N + x), qb = *(const float4 *)(img + yb * N + x);
+                const float ra[4] = { qa.x, qa.y, qa.z, qa.w }, rb[4] = { qb.x, qb.y, qb.z, qb.w };
+                float f1 = 0.f, f2 = 0.f, fc = 0.f, g1 = 0.f, g2 = 0.f;
 #pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        float va = (ra[j] - mu) * sc, vb = (rb[j] - mu) * sc;
-                        if (P.do_mask) { va *= mask_px(x + j, ya); vb *= mask_px(x + j, yb); }
-                        Wk[l * WS + x + j] = make_float2(va, vb);
-                        if (fold) {
-                            const float dx = (float)(x + j - N / 2), dya = (float)(ya - N / 2), dyb = dya + 1.f;
-                            g1 += va + vb; g2 = fmaf(va, va, fmaf(vb, vb, g2));
-                            if (dx * dx + dya * dya > Rm2) { f1 += va; f2 = fmaf(va, va, f2); fc += 1.f; }
-                            if (dx * dx + dyb * dyb > Rm2) { f1 += vb; f2 = fmaf(vb, vb, f2); fc += 1.f; }
-                        }
+                for (int j = 0; j < 4; j++) {
+                    float va = (ra[j] - mu) * sc, vb = (rb[j] - mu) * sc;
+                    if (P.do_mask) { va *= mask_weight(x + j, ya); vb *= mask_weight(x + j, yb); }
+                    Wk[l * WS + x + j] = make_float2(va, vb);
+                    if (fold) {
+                        const float dx = (float)(x + j - N / 2), dya = (float)(ya - N / 2), dyb = dya + 1.f;
+                        g1 += va + vb; g2 = fmaf(va, va, fmaf(vb, vb, g2));
+                        if (dx * dx + dya * dya > Rm2) { f1 += va; f2 = fmaf(va, va, f2); fc += 1.f; }
+                        if (dx * dx + dyb * dyb > Rm2) { f1 += vb; f2 = fmaf(vb, vb, f2); fc += 1.f; }
                     }
-                    if (fold) { s1 += (double)f1; s2 += (double)f2; cnt += (double)fc; t1 += (double)g1; t2 += (double)g2; }
                 }
-                lds_fft256(Wk, 64, WS, tid, PT, tw_s);
-#pragma unroll
-                for (int it = 0; it < NIT; it++) {
-                    const int l = (tid >> 7) + HR * it, kx = tid & 127;
-                    const float2 z = Wk[l * WS + kx], zc = Wk[l * WS + (kx ? N - kx : 0)];
-                    const float2 d = make_float2(z.x - zc.x, z.y + zc.y);
-                    const float2 xa = make_float2(0.5f * (z.x + zc.x), 0.5f * (z.y - zc.y)), xb = make_float2(0.5f * d.y, -0.5f * d.x);
-                    if (pass == 0) { holdA[it][0] = xa; holdA[it][1] = xb; } else { holdB[it][0] = xa; holdB[it][1] = xb; }
-                }
+                if (fold) { s1 += (double)f1; s2 += (double)f2; cnt += (double)fc; t1 += (double)g1; t2 += (double)g2; }
             }
-            if (fold) {                                          // the statistics are complete: scales for the output
-                lds_barrier();
-                finish_stats();
-                oscale = stat[1]; qscale = stat[2];
-                btx = fmask[4]; bty = fmask[5]; beam_tilt = btx != 0.f || bty != 0.f;
-            }
-            const int ncols = W < 128 ? W : 128;
-            for (int c0 = 0; c0 < ncols; c0 += 64) {
-                const int ncol = ncols - c0 < 64 ? ncols - c0 : 64;
-                lds_barrier();
-                const int kx = tid & 127;
-                if (kx >= c0 && kx < c0 + ncol) {
+            lds_fft256(Wk, 64, WS, tid, PT, tw_s);
 #pragma unroll
-                    for (int pass = 0; pass < 2; pass++)
-#pragma unroll
-                        for (int it = 0; it < NIT; it++) {
-                            const int y = 128 * pass + 2 * ((tid >> 7) + HR * it);
-                            T[(kx - c0) * TS + y] = pass == 0 ? holdA[it][0] : holdB[it][0];
-                            T[(kx - c0) * TS + y + 1] = pass == 0 ? holdA[it][1] : holdB[it][1];
-                        }
-                }
-                lds_fft256(T, ncol, TS, tid, PT, tw_s);
-                emit(c0, ncol);
+            for (int it = 0; it < NIT; it++) {
+                const int l = (tid >> 7) + HR * it, kx = tid & 127;
+                const float2 z = Wk[l * WS + kx], zc = Wk[l * WS + (kx ? N - kx : 0)];
+                const float2 d = make_float2(z.x - zc.x, z.y + zc.y);
+                const float2 xa = make_float2(0.5f * (z.x + zc.x), 0.5f * (z.y - zc.y)), xb = make_float2(0.5f * d.y, -0.5f * d.x);
+                if (pass == 0) { holdA[it][0] = xa; holdA[it][1] = xb; } else { holdB[it][0] = xa; holdB[it][1] = xb; }
             }
-            for (int i = tid; i < (W - ncols) * H; i += PT)       // columns the band never reaches (kx = 128)
-                bandp[(i / (W - ncols)) * W + ncols + i % (W - ncols)] = make_float2(0.f, 0.f);
-            done = true;
         }
+        if (fold) {                                          // the statistics are complete: scales for the output
+            lds_barrier();
+            finish_stats();
+            oscale = stat[1]; qscale = stat[2];
+            btx = fmask[4]; bty = fmask[5]; beam_tilt = btx != 0.f || bty != 0.f;
+        }
+        const int ncols = W < 128 ? W : 128;
+        for (int c0 = 0; c0 < ncols; c0 += 64) {
+            const int ncol = ncols - c0 < 64 ? ncols - c0 : 64;
+            lds_barrier();
+            const int kx = tid & 127;
+            if (kx >= c0 && kx < c0 + ncol) {
+#pragma unroll
+                for (int pass = 0; pass < 2; pass++)
+#pragma unroll
+                    for (int it = 0; it < NIT; it++) {
+                        const int y = 128 * pass + 2 * ((tid >> 7) + HR * it);
+                        T[(kx - c0) * TS + y] = pass == 0 ? holdA[it][0] : holdB[it][0];
+                        T[(kx - c0) * TS + y + 1] = pass == 0 ? holdA[it][1] : holdB[it][1];
+                    }
+            }
+            lds_fft256(T, ncol, TS, tid, PT, tw_s);
+            emit(c0, ncol);
+        }
+        for (int i = tid; i < (W - ncols) * H; i += PT)       // columns the band never reaches (kx = 128)
+            bandp[(i / (W - ncols)) * W + ncols + i % (W - ncols)] = make_float2(0.f, 0.f);
     }
-    if (!done) {
-    // ---- row pass: two real rows per complex transform; every row of the half spectrum goes to the scratch
-    {
-        {
-            // the pixels of the NEXT pass are fetched into registers while this pass runs its FFT (host: L N <= 8 PT).
-            // N % 4 == 0: 16-byte loads of 4 consecutive pixels of both rows, staged at their plan positions; otherwise
-            // 4-byte loads gathered so that consecutive lanes write consecutive LDS positions.
-            constexpr int MAXI = 8;
-            float2 pre[MAXI];
-            float4 pa[MAXI / 4], pb[MAXI / 4];
-            const float invNf = 1.0f / (float)N, invN4 = 4.0f / (float)N;
-            const bool wide = (N & 3) == 0;
-            auto mask_at = [&](int x, int y) {
-                const float dx = (float)(x - N / 2) - mcx, dy = (float)(y - N / 2) - mcy;
-                const float r = sqrtf(dx * dx + dy * dy);
-                return r >= mrad + 0.5f * wf ? 0.f : (r > mrad - 0.5f * wf ? 0.5f * (1.f + cosf(kPiF * (r - mrad + 0.5f * wf) / wf)) : 1.f);
-            };
-            auto fetch = [&](int y0) {
-                if (wide) {
+
+    // ---- scratch row phase: two real rows per complex transform; every row of the half spectrum goes to the scratch `sp`, [N][W]
+    __device__ __forceinline__ void row_phase(float2 *sp) {
+        // the pixels of the NEXT pass are fetched into registers while this pass runs its FFT (host: L N <= 8 PT).
+        // N % 4 == 0: 16-byte loads of 4 consecutive pixels of both rows, staged at their plan positions; otherwise
+        // 4-byte loads gathered so that consecutive lanes write consecutive LDS positions.
+        constexpr int MAXI = 8;
+        float2 pre[MAXI];
+        float4 pa[MAXI / 4], pb[MAXI / 4];
+        const float invNf = 1.0f / (float)N, invN4 = 4.0f / (float)N;
+        const bool wide = (N & 3) == 0;
+        auto fetch = [&](int y0) {
+            if (wide) {
 #pragma unroll
-                    for (int k = 0; k < MAXI / 4; k++) {
-                        const int i4 = tid + k * PT;
-                        if (i4 < P.L * N / 4) {
-                            const int l = fast_div(i4, N / 4, invN4), x = 4 * (i4 - l * (N / 4)), ya = y0 + 2 * l;
-                            pa[k] = *(const float4 *)(img + ya * N + x); pb[k] = *(const float4 *)(img + (ya + 1) * N + x);
-                        }
+                for (int k = 0; k < MAXI / 4; k++) {
+                    const int i4 = tid + k * PT;
+                    if (i4 < P.L * N / 4) {
+                        const int l = fast_div(i4, N / 4, invN4), x = 4 * (i4 - l * (N / 4)), ya = y0 + 2 * l;
+                        pa[k] = *(const float4 *)(img + ya * N + x); pb[k] = *(const float4 *)(img + (ya + 1) * N + x);
                     }
-                } else {
+                }
+            } else {
 #pragma unroll
-                    for (int k = 0; k < MAXI; k++) {
-                        const int i = tid + k * PT;
-                        if (i < P.L * N) {
-                            const int l = fast_div(i, N, invNf), d = i - l * N, x = iperm_s[d], ya = y0 + 2 * l;
-                            pre[k] = make_float2(img[ya * N + x], img[(ya + 1) * N + x]);
+                for (int k = 0; k < MAXI; k++) {
+                    const int i = tid + k * PT;
+                    if (i < P.L * N) {
+                        const int l = fast_div(i, N, invNf), d = i - l * N, x = iperm_s[d], ya = y0 + 2 * l;
+                        pre[k] = make_float2(img[ya * N + x], img[(ya + 1) * N + x]);
+                    }
+                }
+            }
+        };
+        fetch(0);
+        for (int y0 = 0; y0 < N; y0 += 2 * P.L) {
+            lds_barrier();
+            if (wide) {
+#pragma unroll
+                for (int k = 0; k < MAXI / 4; k++) {
+                    const int i4 = tid + k * PT;
+                    if (i4 < P.L * N / 4) {
+                        const int l = fast_div(i4, N / 4, invN4), x = 4 * (i4 - l * (N / 4));
+                        const int ya = y0 + 2 * l, yb = ya + 1;
+                        const float ra[4] = { pa[k].x, pa[k].y, pa[k].z, pa[k].w }, rb[4] = { pb[k].x, pb[k].y, pb[k].z, pb[k].w };
+#pragma unroll
+                        for (int j = 0; j < 4; j++) {
+                            float va = (ra[j] - mu) * sc, vb = (rb[j] - mu) * sc;
+                            if (P.do_mask) { va *= mask_weight(x + j, ya); vb *= mask_weight(x + j, yb); }
+                            Wk[l * WS + perm_s[x + j]] = make_float2(va, vb);
                         }
                     }
                 }
-            };
-            fetch(0);
-            for (int y0 = 0; y0 < N; y0 += 2 * P.L) {
-                lds_barrier();
-                if (wide) {
+            } else {
 #pragma unroll
-                    for (int k = 0; k < MAXI / 4; k++) {
-                        const int i4 = tid + k * PT;
-                        if (i4 < P.L * N / 4) {
-                            const int l = fast_div(i4, N / 4, invN4), x = 4 * (i4 - l * (N / 4));
-                            const int ya = y0 + 2 * l, yb = ya + 1;
-                            const float ra[4] = { pa[k].x, pa[k].y, pa[k].z, pa[k].w }, rb[4] = { pb[k].x, pb[k].y, pb[k].z, pb[k].w };
-#pragma unroll
-                            for (int j = 0; j < 4; j++) {
-                                float va = (ra[j] - mu) * sc, vb = (rb[j] - mu) * sc;
-                                if (P.do_mask) { va *= mask_at(x + j, ya); vb *= mask_at(x + j, yb); }
-                                Wk[l * WS + perm_s[x + j]] = make_float2(va, vb);
-                            }
-                        }
-                    }
-                } else {
-#pragma unroll
-                    for (int k = 0; k < MAXI; k++) {
-                        const int i = tid + k * PT;
-                        if (i < P.L * N) {
-                            const int l = fast_div(i, N, invNf), d = i - l * N, x = iperm_s[d];
-                            const int ya = y0 + 2 * l, yb = ya + 1;
-                            float va = (pre[k].x - mu) * sc, vb = (pre[k].y - mu) * sc;
-                            if (P.do_mask) { va *= mask_at(x, ya); vb *= mask_at(x, yb); }
-                            Wk[l * WS + d] = make_float2(va, vb);
-                        }
+                for (int k = 0; k < MAXI; k++) {
+                    const int i = tid + k * PT;
+                    if (i < P.L * N) {
+                        const int l = fast_div(i, N, invNf), d = i - l * N, x = iperm_s[d];
+                        const int ya = y0 + 2 * l, yb = ya + 1;
+                        float va = (pre[k].x - mu) * sc, vb = (pre[k].y - mu) * sc;
+                        if (P.do_mask) { va *= mask_weight(x, ya); vb *= mask_weight(x, yb); }
+                        Wk[l * WS + d] = make_float2(va, vb);
                     }
                 }
-                if (y0 + 2 * P.L < N) fetch(y0 + 2 * P.L);
-                if (P.fast256) lds_fft256(Wk, P.L, WS, tid, PT, tw_s);
-                else lds_fft(Wk, P.plan, P.L, WS, false, tid, PT, tw_s);
-                const float invW = 1.0f / (float)W;
-                for (int i = tid; i < P.L * W; i += PT) {
-                    const int l = fast_div(i, W, invW), kx = i - l * W;
-                    float2 z = Wk[l * WS + kx], zc = Wk[l * WS + (kx ? N - kx : 0)];
-                    float2 xa = make_float2(0.5f * (z.x + zc.x), 0.5f * (z.y - zc.y));
-                    float2 d = make_float2(z.x - zc.x, z.y + zc.y);
-                    float2 xb = make_float2(0.5f * d.y, -0.5f * d.x);
-                    const int ya = y0 + 2 * l;
-                    sp[(size_t)ya * W + kx] = xa;
-                    sp[(size_t)(ya + 1) * W + kx] = xb;
-                }
+            }
+            if (y0 + 2 * P.L < N) fetch(y0 + 2 * P.L);
+            lds_fft(Wk, P.plan, P.L, WS, false, tid, PT, tw_s);
+            const float invW = 1.0f / (float)W;
+            for (int i = tid; i < P.L * W; i += PT) {
+                const int l = fast_div(i, W, invW), kx = i - l * W;
+                float2 z = Wk[l * WS + kx], zc = Wk[l * WS + (kx ? N - kx : 0)];
+                float2 xa = make_float2(0.5f * (z.x + zc.x), 0.5f * (z.y - zc.y));
+                float2 d = make_float2(z.x - zc.x, z.y + zc.y);
+                float2 xb = make_float2(0.5f * d.y, -0.5f * d.x);
+                const int ya = y0 + 2 * l;
+                sp[(size_t)ya * W + kx] = xa;
+                sp[(size_t)(ya + 1) * W + kx] = xb;
             }
         }
     }
-    __threadfence_block();
-    __syncthreads();                                  // the scratch rows written above are read by other threads below
-    // the NEXT chunk's columns are fetched into registers while this chunk is transformed (host: N nc <= MAXC threads)
-    constexpr int MAXC = 12;
-    float2 nx[MAXC];
-    auto fetch_chunk = [&](int ch) {
-        const int c0 = ch * P.nc, ncol = (W - c0) < P.nc ? (W - c0) : P.nc;
-        const float inv_ncol = 1.0f / (float)ncol;
+
+    // ---- scratch column phase: the half spectrum comes back from `sp` one chunk of P.nc columns at a time, is transformed and emitted
+    __device__ __forceinline__ void column_phase(const float2 *sp) {
+        // the NEXT chunk's columns are fetched into registers while this chunk is transformed (host: N nc <= MAXC threads)
+        constexpr int MAXC = 12;
+        float2 nx[MAXC];
+        auto fetch_chunk = [&](int ch) {
+            const int c0 = ch * P.nc, ncol = (W - c0) < P.nc ? (W - c0) : P.nc;
+            const float inv_ncol = 1.0f / (float)ncol;
 #pragma unroll
-        for (int k = 0; k < MAXC; k++) {
-            const int i = tid + k * PT;
-            if (i < N * ncol) {
-                const int y = fast_div(i, ncol, inv_ncol), c = i - y * ncol;
-                nx[k] = sp[(size_t)y * W + c0 + c];
+            for (int k = 0; k < MAXC; k++) {
+                const int i = tid + k * PT;
+                if (i < N * ncol) {
+                    const int y = fast_div(i, ncol, inv_ncol), c = i - y * ncol;
+                    nx[k] = sp[(size_t)y * W + c0 + c];
+                }
             }
-        }
-    };
-    fetch_chunk(0);
-    for (int ch = 0; ch < P.nchunks; ch++) {
-        const int c0 = ch * P.nc, ncol = (W - c0) < P.nc ? (W - c0) : P.nc;
-        const float inv_ncol = 1.0f / (float)ncol;
-        lds_barrier();
+        };
+        fetch_chunk(0);
+        for (int ch = 0; ch < P.nchunks; ch++) {
+            const int c0 = ch * P.nc, ncol = (W - c0) < P.nc ? (W - c0) : P.nc;
+            const float inv_ncol = 1.0f / (float)ncol;
+            lds_barrier();
 #pragma unroll
-        for (int k = 0; k < MAXC; k++) {                 // this chunk's columns, staged at their plan positions
-            const int i = tid + k * PT;
-            if (i < N * ncol) {
-                const int y = fast_div(i, ncol, inv_ncol), c = i - y * ncol;
-                T[c * TS + perm_s[y]] = nx[k];
+            for (int k = 0; k < MAXC; k++) {                 // this chunk's columns, staged at their plan positions
+                const int i = tid + k * PT;
+                if (i < N * ncol) {
+                    const int y = fast_div(i, ncol, inv_ncol), c = i - y * ncol;
+                    T[c * TS + perm_s[y]] = nx[k];
+                }
             }
+            if (ch + 1 < P.nchunks) fetch_chunk(ch + 1);
+            lds_fft(T, P.plan, ncol, TS, false, tid, PT, tw_s);
+            emit(c0, ncol);
         }
-        if (ch + 1 < P.nchunks) fetch_chunk(ch + 1);
-        // ---- column pass
-        if (P.fast256) lds_fft256(T, ncol, TS, tid, PT, tw_s);
-        else lds_fft(T, P.plan, ncol, TS, false, tid, PT, tw_s);
-        emit(c0, ncol);
     }
+
+    // ---- outputs: ring weights (P.wring; kept in ringpw for the rest), the ring-ordered lists Il / cw, the search tables Wp / C2 / nI
+    __device__ __forceinline__ void outputs() {
+        for (int b = tid; b < B + 2; b += PT) {
+            float pw = ringc[b] > 0u ? (float)((double)ringq[b] / (double)qscale / (double)ringc[b]) : 0.f;
+            float wgt = P.whiten ? (pw > 0.f ? rsqrtf(pw) : 0.f) : 1.f;
+            ringpw[b] = wgt;
+            if (P.wring) P.wring[(size_t)p * (B + 2) + b] = wgt;
+        }
+        __syncthreads();
+        CtfP ctf = ctf_from_row(P.rows + (size_t)p * PPM_NCOL, N, (double)P.a);
+        if (P.Il) {
+            float2 *Ilp = P.Il + (size_t)p * P.S_pad;
+            float *cwp = P.cw + (size_t)p * P.S_pad;
+            for (int s = tid; s < P.S_pad; s += PT) {
+                int kx, ky, al, ring;
+                unpack_sample(P.samples[s], kx, ky, al, ring);
+                float2 v = make_float2(0.f, 0.f); float c = 0.f;
+                if (al) {
+                    float wgt = ringpw[ring];
+                    float2 u = bandp[(ky + B) * W + kx];
+                    v = make_float2(u.x * wgt, u.y * wgt);
+                    c = ctf_eval(ctf, kx, ky) * wgt;
+                }
+                Ilp[s] = v; cwp[s] = c;
+            }
+        }
+        if (P.Wp) {
+            float2 *Wpp = P.Wp + (size_t)p * P.Hs * 64;
+            float *C2p = P.C2 + (size_t)p * P.Hs * 64;
+            float ni = 0.f;
+            for (int i = tid; i < P.Hs * 64; i += PT) {
+                int kx = i & 63, ky = (i >> 6) - P.Bs;
+                float k2 = (float)(kx * kx + ky * ky);
+                float2 wv = make_float2(0.f, 0.f); float c2 = 0.f;
+                if (kx <= P.Bs && k2 < P.r_s2 && k2 >= P.r_lo2 && k2 > 0.f) {
+                    int b = (int)floorf(sqrtf(k2));
+                    float wgt = ringpw[b], al = kx == 0 ? 1.f : 2.f;
+                    float2 u = bandp[(ky + B) * W + kx];
+                    float2 v = make_float2(u.x * wgt, u.y * wgt);
+                    float c = ctf_eval(ctf, kx, ky) * wgt;
+                    wv = make_float2(al * c * v.x, al * c * v.y);
+                    c2 = al * c * c;
+                    ni += al * (v.x * v.x + v.y * v.y);
+                }
+                Wpp[i] = wv; C2p[i] = c2;
+            }
+            ni = wave_sum(ni);
+            __syncthreads();
+            if ((tid & 63) == 0) stat[3 + (tid >> 6)] = ni;
+            __syncthreads();
+            if (tid == 0) { float t = 0.f; for (int w = 0; w < PW; w++) t += stat[3 + w]; P.nI[p] = t; }
+        }
+    }
+};
+
+// Two shapes (launch_prep, host_refine.h; planned by prep_plan, ppm_geom.h), PT threads and MINW waves per SIMD the register
+// allocation has to leave room for.  The instantiation is the path:
+//   k_prep<512, 2>  N = 256, the scratch-free path: one block per CU holds the half spectrum in registers between the row and
+//                   the column phase, 16 x 16 register FFTs (lds_fft256), natural-order staging;
+//   k_prep<256, 3>  every other box, the scratch path: the half spectrum goes through a global scratch, mixed-radix FFTs on the
+//                   plan's staging order; <= 40 KB of LDS and <= 168 VGPRs (166 in this build) make three blocks per CU resident, so that one block's
+//                   barrier and global-memory waits overlap the others' FFT work.
+template <int PT, int MINW>
+__global__ void __launch_bounds__(PT, MINW) k_prep(PrepP P) {
+    static_assert((PT == 512 && MINW == 2) || (PT == 256 && MINW == 3), "the two shapes launch_prep plans for");
+    constexpr bool kScratchFree = PrepBlock<PT>::kScratchFree;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    PrepBlock<PT> K(P, smem);
+    const int tid = K.tid;
+    for (int i = tid; i < P.N; i += PT) {             // [N] twiddles and, on the scratch path, [N] staging positions of the FFT plan, kept in LDS
+        K.tw_s[i] = P.plan.tw[i];
+        if constexpr (!kScratchFree) { const unsigned short q = P.plan.perm[i]; K.perm_s[i] = q; K.iperm_s[q] = (unsigned short)i; }
+    }
+    __syncthreads();
+    // scratch-free path without a mask: the statistics are folded into the row passes (scratch_free_phases)
+    const bool fold = kScratchFree && !P.do_mask;
+    if (!fold) K.stats_up_front();
+    for (int i = tid; i < P.B + 2; i += PT) { K.ringq[i] = 0ull; K.ringc[i] = 0u; }
+    if constexpr (kScratchFree) K.scratch_free_phases(fold);
+    else {
+        float2 *sp = P.spill + (size_t)K.p * P.N * P.W;   // [N][W] half spectrum after the row phase (global scratch, L2-resident)
+        K.row_phase(sp);
+        __threadfence_block();
+        __syncthreads();                              // the scratch rows written above are read by other threads below
+        K.column_phase(sp);
     }
     if (P.band_max) {
 #pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) omax = fmaxf(omax, __shfl_xor(omax, o, 64));
-        if ((tid & 63) == 0 && omax > 0.f && omax < 3.0e38f) atomicMax(P.band_max, __float_as_uint(omax));
+        for (int o = 32; o >= 1; o >>= 1) K.omax = fmaxf(K.omax, __shfl_xor(K.omax, o, 64));
+        if ((tid & 63) == 0 && K.omax > 0.f && K.omax < 3.0e38f) atomicMax(P.band_max, __float_as_uint(K.omax));
     }
     __threadfence_block();
     __syncthreads();
-    // ---- ring weights (re-using ringpw as the weight table)
-    for (int b = tid; b < B + 2; b += PT) {
-        float pw = ringc[b] > 0u ? (float)((double)ringq[b] / (double)qscale / (double)ringc[b]) : 0.f;
-        float wgt = P.whiten ? (pw > 0.f ? rsqrtf(pw) : 0.f) : 1.f;
-        ringpw[b] = wgt;
-        if (P.wring) P.wring[(size_t)p * (B + 2) + b] = wgt;
-    }
-    __syncthreads();
-    CtfP ctf = ctf_from_row(P.rows + (size_t)p * PPM_NCOL, N, (double)P.a);
-    if (P.Il) {
-        float2 *Ilp = P.Il + (size_t)p * P.S_pad;
-        float *cwp = P.cw + (size_t)p * P.S_pad;
-        for (int s = tid; s < P.S_pad; s += PT) {
-            int kx, ky, al, ring;
-            unpack_sample(P.samples[s], kx, ky, al, ring);
-            float2 v = make_float2(0.f, 0.f); float c = 0.f;
-            if (al) {
-                float wgt = ringpw[ring];
-                float2 u = bandp[(ky + B) * W + kx];
-                v = make_float2(u.x * wgt, u.y * wgt);
-                c = ctf_eval(ctf, kx, ky) * wgt;
-            }
-            Ilp[s] = v; cwp[s] = c;
-        }
-    }
-    if (P.Wp) {
-        float2 *Wpp = P.Wp + (size_t)p * P.Hs * 64;
-        float *C2p = P.C2 + (size_t)p * P.Hs * 64;
-        float ni = 0.f;
-        for (int i = tid; i < P.Hs * 64; i += PT) {
-            int kx = i & 63, ky = (i >> 6) - P.Bs;
-            float k2 = (float)(kx * kx + ky * ky);
-            float2 wv = make_float2(0.f, 0.f); float c2 = 0.f;
-            if (kx <= P.Bs && k2 < P.r_s2 && k2 >= P.r_lo2 && k2 > 0.f) {
-                int b = (int)floorf(sqrtf(k2));
-                float wgt = ringpw[b], al = kx == 0 ? 1.f : 2.f;
-                float2 u = bandp[(ky + B) * W + kx];
-                float2 v = make_float2(u.x * wgt, u.y * wgt);
-                float c = ctf_eval(ctf, kx, ky) * wgt;
-                wv = make_float2(al * c * v.x, al * c * v.y);
-                c2 = al * c * c;
-                ni += al * (v.x * v.x + v.y * v.y);
-            }
-            Wpp[i] = wv; C2p[i] = c2;
-        }
-        ni = wave_sum(ni);
-        __syncthreads();
-        if ((tid & 63) == 0) stat[3 + (tid >> 6)] = ni;
-        __syncthreads();
-        if (tid == 0) { float t = 0.f; for (int w = 0; w < PW; w++) t += stat[3 + w]; P.nI[p] = t; }
-    }
+    K.outputs();
 }
 
 // ---------------------------------------------------------------------------------- slice bank

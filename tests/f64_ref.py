@@ -480,3 +480,34 @@ def ssnr_tolerance(stats, fsc_tol, rel_tol):
     ok = rec > 0
     ratio = np.interp(np.arange(len(rec)), np.flatnonzero(ok), part[ok] / rec[ok]) if ok.any() else np.ones_like(rec)
     return drec + rel_tol * np.abs(rec), drec * ratio + rel_tol * np.abs(part)
+
+
+# ------------------------------------------------------------------------------------------- k_prep launch plan
+SEARCH_ABOVE_256 = (270, 294, 384, 486, 490, 500, 512)   # search-path boxes above 256 of the box sweep: L = 5, 3, 4, 3, 1, 2, 2 below
+
+
+def prep_plan(N, B):
+    """The column-chunk plan launch_prep (pyp_amd/csrc/host_refine.h) launches with for box N and band half-width B on its default
+    path (256 threads, 40 KB of LDS): row pairs L (divides N/2), chunk width nc, chunk count and the last chunk's width.
+    lds_fixed = 16 (B + 2) + 16 + 5 x 4 x 8 + (12 + 4) x 4 + 12 N + 16 bytes; L = min(2048 / N, N / 2), lowered until it
+    divides N/2 and L N 8 + lds_fixed + 8 (N + 1) <= 20 KB + 8 KB; nc = min(W, (40 KB - lds_fixed - L N 8) / (8 (N + 1)),
+    3072 / N); chunks = ceil(W / nc), then nc = ceil(W / chunks) (even chunks), W = B + 1.  Last: the LDS bytes of the launch,
+    8 (nc (N + 1) + L N) + lds_fixed.  tests/test_prep_plan_cpu.py holds this restatement to prep_plan of pyp_amd/csrc/ppm_geom.h."""
+    lds_fixed = (B + 2) * 16 + 16 + 5 * 4 * 8 + (12 + 4) * 4 + N * 12 + 16
+    W = B + 1
+    L = max(1, min(2048 // N, N // 2))
+    while (N // 2) % L or L * N * 8 + lds_fixed + (N + 1) * 8 > 20 * 1024 + 8192:
+        L -= 1
+    left = max(0, 40 * 1024 - lds_fixed - L * N * 8)
+    nc = max(1, min(W, left // ((N + 1) * 8), 3072 // N))
+    nch = -(-W // nc)
+    nc = -(-W // nch)
+    return L, nc, nch, W - (nch - 1) * nc, 8 * (nc * (N + 1) + L * N) + lds_fixed
+
+
+def ragged_band(N):
+    """Band half-width whose last k_prep column chunk is narrowest (a single column wherever the plan allows one, i.e. at
+    boxes of 240 and up; below, chunks are as wide as 3072 / N and evening them leaves no one-column remainder), the widest
+    such band."""
+    best = min(range(8, N // 2), key=lambda B: (prep_plan(N, B)[3], -B))
+    return best

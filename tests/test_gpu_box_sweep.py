@@ -26,9 +26,10 @@ pytestmark = pytest.mark.gpu
 BOXES = R.supported_boxes()
 ANG_TOL_DEG, SHIFT_TOL_PX = 0.1, 0.5                 # BASELINE.json north_star
 MAPS_ABOVE_256 = (270, 324, 512)                      # maps of leg A above 256 (time budget: a float64 map costs ~N^3 log N)
-SEARCH_ABOVE_256 = (270, 294, 384, 486, 490, 500, 512)   # leg B above 256: the distinct k_prep plans (see prep_plan)
+SEARCH_ABOVE_256 = R.SEARCH_ABOVE_256                 # leg B above 256: the distinct k_prep plans (see f64_ref.prep_plan)
 SHELL_K, VOXEL_K, FSC_K, MAP_K = R.SHELL_K, R.VOXEL_K, R.FSC_K, R.MAP_K
 floor_model, leg_a_rows = R.floor_model, R.leg_a_rows
+prep_plan, ragged_band = R.prep_plan, R.ragged_band
 
 
 
@@ -124,32 +125,6 @@ def test_finalize_is_reproducible(H, N):
 
 
 # ----------------------------------------------------------------------------------------------------------- leg B
-def prep_plan(N, B):
-    """The column-chunk plan launch_prep (pyp_amd/csrc/host_refine.h) derives for box N and band half-width B on its default
-    path (256 threads, 40 KB of LDS): row pairs L (divides N/2), chunk width nc, chunk count and the last chunk's width.
-    lds_fixed = 16 (B + 2) + 16 + 5 x 4 x 8 + (12 + 4) x 4 + 12 N + 16 bytes; L = min(2048 / N, N / 2), lowered until it
-    divides N/2 and L N 8 + lds_fixed + 8 (N + 1) <= 20 KB + 8 KB; nc = min(W, (40 KB - lds_fixed - L N 8) / (8 (N + 1)),
-    3072 / N); chunks = ceil(W / nc), then nc = ceil(W / chunks) (even chunks), W = B + 1."""
-    lds_fixed = (B + 2) * 16 + 16 + 5 * 4 * 8 + (12 + 4) * 4 + N * 12 + 16
-    W = B + 1
-    L = max(1, min(2048 // N, N // 2))
-    while (N // 2) % L or L * N * 8 + lds_fixed + (N + 1) * 8 > 20 * 1024 + 8192:
-        L -= 1
-    left = max(0, 40 * 1024 - lds_fixed - L * N * 8)
-    nc = max(1, min(W, left // ((N + 1) * 8), 3072 // N))
-    nch = -(-W // nc)
-    nc = -(-W // nch)
-    return L, nc, nch, W - (nch - 1) * nc
-
-
-def ragged_band(N):
-    """Band half-width whose last k_prep column chunk is narrowest (a single column wherever the plan allows one, i.e. at
-    boxes of 240 and up; below, chunks are as wide as 3072 / N and evening them leaves no one-column remainder), the widest
-    such band."""
-    best = min(range(8, N // 2), key=lambda B: (prep_plan(N, B)[3], -B))
-    return best
-
-
 def blob_volume(N, seed):
     """A few Gaussian blobs on the box grid (numpy, separable: no phantom at large boxes)."""
     rng = np.random.default_rng(seed)
