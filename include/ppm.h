@@ -230,6 +230,11 @@ int ppm_refine_last_counts(ppm_ref_t *ref, long *n_global, long *n_local, long *
 /* remarks of the last ppm_refine_batch on this reference that the caller should log (e.g. the search band was capped);
  * "" if none */
 const char *ppm_refine_note(ppm_ref_t *ref);
+/* Sections of the last ppm_refine_batch's grid search on this reference, 0 when it had none.  The search builds and searches its slice
+ * banks one section of the orientation grid at a time (contiguous ranges of grid directions) where the banks of the whole grid would
+ * pass 4 GB on the transform path or their share of the device's memory; the result does not depend on the sectioning.  With more
+ * than one section ppm_refine_note() says so. */
+int ppm_refine_last_sections(ppm_ref_t *ref);
 
 /* refine3d answers 8 / 43 "matching projections" (frealign.py:3929-3931, refine_fmatch): out[i] (box * box floats, host) = the
  * reference projected at row i's pose, times the row's CTF, moved to the row's X / Y shift and band-limited at cfg->res_high — the

@@ -32,6 +32,7 @@ struct Ctx {
     hipStream_t upload = nullptr;   // ppm_device_upload (may be called from a helper thread of the caller)
     struct PlanDev { FftPlan plan; bool ready = false; };
     PlanDev plans[513];             // FFT plans by length (tables live in device memory)
+    size_t total_mem = 0;           // of the device (hipDeviceProp_t::totalGlobalMem): what the byte budgets of the workspaces are shares of
     bool prof_on = false;
     double prof_ms[PPM_K_COUNT] = { 0 };
     long prof_n[PPM_K_COUNT] = { 0 };
@@ -190,11 +191,13 @@ struct ppm_ref {
     DevBuf<uint32_t> samples;
     DevBuf<Hit> hits, hits_t;        // hits_t: per-tile top-K lists of a shift window wider than the kernel's
     DevBuf<int> tile_c;
+    DevBuf<Hit> hits_s; DevBuf<int> sec_k;      // grid search in sections: the sections' top-K lists of a chunk and the offsets of the lists
     DevBuf<LState> states, states2;
     // full-window correlation (k_gfft): the bank in the column pass's layout, window maxima per (particle, orientation), column penalties
     DevBuf<float4> bank4; DevBuf<float> part, gtw;       // gtw: twiddle tables of the search grid (butterfly table, line table), then the window's column penalties
-    std::string bank_key, bank4_key; int gtw_ns = 0, gtw_rsx = -1;
+    std::string grid_key, bank_key, bank4_key; int gtw_ns = 0, gtw_rsx = -1;     // what mats / dir_* / twN / rowtw and the two banks hold (grid; grid + section)
     long last_counts[4] = { 0, 0, 0, 0 };
+    int last_sections = 0;           // sections of the last call's grid search (0: it had none)
     std::string note;
 };
 
@@ -289,6 +292,7 @@ int ppm_init(int device) {
     HIPCHK(hipGetDeviceProperties(&prop, device));
     if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
         return fail(-19, std::string("device is ") + prop.gcnArchName + ", libpypmatch is built for gfx950 only");
+    g.total_mem = prop.totalGlobalMem;
     if (!g.stream) HIPCHK(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
     if (!g.copy) HIPCHK(hipStreamCreateWithFlags(&g.copy, hipStreamNonBlocking));
     if (!g.upload) HIPCHK(hipStreamCreateWithFlags(&g.upload, hipStreamNonBlocking));

@@ -70,8 +70,8 @@ static int launch_global(GlobP &P, int n_img, bool half, int R) {
     size_t lds = (size_t)P.HsP * 64 * sizeof(float2) * global_particles(R);
     P.n = n_img;
     if (lds < 1024) lds = 1024;
-    // the top-K pass re-uses the block's LDS for a copy of the particle's n_orient scores when they fit (160 KB = 40 928
-    // orientations, e.g. 8 deg at C1); finer grids select on the global scratch instead
+    // the top-K pass re-uses the block's LDS for a copy of the particle's scores of this launch (one section of the grid) when they
+    // fit (160 KB = 40 928 orientations, e.g. 8 deg at C1 in one section); larger sections select on the global scratch instead
     const size_t lds_topk = (size_t)(32 + P.n_orient) * sizeof(float);
     P.topk_lds = lds_topk <= (size_t)160 * 1024 ? 1 : 0;
     if (P.topk_lds && lds_topk > lds) lds = lds_topk;
@@ -88,7 +88,7 @@ static int launch_global(GlobP &P, int n_img, bool half, int R) {
 
 // Full-window correlation (ppm_gfft.h): LDS plan and launch.  Returns -1 when the search grid is outside what the kernel is built
 // for (Ns = 16 .. 128), in which case the caller keeps the tiled k_global.
-struct GfftPlan { int LN = 0, L = 0, RC = 0, nchunk = 1; size_t t_bytes = 0, lds = 0; int topk_lds = 0; };
+struct GfftPlan { int LN = 0, L = 0, RC = 0, nchunk = 1; size_t fixed = 0, t_bytes = 0, lds = 0; int topk_lds = 0; };
 static bool gfft_plan(const Geom &gm, GfftPlan &pl) {
     int LN = 0; while ((1 << LN) < gm.Ns) LN++;
     if ((1 << LN) != gm.Ns || LN < 4 || LN > 7) return false;
@@ -103,12 +103,16 @@ static bool gfft_plan(const Geom &gm, GfftPlan &pl) {
     pl.RC = RC; pl.nchunk = (NR + RC - 1) / RC;
     pl.RC = (NR + pl.nchunk - 1) / pl.nchunk;        // even chunks
     pl.t_bytes = std::max((size_t)pl.RC * row, (size_t)G * L * L * sizeof(float4));        // T doubles as the staging area of the bank slice(s) of a pass
-    const size_t topk = (size_t)gm.n_orient * sizeof(float);
+    pl.fixed = fixed;
+    return true;
+}
+// ... and where the top-K step keeps its scores: in T when the orientations of one launch (the largest section of the grid) fit
+static void gfft_plan_topk(GfftPlan &pl, int n_orient) {
+    const size_t topk = (size_t)n_orient * sizeof(float);
     pl.topk_lds = 0;
     if (topk <= pl.t_bytes) pl.topk_lds = 1;
-    else if (fixed + topk <= (size_t)160 * 1024) { pl.topk_lds = 1; pl.t_bytes = (topk + 15) & ~(size_t)15; }
-    pl.lds = fixed + pl.t_bytes;
-    return true;
+    else if (pl.fixed + topk <= (size_t)160 * 1024) { pl.topk_lds = 1; pl.t_bytes = (topk + 15) & ~(size_t)15; }
+    pl.lds = pl.fixed + pl.t_bytes;
 }
 template <int LN, bool CHUNKED>
 static int launch_gfft_k(const GfftP &P, int n_img, size_t lds) {
@@ -179,6 +183,8 @@ struct RefineRun {
     // grid search: the window's path and, for k_global, its tiles
     GfftPlan gpl; bool use_fft = false;
     int Rtx = 0, Rty = 0, Rwin = 0, HsP = 0, nslices = 0; std::vector<int> cxs, cys;
+    // ... and the sections of the grid (ppm_sections.h) with the offsets of their hit lists: section s keeps kpre[s + 1] - kpre[s] hits
+    std::vector<GridSection> secs; std::vector<int> kpre; int sec_dirs = 0;     // sec_dirs: directions of the largest section
     // local refinement
     LocalP LP; bool local_tab = false;
     double bf = 3.0; bool any_ang = false, any_sh = false;
@@ -187,6 +193,9 @@ struct RefineRun {
     double sample_evals = 0;            // in-band samples summed over all local score evaluations of one particle
 
     int ntiles() const { return (int)(cxs.size() * cys.size()); }
+    int nsec() const { return (int)secs.size(); }
+    size_t bank_slice() const { return (size_t)HsP * 64; }                                  // float2 per stored slice of k_global's bank
+    size_t bank4_slice() const { return use_fft ? (size_t)gpl.L * gpl.L : 0; }              // float4 per stored slice of k_gfft's
     size_t HS() const { return (size_t)gm.Hs * 64; }
     int prefix_of(double rband) const { int rg = (int)std::ceil(rband); if (rg > gm.B + 1) rg = gm.B + 1; return sl.ring_off[rg]; }
 };
@@ -212,7 +221,47 @@ static void refine_notes(ppm_ref *ref, const ppm_refine_cfg *cfg, const Geom &gm
     }
 }
 
-// iteration counts, masks, the sample list (uploaded), the grid search's window path and tiles, the chunk size
+// Device memory the slice banks of one section may take, and what the per-chunk workspaces may: a quarter of the device's TOTAL memory
+// each — never of what happens to be free (a budget read from the free memory made the chunks of two processes on one device depend on
+// which of them asked first).  PPM_BANK_BYTES lowers the banks' share (tests: force several sections).
+static size_t workspace_budget() { return g.total_mem / 4; }
+static size_t bank_budget() {
+    size_t b = g.total_mem / 4;
+    if (const char *e = std::getenv("PPM_BANK_BYTES")) { const long long v = std::atoll(e); if (v > 0 && (size_t)v < b) b = (size_t)v; }
+    return b;
+}
+
+// sections of the grid (ppm_sections.h), the lengths of their hit lists, the top-K plan of k_gfft for the largest of them, the note
+static int plan_grid_sections(RefineRun &r) {
+    ppm_ref *ref = r.ref; const Geom &gm = r.gm;
+    std::string err;
+    const size_t budget = bank_budget();
+    if (!plan_sections(gm.n_dir, gm.npsi_store, r.bank_slice() * sizeof(float2), r.bank4_slice() * sizeof(float4), budget, r.secs, err)) return fail(-22, err);
+    if (r.nsec() > 1 && !r.use_fft && r.ntiles() > 1) {
+        // the tiled k_global (PPM_GLOBAL_PATH=tiles, the A/B path of wide windows) searches the whole grid from one bank
+        char b[320];
+        std::snprintf(b, sizeof(b), "PPM_GLOBAL_PATH=tiles keeps the slice bank of the whole grid (%.2f GB at an angular step of %.3g degrees), the bank may take "
+                      "%.2f GB; use a coarser angular step or the default path, which searches the grid in sections", (double)r.nslices * r.bank_slice() * sizeof(float2) / 1073741824.0,
+                      gm.dstep, budget / 1073741824.0);
+        return fail(-22, b);
+    }
+    r.kpre.assign(1, 0); r.sec_dirs = 0;
+    for (const GridSection &sc : r.secs) {
+        r.kpre.push_back(r.kpre.back() + std::min(r.K, sc.nd * gm.n_psi));
+        r.sec_dirs = std::max(r.sec_dirs, sc.nd);
+    }
+    if (r.use_fft) gfft_plan_topk(r.gpl, r.sec_dirs * gm.n_psi);
+    ref->last_sections = r.nsec();
+    if (r.nsec() > 1) {
+        char b[200];
+        std::snprintf(b, sizeof(b), "%sNOTE: grid search in %d sections of the orientation grid (%d directions, angular step %.3g degrees: the slice banks are "
+                      "built and searched one section at a time)", ref->note.empty() ? "" : "\n", r.nsec(), gm.n_dir, gm.dstep);
+        ref->note += b;
+    }
+    return 0;
+}
+
+// iteration counts, masks, the sample list (uploaded), the grid search's window path and tiles, its sections, the chunk size
 static int refine_plan(RefineRun &r, int n_img) {
     ppm_ref *ref = r.ref; const ppm_refine_cfg *cfg = r.cfg; const Geom &gm = r.gm;
     r.K = cfg->top_hits > 0 ? cfg->top_hits : 20;
@@ -258,11 +307,26 @@ static int refine_plan(RefineRun &r, int n_img) {
     // bank rows per slice in the paired order of k_global: row 0 = ky 0, row 1 = empty, rows 2t / 2t+1 = ky +t / -t
     r.HsP = ((2 * (gm.Bs + 1) + 2 * global_unroll(r.Rwin) - 1) / (2 * global_unroll(r.Rwin))) * (2 * global_unroll(r.Rwin));   // k_global walks 2 U rows per trip
     r.nslices = gm.n_dir * gm.npsi_store;
+    if (cfg->global_search) if (int rc = plan_grid_sections(r)) return rc;
     // chunk so that the scratch stays well inside HBM
     const size_t NN = (size_t)gm.N * gm.N, HW = (size_t)gm.H * gm.W;
     size_t per = NN * 4 + HW * 8 + (size_t)r.S_pad * 12 + 2 * PPM_NCOL * 8 + (gm.B + 2) * 4;
     if (cfg->global_search) per += r.HS() * 12 + (size_t)r.nslices * 4 + (size_t)gm.n_orient * 8 + (size_t)r.K * (sizeof(Hit) + sizeof(LState)) + sizeof(LState);
-    int CH = (int)std::min<size_t>((size_t)n_img, std::max<size_t>(64, ((size_t)4 << 30) / per));
+    size_t fit = ((size_t)4 << 30) / per;
+    if (fit < 64) {
+        // Fine angular steps: the per-orientation tables of a particle (norms, scores, shifts, window maxima) stay whole over the
+        // sections and outgrow 4 GB per 64 particles (about 1.4 degrees in C1).  The chunk keeps its 64 particles while they fit the
+        // workspace share of the device, shrinks below that, and a step whose tables do not fit for one particle is refused here.
+        const size_t ws = workspace_budget(), per_all = per + (r.use_fft ? (size_t)gm.n_orient * 8 : 0);
+        fit = std::min<size_t>(64, ws / per_all);
+        if (fit < 1) {
+            char b[320];
+            std::snprintf(b, sizeof(b), "angular step of %.3g degrees: the grid search keeps %.1f GB of tables per particle for its %d orientations, "
+                          "the workspace holds %.1f GB; use a coarser angular step", gm.dstep, per_all / 1073741824.0, gm.n_orient, ws / 1073741824.0);
+            return fail(-22, b);
+        }
+    }
+    int CH = (int)std::min<size_t>((size_t)n_img, fit);
     CH = std::min(CH, 8192);
     if (CH >= 2048) CH &= ~1023;        // whole rounds of blocks: 256 CUs x 1 (k_global) and x 4 (k_local, one block per particle)
     if (const char *e = std::getenv("PPM_CHUNK")) { int v = std::atoi(e); if (v > 0) CH = std::min(CH, v); }   // tests: force several chunks
@@ -285,7 +349,43 @@ static int ensure_chunk_buffers(RefineRun &r, bool images_on_device) {
     return 0;
 }
 
-// grid search: per-chunk workspaces; slice bank, twiddles and direction tables (rebuilt only when the grid / band changes)
+// k_global's bank of one section of the grid (rebuilt only when the grid, the band or the section changes: a call of one section finds
+// the bank of the call before; with several, every chunk rebuilds every section, and the key keeps the first section of a chunk from
+// taking the last section of the chunk before for its own)
+static int ensure_bank(RefineRun &r, const GridSection &sec) {
+    ppm_ref *ref = r.ref; const Geom &gm = r.gm;
+    const std::string key = ref->grid_key + "/d" + std::to_string(sec.d0) + "+" + std::to_string(sec.nd);
+    if (ref->bank_key == key) return 0;
+    const int nsl = sec.nd * gm.npsi_store;
+    BankP BP; BP.cv = r.cv; BP.mats = ref->mats.p + (size_t)sec.d0 * gm.npsi_store * 6; BP.bank = ref->bank.p; BP.nslices = nsl; BP.Bs = gm.Bs; BP.Hs = r.HsP;
+    BP.r_s2 = (float)(gm.r_s * gm.r_s);
+    {
+        ProfScope ps(PPM_K_BANK);
+        size_t tot = (size_t)nsl * r.bank_slice();
+        hipLaunchKernelGGL(k_bank, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, cur_stream(), BP);
+    }
+    HIPCHK(hipGetLastError());
+    ref->bank_key = key;
+    return 0;
+}
+
+// ... and k_gfft's, in the column pass's layout
+static int ensure_bank4(RefineRun &r, const GridSection &sec) {
+    ppm_ref *ref = r.ref; const Geom &gm = r.gm; const int L = r.gpl.L;
+    const std::string key = ref->grid_key + "/d" + std::to_string(sec.d0) + "+" + std::to_string(sec.nd) + "/L" + std::to_string(L);
+    if (ref->bank4_key == key) return 0;
+    const int nsl = sec.nd * gm.npsi_store;
+    Bank4P BP; BP.cv = r.cv; BP.mats = ref->mats.p + (size_t)sec.d0 * gm.npsi_store * 6; BP.bank4 = ref->bank4.p; BP.nslices = nsl; BP.Bs = gm.Bs; BP.L = L; BP.r_s2 = (float)(gm.r_s * gm.r_s);
+    ProfScope ps(PPM_K_BANK);
+    const size_t tot = (size_t)nsl * r.bank4_slice();
+    hipLaunchKernelGGL(k_bank4, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, cur_stream(), BP);
+    HIPCHK(hipGetLastError());
+    ref->bank4_key = key;
+    return 0;
+}
+
+// grid search: per-chunk workspaces; twiddles, direction tables and rotation matrices of the whole grid (rebuilt only when the grid /
+// band changes); the banks' storage, sized for the largest section
 static int ensure_search_tables(RefineRun &r) {
     ppm_ref *ref = r.ref; const Geom &gm = r.gm; const int CH = r.CH, K = r.K, nslices = r.nslices, HsP = r.HsP;
     const size_t HS = r.HS(), HSP = (size_t)HsP * 64;
@@ -297,9 +397,20 @@ static int ensure_search_tables(RefineRun &r) {
     if (int rc = ref->sh.ensure((size_t)CH * gm.n_orient)) return rc;
     if (int rc = ref->hits.ensure((size_t)CH * K)) return rc;
     if (int rc = ref->states.ensure((size_t)CH * K)) return rc;
+    {   // a bank that had to grow is empty again
+        const size_t cap = ref->bank.cap;
+        if (int rc = ref->bank.ensure((size_t)r.sec_dirs * gm.npsi_store * HSP)) return rc;
+        if (ref->bank.cap != cap) ref->bank_key.clear();
+    }
+    if (r.nsec() > 1) {
+        if (int rc = ref->hits_s.ensure((size_t)CH * r.kpre.back())) return rc;
+        if (int rc = ref->sec_k.ensure(r.kpre.size())) return rc;
+        HIPCHK(hipMemcpyAsync(ref->sec_k.p, r.kpre.data(), r.kpre.size() * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    }
     char key[160];
     std::snprintf(key, sizeof(key), "%d/%.6f/%.6f/%d/%d/%d/%.3f/%.3f", gm.N, gm.r_s, gm.dstep, gm.Ns, gm.npsi_store, HsP, gm.phi_max, gm.theta_max);
-    if (ref->bank_key == key) return 0;
+    if (ref->grid_key == key) return 0;
+    ref->bank_key.clear(); ref->bank4_key.clear();      // the banks were sampled with the old grid's matrices
     std::vector<float> mats((size_t)nslices * 6);
     std::vector<double> dth(gm.n_dir), dph(gm.n_dir);
     for (int d = 0; d < gm.n_dir; d++) {
@@ -316,7 +427,6 @@ static int ensure_search_tables(RefineRun &r) {
     if (int rc = ref->dir_theta.ensure(gm.n_dir)) return rc;
     if (int rc = ref->dir_phi.ensure(gm.n_dir)) return rc;
     if (int rc = ref->twN.ensure(gm.Ns)) return rc;
-    if (int rc = ref->bank.ensure((size_t)nslices * HSP)) return rc;
     HIPCHK(hipMemcpyAsync(ref->mats.p, mats.data(), mats.size() * sizeof(float), hipMemcpyHostToDevice, cur_stream()));
     HIPCHK(hipMemcpyAsync(ref->dir_theta.p, dth.data(), dth.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
     HIPCHK(hipMemcpyAsync(ref->dir_phi.p, dph.data(), dph.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
@@ -331,37 +441,22 @@ static int ensure_search_tables(RefineRun &r) {
         }
         if (int rc = ref->rowtw.ensure(rt.size())) return rc;
         HIPCHK(hipMemcpyAsync(ref->rowtw.p, rt.data(), rt.size() * sizeof(float4), hipMemcpyHostToDevice, cur_stream()));
-        HIPCHK(hipStreamSynchronize(cur_stream()));
     }
-    BankP BP; BP.cv = r.cv; BP.mats = ref->mats.p; BP.bank = ref->bank.p; BP.nslices = nslices; BP.Bs = gm.Bs; BP.Hs = HsP;
-    BP.r_s2 = (float)(gm.r_s * gm.r_s);
-    {
-        ProfScope ps(PPM_K_BANK);
-        size_t tot = (size_t)nslices * HSP;
-        hipLaunchKernelGGL(k_bank, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, cur_stream(), BP);
-    }
-    HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(cur_stream()));   // host vectors go out of scope
-    ref->bank_key = key;
+    ref->grid_key = key;
     return 0;
 }
 
-// full-window correlation (k_gfft): the bank in the column pass's layout, the twiddle tables of the search grid and the column penalties
+// full-window correlation (k_gfft): the storage of its bank (the largest section: below 4 GB, ppm_sections.h), the twiddle tables of the
+// search grid and the column penalties
 static int ensure_gfft_tables(RefineRun &r) {
-    ppm_ref *ref = r.ref; const Geom &gm = r.gm; const int nslices = r.nslices;
+    ppm_ref *ref = r.ref; const Geom &gm = r.gm;
     const int L = r.gpl.L;
     if (int rc = ref->part.ensure((size_t)r.CH * gm.n_orient * 2)) return rc;
-    char key[200];
-    std::snprintf(key, sizeof(key), "%s/L%d", ref->bank_key.c_str(), L);
-    if (ref->bank4_key != key) {
-        if ((size_t)nslices * L * L * sizeof(float4) >= ((size_t)1 << 32)) return fail(-22, "slice bank of the grid search exceeds 4 GB: use a coarser angular step or a narrower search band");
-        if (int rc = ref->bank4.ensure((size_t)nslices * L * L)) return rc;
-        Bank4P BP; BP.cv = r.cv; BP.mats = ref->mats.p; BP.bank4 = ref->bank4.p; BP.nslices = nslices; BP.Bs = gm.Bs; BP.L = L; BP.r_s2 = (float)(gm.r_s * gm.r_s);
-        ProfScope ps(PPM_K_BANK);
-        const size_t tot = (size_t)nslices * L * L;
-        hipLaunchKernelGGL(k_bank4, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, cur_stream(), BP);
-        HIPCHK(hipGetLastError());
-        ref->bank4_key = key;
+    {
+        const size_t cap = ref->bank4.cap;
+        if (int rc = ref->bank4.ensure((size_t)r.sec_dirs * gm.npsi_store * r.bank4_slice())) return rc;
+        if (ref->bank4.cap != cap) ref->bank4_key.clear();
     }
     if (ref->gtw_ns != gm.Ns || ref->gtw_rsx != gm.RSx) {
         // twiddle tables of the in-register transforms (ppm_fft_reg.h), (cos, sin) pairs: the butterfly table of the L-point transform
@@ -442,32 +537,39 @@ static void fill_schedule(RefineRun &r, double ha, double hs, int T, double rcap
     }
 }
 
-// grid search of one chunk: slice norms -> k_gfft | one k_global tile | tiles + merge -> states from the hits -> refinement of
-// every hit over the search band -> the best hit, refined at the full band into states2
-static int global_stage(RefineRun &r, int nb) {
-    ppm_ref *ref = r.ref; const ppm_refine_cfg *cfg = r.cfg; const Geom &gm = r.gm; LocalP &LP = r.LP;
-    const int K = r.K, Tb = r.Tb, Tc = r.Tc, HsP = r.HsP, nslices = r.nslices, ntiles = r.ntiles();
+// one section of the grid for one chunk: the section's banks (built unless they are the ones in place), slice norms -> k_gfft | one
+// k_global tile | tiles + merge -> the section's K best in `hits`.  The per-orientation tables (nP, cc, sh, part) are those of the
+// whole grid: the kernels get pointers to the section's first column and the tables' row lengths, and name the grid's orientations
+// in their hits.
+static int search_section(RefineRun &r, int nb, const GridSection &sec, Hit *hits, int K) {
+    ppm_ref *ref = r.ref; const Geom &gm = r.gm;
+    const int HsP = r.HsP, ntiles = r.ntiles(), nsl = sec.nd * gm.npsi_store, sl0 = sec.d0 * gm.npsi_store, o0 = sec.d0 * gm.n_psi;
+    if (int rc = ensure_bank(r, sec)) return rc;
+    if (r.use_fft) if (int rc = ensure_bank4(r, sec)) return rc;
     GlobP GP;
-    GP.bank = ref->bank.p; GP.Wp = ref->Wp.p; GP.nP = ref->nP.p; GP.nI = ref->nI.p; GP.twN = ref->twN.p; GP.rowtw = ref->rowtw.p;
-    GP.cc = ref->cc.p; GP.sh = ref->sh.p; GP.hits = ref->hits.p;
+    GP.bank = ref->bank.p; GP.Wp = ref->Wp.p; GP.nP = ref->nP.p + sl0; GP.nI = ref->nI.p; GP.twN = ref->twN.p; GP.rowtw = ref->rowtw.p;
+    GP.cc = ref->cc.p + o0; GP.sh = ref->sh.p + o0; GP.hits = hits;
     GP.Bs = gm.Bs; GP.Hs = gm.Hs; GP.HsP = HsP; GP.Ns = gm.Ns; GP.RSx = r.Rtx; GP.RSy = r.Rty;
-    GP.n_dir = gm.n_dir; GP.n_psi = gm.n_psi; GP.npsi_store = gm.npsi_store; GP.n_orient = gm.n_orient; GP.K = K;
+    GP.n_dir = sec.nd; GP.n_psi = gm.n_psi; GP.npsi_store = gm.npsi_store; GP.n_orient = sec.nd * gm.n_psi; GP.K = K;
+    GP.nP_ld = r.nslices; GP.o_ld = gm.n_orient; GP.o_base = o0;
     {
         ProfScope ps(PPM_K_NORMS);
-        NormP NP; NP.C2 = ref->C2.p; NP.bank = ref->bank.p; NP.nP = ref->nP.p; NP.n = nb; NP.nslices = nslices; NP.Bs = gm.Bs; NP.Hs = gm.Hs; NP.HsP = HsP;
-        hipLaunchKernelGGL(k_slice_norms, dim3((nb + 127) / 128, (nslices + 127) / 128), dim3(256), 0, cur_stream(), NP);
+        NormP NP; NP.C2 = ref->C2.p; NP.bank = ref->bank.p; NP.nP = ref->nP.p + sl0; NP.n = nb; NP.nslices = nsl; NP.ldn = r.nslices; NP.Bs = gm.Bs; NP.Hs = gm.Hs; NP.HsP = HsP;
+        hipLaunchKernelGGL(k_slice_norms, dim3((nb + 127) / 128, (nsl + 127) / 128), dim3(256), 0, cur_stream(), NP);
     }
     if (r.use_fft) {
         GfftP FP;
-        FP.bank4 = ref->bank4.p; FP.bank4_bytes = (unsigned)((size_t)nslices * r.gpl.L * r.gpl.L * sizeof(float4)); FP.Wp = ref->Wp.p; FP.nP = ref->nP.p; FP.nI = ref->nI.p; FP.tw = ref->gtw.p;
-        FP.part = ref->part.p; FP.cc = ref->cc.p; FP.hits = ref->hits.p;
+        FP.bank4 = ref->bank4.p; FP.bank4_bytes = (unsigned)((size_t)nsl * r.bank4_slice() * sizeof(float4)); FP.Wp = ref->Wp.p; FP.nP = ref->nP.p + sl0; FP.nI = ref->nI.p; FP.tw = ref->gtw.p;
+        FP.part = ref->part.p + (size_t)o0 * (r.gpl.L == 64 ? 2 : 1); FP.cc = ref->cc.p + o0; FP.hits = hits;
         FP.Bs = gm.Bs; FP.Hs = gm.Hs; FP.RSx = gm.RSx; FP.RSy = gm.RSy;
-        FP.n_dir = gm.n_dir; FP.n_psi = gm.n_psi; FP.npsi_store = gm.npsi_store; FP.n_orient = gm.n_orient; FP.K = K;
+        FP.n_dir = sec.nd; FP.n_psi = gm.n_psi; FP.npsi_store = gm.npsi_store; FP.n_orient = sec.nd * gm.n_psi; FP.K = K;
+        FP.nP_ld = r.nslices; FP.o_ld = gm.n_orient; FP.o_base = o0;
         if (int rc = launch_gfft(FP, nb, r.gpl)) return rc;
     } else if (ntiles == 1) {
         if (int rc = launch_global(GP, nb, gm.half != 0, r.Rwin)) return rc;
     } else {
-        // tiles of the shift window: ramp the search tables to the tile's centre, search, keep the tile's top-K; then merge
+        // tiles of the shift window (one section: plan_grid_sections): ramp the search tables to the tile's centre, search, keep the
+        // tile's top-K; then merge
         if (int rc = ref->hits_t.ensure((size_t)ntiles * nb * K)) return rc;
         if (int rc = ref->tile_c.ensure((size_t)2 * ntiles)) return rc;
         std::vector<int> tc(2 * ntiles);
@@ -482,9 +584,26 @@ static int global_stage(RefineRun &r, int nb) {
             GP.hits = ref->hits_t.p + (size_t)t * nb * K;
             if (int rc = launch_global(GP, nb, gm.half != 0, r.Rwin)) return rc;
         }
-        GP.hits = ref->hits.p;
-        hipLaunchKernelGGL(k_merge_hits, dim3((nb + 127) / 128), dim3(128), 0, cur_stream(), ref->hits_t.p, ref->hits.p, nb, K, ntiles, ref->tile_c.p, ref->tile_c.p + ntiles);
+        hipLaunchKernelGGL(k_merge_hits, dim3((nb + 127) / 128), dim3(128), 0, cur_stream(), ref->hits_t.p, hits, nb, K, ntiles, ref->tile_c.p, ref->tile_c.p + ntiles);
         HIPCHK(hipStreamSynchronize(cur_stream()));      // the host vector of the centres goes out of scope
+    }
+    return 0;
+}
+
+// grid search of one chunk: the sections of the grid one after another (one section: straight into the chunk's hits; several: every
+// section's K best into its list, then the K best of the lists) -> states from the hits -> refinement of every hit over the search
+// band -> the best hit, refined at the full band into states2
+static int global_stage(RefineRun &r, int nb) {
+    ppm_ref *ref = r.ref; const ppm_refine_cfg *cfg = r.cfg; const Geom &gm = r.gm; LocalP &LP = r.LP;
+    const int K = r.K, Tb = r.Tb, Tc = r.Tc;
+    if (r.nsec() == 1) {
+        if (int rc = search_section(r, nb, r.secs[0], ref->hits.p, K)) return rc;
+    } else {
+        for (int s = 0; s < r.nsec(); s++)
+            if (int rc = search_section(r, nb, r.secs[s], ref->hits_s.p + (size_t)r.kpre[s] * nb, r.kpre[s + 1] - r.kpre[s])) return rc;
+        ProfScope ps(PPM_K_TOPK);
+        hipLaunchKernelGGL(k_merge_sections, dim3(nb), dim3(64), 0, cur_stream(), ref->hits_s.p, ref->hits.p, nb, K, r.nsec(), ref->sec_k.p);
+        HIPCHK(hipGetLastError());
     }
     {
         ProfScope ps(PPM_K_TOPK);
@@ -618,7 +737,7 @@ void ppm_reference_destroy(ppm_ref_t *r) {
     r->c_delta.release(); r->c_s0.release(); r->c_g0.release(); r->c_out.release(); r->c_eval.release(); r->c_rp.release(); r->c_rt.release(); r->c_slot.release(); r->c_states.release(); r->c_uoff.release(); r->c_mean.release(); r->c_active.release(); r->c_tmean.release(); r->c_acc.release(); r->c_dtrial.release(); r->c_fpm.release(); r->c_delta_t.release(); r->cc.release(); r->mats.release(); r->ddef.release();
     r->band.release(); r->spill.release(); r->Il.release(); r->Wp.release(); r->bank.release(); r->twN.release(); r->rowtw.release(); r->sh.release(); r->samples.release();
     r->hits.release(); r->states.release(); r->states2.release();
-    r->hits_t.release(); r->tile_c.release(); r->bank4.release(); r->part.release(); r->gtw.release();
+    r->hits_t.release(); r->tile_c.release(); r->hits_s.release(); r->sec_k.release(); r->bank4.release(); r->part.release(); r->gtw.release();
     if (r->stream) (void)hipStreamDestroy(r->stream);
     if (r->copy) (void)hipStreamDestroy(r->copy);
     delete r;
@@ -673,6 +792,7 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
     if (!ref || !cfg || !images || !rows_in || !rows_out) return fail(-22, "null argument");
     StreamScope ss_(ref->stream, ref->copy);
     if (n_img <= 0) return 0;
+    ref->last_sections = 0;
     RefineRun r; r.ref = ref; r.cfg = cfg;
     const Geom &gm = r.gm; std::string err;
     if (!geom_init(r.gm, *cfg, err)) return fail(-22, err);
@@ -684,8 +804,11 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
     if (int rc = refine_plan(r, n_img)) return rc;
     if (int rc = ensure_chunk_buffers(r, images_on_device != 0)) return rc;
     r.cv = cube_view(ref);
-    if (cfg->global_search) if (int rc = ensure_search_tables(r)) return rc;
-    if (r.use_fft) if (int rc = ensure_gfft_tables(r)) return rc;
+    if (cfg->global_search) {       // the tables of the grid and the banks of its first section (the only one of most calls: kept across calls)
+        if (int rc = ensure_search_tables(r)) return rc;
+        if (int rc = ensure_bank(r, r.secs[0])) return rc;
+        if (r.use_fft) { if (int rc = ensure_gfft_tables(r)) return rc; if (int rc = ensure_bank4(r, r.secs[0])) return rc; }
+    }
     HIPCHK(hipStreamSynchronize(cur_stream()));
     if (int rc = local_setup(r)) return rc;
 
@@ -717,6 +840,8 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
 
 
 const char *ppm_refine_note(ppm_ref_t *ref) { return ref ? ref->note.c_str() : ""; }
+
+int ppm_refine_last_sections(ppm_ref_t *ref) { return ref ? ref->last_sections : 0; }
 
 int ppm_refine_last_counts(ppm_ref_t *ref, long *n_global, long *n_local, long *samples_global, long *samples_local) {
     if (!ref) return fail(-22, "null reference");

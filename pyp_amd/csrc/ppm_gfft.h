@@ -45,6 +45,11 @@ struct GfftP {
     int n, Bs, Hs, RSx, RSy, n_dir, n_psi, npsi_store, n_orient, K, topk_lds;
     int RC, nchunk;          // rows of T held at a time, and how many such chunks cover the 2 RSy + 1 rows (1 unless LDS is short)
     int t_bytes;             // bytes of the T image (the small arrays follow it)
+    // One launch searches one SECTION of the grid (ppm_sections.h): n_dir directions, n_orient = n_dir * n_psi, K the hits of the
+    // section, bank4 the section's bank.  nP, part and cc point at the section's first column of the tables of the whole grid, whose
+    // rows are nP_ld / o_ld apart; o_base turns the section's orientation index into the grid's in the hits.  The arg-max passes over
+    // the section's winners follow its own top-K step, while their slices are still in the bank.
+    int nP_ld, o_ld, o_base;
 };
 
 constexpr int gfft_row_stride(int L) { return L + 2; }       // float2 per T row: 16-byte row reads of 64 lanes hit distinct banks
@@ -206,9 +211,9 @@ __global__ void __launch_bounds__(256) k_gfft(GfftP P) {
 
     const int npass0 = (nslices + G - 1) / G;
     int npass1 = 0;                                                  // arg-max passes over the winners, known after the top-K step
-    float *partp = P.part + (size_t)p * P.n_orient * NPART;
+    float *partp = P.part + (size_t)p * P.o_ld * NPART;
     const float nIp = P.nI[p];
-    const float *nPp = P.nP + (size_t)p * nslices;
+    const float *nPp = P.nP + (size_t)p * P.nP_ld;
     Hit *hitp = P.hits + (size_t)p * P.K;
 
     // window rows of this wave's outputs (column pass, not CHUNKED): bit f of mask_pos for f = 0 .. fmax, bit j - 1 of mask_neg for j = 1 .. jmax
@@ -235,7 +240,7 @@ __global__ void __launch_bounds__(256) k_gfft(GfftP P) {
             // ---- scores of all orientations, top-K (ties -> lower orientation index, like the oracle)
             __threadfence_block();
             __syncthreads();
-            float *sc = P.topk_lds ? (float *)T : P.cc + (size_t)p * P.n_orient;
+            float *sc = P.topk_lds ? (float *)T : P.cc + (size_t)p * P.o_ld;
             for (int o = tid; o < P.n_orient; o += 256) {
                 const int dir = o / P.n_psi, k = o - dir * P.n_psi;
                 const int e = (half && k >= P.npsi_store) ? 1 : 0, sl = dir * P.npsi_store + k - e * P.npsi_store;
@@ -458,7 +463,7 @@ __global__ void __launch_bounds__(256) k_gfft(GfftP P) {
                 const float v = red_v[tid + j]; const int k = red_k[tid + j];
                 if (v > bv || (v == bv && k < bk)) { bv = v; bk = k; }
             }
-            Hit h; h.cc = win_c[r_hit]; h.orient = win_o[r_hit]; h.sx = 0; h.sy = 0;
+            Hit h; h.cc = win_c[r_hit]; h.orient = win_o[r_hit] + P.o_base; h.sx = 0; h.sy = 0;
             if (bk != 0x7fffffff) { h.sy = bk / Ns - RSy; h.sx = bk % Ns - L; }
             hitp[r_hit] = h;
         }

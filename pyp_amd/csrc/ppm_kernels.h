@@ -578,7 +578,9 @@ __global__ void __launch_bounds__(256) k_bank(BankP P) {
 // instructions per row pair and lane.  Block = 4 waves, tile 128 particles x 128 slices, K tile = half a paired bank row
 // (32 kx); each wave owns 64 x 64 = 2 x 2 MFMA tiles (64 accumulator registers).  LDS rows are padded to 33 floats: the
 // operand reads (lane = row, two k per instruction) then touch 32 distinct banks.
-struct NormP { const float *C2; const float2 *bank; float *nP; int n, nslices, Bs, Hs, HsP; };
+// bank, nslices: the slices of one section of the grid (host_refine.h); nP points at the section's first column of the whole
+// [n][ldn] table (ldn = slices of the whole grid)
+struct NormP { const float *C2; const float2 *bank; float *nP; int n, nslices, ldn, Bs, Hs, HsP; };
 typedef float v16f __attribute__((ext_vector_type(16)));
 
 __global__ void __launch_bounds__(256, 2) k_slice_norms(NormP P) {
@@ -650,7 +652,7 @@ __global__ void __launch_bounds__(256, 2) k_slice_norms(NormP P) {
 #pragma unroll
             for (int v = 0; v < 16; v++) {
                 const int pr = p0 + 64 * wm + 32 * a + 8 * (v >> 2) + 4 * (lane >> 5) + (v & 3);
-                if (pr < P.n && sc < P.nslices) P.nP[(size_t)pr * P.nslices + sc] = acc[a][b][v];
+                if (pr < P.n && sc < P.nslices) P.nP[(size_t)pr * P.ldn + sc] = acc[a][b][v];
             }
         }
 }
@@ -698,6 +700,33 @@ __global__ void k_merge_hits(Hit *tiles, Hit *out, int n, int K, int ntiles, con
     }
 }
 
+// Top-K of the top-K lists of the grid's SECTIONS (ppm_sections.h).  Unlike the tiles above, which cover the same orientations over
+// different shifts, the sections cover disjoint orientations: nothing is struck out, an entry's place in the result is the number of
+// entries that come before it — higher correlation first, ties -> lower orientation index, the rule of the single-section selection.
+// lists: section s holds [n][ks] hits from entry kpre[s] * n on, ks = kpre[s + 1] - kpre[s] = min(K, orientations of the section): a
+// section of fewer than K orientations has a short list.  The lists hold at least K entries together (K <= n_orient).  Two entries can
+// only tie in both keys as the placeholders of a particle without comparable scores (NaN images): the entry index then decides, so
+// that every place is written once.  Block = one particle, one wave; lane = entry of a section's list.
+__global__ void __launch_bounds__(64) k_merge_sections(const Hit *lists, Hit *out, int n, int K, int nsec, const int *kpre) {
+    const int p = blockIdx.x, lane = threadIdx.x;
+    for (int s = 0; s < nsec; s++) {
+        const int k0 = kpre[s], ks = kpre[s + 1] - k0;
+        if (lane >= ks) continue;
+        const Hit me = lists[(size_t)k0 * n + (size_t)p * ks + lane];
+        const int mi = k0 + lane;
+        int rank = 0;
+        for (int t = 0; t < nsec && rank < K; t++) {
+            const int t0 = kpre[t], kt = kpre[t + 1] - t0;
+            const Hit *h = lists + (size_t)t0 * n + (size_t)p * kt;
+            for (int j = 0; j < kt; j++) {
+                const float c = h[j].cc; const int o = h[j].orient;
+                rank += (c > me.cc || (c == me.cc && (o < me.orient || (o == me.orient && t0 + j < mi)))) ? 1 : 0;
+            }
+        }
+        if (rank < K) out[(size_t)p * K + rank] = me;
+    }
+}
+
 // Pair twiddles e^{+2 pi i t j / Ns}, [t][j-1] for the row pair ky = +-t: wave-uniform, fetched with scalar loads.
 // Stored as {cos, cos, sin, sin} so that a scalar load delivers the two operand pairs of the packed FMAs as they are.
 // The table belongs to the reference handle (two references with different search grids may be live at once); it is read
@@ -728,6 +757,11 @@ struct GlobP {
     Hit *hits;            // [n][K]
     int n, Bs, Hs, HsP, Ns, RSx, RSy, n_dir, n_psi, npsi_store, n_orient, K;   // n: particles of this launch
     int topk_lds;         // 1: the top-K pass works on an LDS copy of the particle's scores (they fit), 0: on the global scratch
+    // One launch searches one SECTION of the grid (ppm_sections.h): n_dir directions from direction d0 on, n_orient = n_dir * n_psi, K
+    // the hits of the section.  bank is the section's; nP, cc and sh point at the section's first column of the tables of the whole
+    // grid, whose rows are nP_ld / o_ld apart; o_base = d0 * n_psi turns the section's orientation index into the grid's in the hits.
+    // The whole grid in one section: nP_ld = n_dir * npsi_store, o_ld = n_orient, o_base = 0.
+    int nP_ld, o_ld, o_base;
 };
 
 // The same for pairs of values held in packed registers (both orientations of a stored slice): the swaps and DPP steps work
@@ -860,7 +894,7 @@ __global__ void __launch_bounds__(global_threads(R)) k_global(GlobP P) {
 #pragma unroll
     for (int q = 0; q < NQ; q++) {
         nI[q] = P.nI[pq[q]];
-        c_nP[q] = (const __attribute__((address_space(4))) float *)P.nP + (size_t)pq[q] * nslices;
+        c_nP[q] = (const __attribute__((address_space(4))) float *)P.nP + (size_t)pq[q] * P.nP_ld;
     }
     float txc[R + 1], txs[R + 1];      // per-lane x twiddles e^{+2 pi i kx j / Ns}
 #pragma unroll
@@ -960,7 +994,7 @@ __global__ void __launch_bounds__(global_threads(R)) k_global(GlobP P) {
                 vax[j] = va[q][j].x; vay[j] = va[q][j].y; vbx[j] = vb[q][j].y; vby[j] = -vb[q][j].x;
             }
             const float inv = (nP > 0.f && nI[q] > 0.f) ? rsqrtf(nP * nI[q]) : 0.f;
-            float *ccp = P.cc + (size_t)pq[q] * P.n_orient; int *shp = P.sh + (size_t)pq[q] * P.n_orient;
+            float *ccp = P.cc + (size_t)pq[q] * P.o_ld; int *shp = P.sh + (size_t)pq[q] * P.o_ld;
             if constexpr (!TWO && HALF && NS * NS <= 64) {
                 // both orientations of the stored slice at once, in the halves of packed registers (.x: psi, sg = +1; .y: psi + 180 deg,
                 // sg = -1): Q = A + sg Bq, U = ua + sg ub, V = va + sg vb; G(+j) = U + iV, G(-j) = U - iV;
@@ -1127,7 +1161,7 @@ __global__ void __launch_bounds__(global_threads(R)) k_global(GlobP P) {
     float *rv = (float *)smem; int *ri = (int *)(rv + 16);
     for (int q = 0; q < NQ && p0 + q < P.n; q++) {
         const int p = p0 + q;
-        float *ccp = P.cc + (size_t)p * P.n_orient; int *shp = P.sh + (size_t)p * P.n_orient;
+        float *ccp = P.cc + (size_t)p * P.o_ld; int *shp = P.sh + (size_t)p * P.o_ld;
         float *sc = P.topk_lds ? rv + 32 : ccp;           // host: the LDS allocation covers 32 + n_orient floats when topk_lds is set
         if (P.topk_lds) for (int o = tid; o < P.n_orient; o += NT) sc[o] = ccp[o];
         __syncthreads();
@@ -1147,7 +1181,7 @@ __global__ void __launch_bounds__(global_threads(R)) k_global(GlobP P) {
             if (tid == 0) {
                 for (int w = 1; w < NW; w++) if (rv[w] > bv || (rv[w] == bv && ri[w] < bi)) { bv = rv[w]; bi = ri[w]; }
                 if (bi >= P.n_orient) { bi = 0; bv = 0.f; }     // nothing comparable left (NaN scores): stay inside the tables
-                Hit h; h.cc = bv; h.orient = bi;
+                Hit h; h.cc = bv; h.orient = bi + P.o_base;
                 int sv = shp[bi];
                 h.sx = (int)(short)(sv & 0xffff); h.sy = sv >> 16;
                 P.hits[(size_t)p * P.K + k] = h;

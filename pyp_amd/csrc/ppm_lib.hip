@@ -23,6 +23,7 @@
 
 #include "../../include/ppm.h"
 #include "ppm_geom.h"
+#include "ppm_sections.h"
 #include "ppm_kernels2.h"
 #include "ppm_csp_kernels.h"
 #include "ppm_sva_kernels.h"

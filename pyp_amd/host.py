@@ -130,6 +130,10 @@ class Reference:
         lib.check(lib.load().ppm_refine_last_counts(self.h, *[C.byref(x) for x in v]))
         return dict(zip(("n_global", "n_local", "samples_global", "samples_local"), [x.value for x in v]))
 
+    def last_sections(self):
+        """Sections of the orientation grid the last refine()'s grid search ran in (ppm_refine_last_sections); 0: it had none."""
+        return int(lib.load().ppm_refine_last_sections(self.h))
+
     def close(self):
         if getattr(self, "h", None):
             lib.load().ppm_reference_destroy(self.h)
