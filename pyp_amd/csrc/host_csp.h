@@ -25,6 +25,28 @@ struct CspUnits {
 };
 // free parameters and step schedule of the compass search
 struct CspSearch { int en[6] = { 0, 0, 0, 0, 0, 0 }; double tol[6] = { 0, 0, 0, 0, 0, 0 }; int nfree = 0, T = 0; double ha0 = 0, hs0 = 0; };
+// One compass search on the stream, for every search whose state and decisions live on the device (k_csp_step_*): the first candidates,
+// then per iteration band -> candidates' scores -> trial step -> its score -> accept, steps halved after each; nothing waits on the host.
+// The caller fills SP but for the steps and the two score buffers (mean: [unit][ncand] of the compass sweep, tmean: [unit] of the trial); band_of(ha, hs) gives an iteration's band, eval(delta, ncand, band, means_out) enqueues the
+// caller's evaluation of `ncand` candidates per unit (non-zero: give up with that code).
+template <class BandOf, class Eval>
+static int compass_enqueue(CspStepP &SP, double *mean, double *tmean, int T, double ha, double hs, BandOf band_of, Eval eval) {
+    SP.mean = mean; SP.tmean = tmean;
+    const unsigned gstep = (unsigned)((SP.n_active + 127) / 128);
+    SP.ha = ha; SP.hs = hs; SP.ha_next = ha; SP.hs_next = hs;
+    hipLaunchKernelGGL(k_csp_step_init, dim3(gstep), dim3(128), 0, cur_stream(), SP);
+    for (int it = 0; it < T; it++) {
+        const double band = band_of(ha, hs);
+        SP.ha = ha; SP.hs = hs; SP.ha_next = 0.5 * ha; SP.hs_next = 0.5 * hs;
+        if (int rc = eval(SP.delta_c, SP.ncand, band, mean)) return rc;
+        hipLaunchKernelGGL(k_csp_step_trial, dim3(gstep), dim3(128), 0, cur_stream(), SP);
+        if (int rc = eval(SP.delta_t, 1, band, tmean)) return rc;
+        hipLaunchKernelGGL(k_csp_step_accept, dim3(gstep), dim3(128), 0, cur_stream(), SP);
+        ha *= 0.5; hs *= 0.5;
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 // what the stages of a call share
 struct CspRun {
     ppm_ref *ref = nullptr; const ppm_refine_cfg *cfg = nullptr; const ppm_csp_cfg *cc = nullptr;
@@ -261,33 +283,22 @@ static int csp_compass(CspRun &c, CspUnits &U, const CspSearch &P, int ncand_max
     CspStepP SP;
     SP.kind = c.kind; SP.n_active = na; SP.ncand = ncand; SP.active = d_active.p; SP.unit_slot = ref->c_slot.p;
     for (int i = 0; i < 6; i++) { SP.en[i] = P.en[i]; SP.tol[i] = P.tol[i]; }
-    SP.mean = ref->c_mean.p; SP.tmean = d_tmean.p; SP.acc = d_acc.p; SP.dtrial = d_dtrial.p; SP.fpm = d_fpm.p;
+    SP.acc = d_acc.p; SP.dtrial = d_dtrial.p; SP.fpm = d_fpm.p;
     SP.delta_c = d_delta.p; SP.delta_t = d_delta_t.p; SP.Nmat = ref->c_N.p; SP.pshift = ref->c_p.p; SP.tl = ref->c_tl.p; SP.nstride = 9; SP.pstride = 3;
     HIPCHK(hipMemsetAsync(d_acc.p, 0, (size_t)na * 6 * sizeof(double), cur_stream()));
-    const unsigned gstep = (unsigned)((na + 127) / 128);
     int nrot_c = 0;         // accounting: gathers = samples x rotations that differ (shift candidates share the centre's)
     for (int i = 0; i < 3; i++) nrot_c += P.en[i] ? 2 : 0;
-    auto eval_async = [&](const double *delta, int nc, double rband, double *means) {
-        EP.delta = delta; EP.ncand = nc; EP.S_used = c.prefix_of(rband); EP.rmax2 = (float)(rband * rband);
-        c.acct_gathers += (double)U.eval_rows.size() * EP.S_used * (nc > 1 ? 1 + nrot_c : 1); c.acct_sweeps++;
-        launch_csp_eval(c, U.eval_rows.size());
-        const int nm = na * nc;
-        hipLaunchKernelGGL(k_csp_unit_means, dim3((nm + 255) / 256), dim3(256), 0, cur_stream(), ref->c_out.p, ref->c_uoff.p, na, nc, means);
-    };
     const bool any_ang = P.en[0] || P.en[1] || P.en[2], any_sh = P.en[3] || P.en[4] || P.en[5];
-    double ha = P.ha0, hs = P.hs0;
-    SP.ha = ha; SP.hs = hs; SP.ha_next = ha; SP.hs_next = hs;
-    hipLaunchKernelGGL(k_csp_step_init, dim3(gstep), dim3(128), 0, cur_stream(), SP);
-    for (int it = 0; it < P.T; it++) {
-        const double rband = march_band(c.bf(), gm.N, c.rm_px, ha, hs, any_ang, any_sh, gm.r_hi);
-        SP.ha = ha; SP.hs = hs; SP.ha_next = 0.5 * ha; SP.hs_next = 0.5 * hs;
-        eval_async(d_delta.p, ncand, rband, ref->c_mean.p);
-        hipLaunchKernelGGL(k_csp_step_trial, dim3(gstep), dim3(128), 0, cur_stream(), SP);
-        eval_async(d_delta_t.p, 1, rband, d_tmean.p);
-        hipLaunchKernelGGL(k_csp_step_accept, dim3(gstep), dim3(128), 0, cur_stream(), SP);
-        ha *= 0.5; hs *= 0.5;
-    }
-    HIPCHK(hipGetLastError());
+    if (int rc = compass_enqueue(SP, ref->c_mean.p, d_tmean.p, P.T, P.ha0, P.hs0,
+            [&](double ha, double hs) { return march_band(c.bf(), gm.N, c.rm_px, ha, hs, any_ang, any_sh, gm.r_hi); },
+            [&](const double *delta, int nc, double rband, double *means) {
+                EP.delta = delta; EP.ncand = nc; EP.S_used = c.prefix_of(rband); EP.rmax2 = (float)(rband * rband);
+                c.acct_gathers += (double)U.eval_rows.size() * EP.S_used * (nc > 1 ? 1 + nrot_c : 1); c.acct_sweeps++;
+                launch_csp_eval(c, U.eval_rows.size());
+                const int nm = na * nc;
+                hipLaunchKernelGGL(k_csp_unit_means, dim3((nm + 255) / 256), dim3(256), 0, cur_stream(), ref->c_out.p, ref->c_uoff.p, na, nc, means);
+                return 0;
+            })) return rc;
     // the units as the search left them
     HIPCHK(hipMemcpyAsync(c.hN.data(), ref->c_N.p, c.hN.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
     HIPCHK(hipMemcpyAsync(c.hp.data(), ref->c_p.p, c.hp.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));

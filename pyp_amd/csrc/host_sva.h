@@ -288,21 +288,11 @@ static int sva_compass(SvaSearch &Q, std::vector<CUnit> &st, const std::vector<i
     CspStepP SP;
     SP.kind = PPM_CSP_PARTICLES; SP.n_active = ns; SP.ncand = nc; SP.active = nullptr; SP.unit_slot = nullptr;
     for (int i = 0; i < 6; i++) { SP.en[i] = en[i]; SP.tol[i] = tol[i]; }
-    SP.mean = Q.d_out; SP.tmean = Q.d_tout; SP.acc = Q.d_acc; SP.dtrial = Q.d_dtrial; SP.fpm = Q.d_fpm;
+    SP.acc = Q.d_acc; SP.dtrial = Q.d_dtrial; SP.fpm = Q.d_fpm;
     SP.delta_c = Q.d_delta; SP.delta_t = Q.d_delta_t; SP.Nmat = Q.d_poses; SP.pshift = Q.d_poses + 9; SP.tl = nullptr; SP.nstride = 12; SP.pstride = 12;
-    const unsigned gstep = (unsigned)((ns + 127) / 128);
-    SP.ha = ha; SP.hs = hs; SP.ha_next = ha; SP.hs_next = hs;
-    hipLaunchKernelGGL(k_csp_step_init, dim3(gstep), dim3(128), 0, cur_stream(), SP);
-    for (int it = 0; it < Tn; it++) {
-        const double rb = march_band(Q.bf, Q.N, Q.rm_px, ha, hs, en[0] != 0, en[3] != 0, Q.rband);
-        SP.ha = ha; SP.hs = hs; SP.ha_next = 0.5 * ha; SP.hs_next = 0.5 * hs;
-        if (int rc = sva_launch_eval(Q, ns, nc, nrot, rb, Q.d_delta, Q.d_out)) return rc;
-        hipLaunchKernelGGL(k_csp_step_trial, dim3(gstep), dim3(128), 0, cur_stream(), SP);
-        if (int rc = sva_launch_eval(Q, ns, 1, 0, rb, Q.d_delta_t, Q.d_tout)) return rc;
-        hipLaunchKernelGGL(k_csp_step_accept, dim3(gstep), dim3(128), 0, cur_stream(), SP);
-        ha *= 0.5; hs *= 0.5;
-    }
-    HIPCHK(hipGetLastError());
+    if (int rc = compass_enqueue(SP, Q.d_out, Q.d_tout, Tn, ha, hs,
+            [&](double ha_, double hs_) { return march_band(Q.bf, Q.N, Q.rm_px, ha_, hs_, en[0] != 0, en[3] != 0, Q.rband); },
+            [&](const double *delta, int ncand, double rb, double *out) { return sva_launch_eval(Q, ns, ncand, delta == Q.d_delta ? nrot : 0, rb, delta, out); })) return rc;      // the compass sweep has the rotated candidates, the trial none
     Q.EP.delta = Q.d_delta;
     Q.hp.resize((size_t)12 * ns);
     HIPCHK(hipMemcpyAsync(Q.hp.data(), Q.d_poses, Q.hp.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
@@ -353,7 +343,7 @@ static int sva_global_candidates(SvaSearch &Q, const SvaPlan &P, const std::vect
         std::partial_sort(order.begin(), order.begin() + Kc, order.end(), [&](int x, int y) { return sc_[x] > sc_[y] || (sc_[x] == sc_[y] && x < y); });
         for (int k = 0; k < Kc; k++) {
             CUnit c = st[v];
-            double Nq[9]; mat_mul3h(st[v].N, &P.grid_d[(size_t)order[k] * 9], Nq); std::memcpy(c.N, Nq, sizeof(Nq));
+            double Nq[9]; mat_mul3(st[v].N, &P.grid_d[(size_t)order[k] * 9], Nq); std::memcpy(c.N, Nq, sizeof(Nq));
             cand.push_back(c); vm.push_back(v);
         }
     }

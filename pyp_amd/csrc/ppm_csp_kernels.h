@@ -28,29 +28,6 @@ struct CspEvalP {
     double *out;                          // [grid][ncand] scores
 };
 
-__device__ __forceinline__ void d_rot_xyz(int k, double deg, double *R) {      // right-handed rotation about x, y, z
-    double s, c;
-    sincos(deg * 3.14159265358979323846 / 180.0, &s, &c);
-    if (k == 0) { R[0] = 1; R[1] = 0; R[2] = 0; R[3] = 0; R[4] = c; R[5] = -s; R[6] = 0; R[7] = s; R[8] = c; }
-    else if (k == 1) { R[0] = c; R[1] = 0; R[2] = s; R[3] = 0; R[4] = 1; R[5] = 0; R[6] = -s; R[7] = 0; R[8] = c; }
-    else { R[0] = c; R[1] = -s; R[2] = 0; R[3] = s; R[4] = c; R[5] = 0; R[6] = 0; R[7] = 0; R[8] = 1; }
-}
-
-// M_row = N Ry(-tilt) Rz(axis); g = [Rz(-axis) Ry(tilt) (-p)]_xy + tilt shift
-__device__ inline void d_csp_row_pose(const double *N, const double *p, double tilt, double axis, double tsx, double tsy, double *M, double *g) {
-    double a[9], b[9], t[9];
-    d_rot_xyz(1, -tilt, a); d_rot_xyz(2, axis, b);
-    d_mat_mul3(N, a, t); d_mat_mul3(t, b, M);
-    d_rot_xyz(2, -axis, a); d_rot_xyz(1, tilt, b);
-    const double q0 = -p[0], q1 = -p[1], q2 = -p[2];
-    double u[3], v[2];
-#pragma unroll
-    for (int i = 0; i < 3; i++) u[i] = b[i * 3] * q0 + b[i * 3 + 1] * q1 + b[i * 3 + 2] * q2;
-#pragma unroll
-    for (int i = 0; i < 2; i++) v[i] = a[i * 3] * u[0] + a[i * 3 + 1] * u[1] + a[i * 3 + 2] * u[2];
-    g[0] = v[0] + tsx; g[1] = v[1] + tsy;
-}
-
 // Block = one projection row, 256 threads: thread q < ncand derives candidate q's row pose in double precision; the
 // candidates that keep the unit's rotation share one gather group (shift variants), every rotated candidate is a group
 // of its own; one sweep (sweep_plan) scores them all.
@@ -77,14 +54,12 @@ __global__ void __launch_bounds__(256, 4) k_csp_eval(CspEvalP P) {
         int same;
         if (P.kind == PPM_CSP_PARTICLES) {
             same = d[0] == 0.0 && d[1] == 0.0 && d[2] == 0.0;
-            for (int k = 0; k < 3; k++)
-                if (d[k] != 0.0) { double R[9], T[9]; d_rot_xyz(k, d[k], R); d_mat_mul3(N, R, T); for (int q = 0; q < 9; q++) N[q] = T[q]; }
-            p[0] += d[3]; p[1] += d[4]; p[2] += d[5];
+            unit_apply_delta(N, p, d);
         } else {
             same = d[0] == 0.0 && d[1] == 0.0;
             tl[0] += d[0]; tl[1] += d[1]; tl[2] += d[3]; tl[3] += d[4];
         }
-        d_csp_row_pose(N, p, tl[0], tl[1], tl[2], tl[3], M, g);
+        csp_row_pose(N, p, tl[0], tl[1], tl[2], tl[3], M, g);
         cm[tid][0] = (float)M[0]; cm[tid][1] = (float)M[1]; cm[tid][2] = (float)M[3]; cm[tid][3] = (float)M[4]; cm[tid][4] = (float)M[6]; cm[tid][5] = (float)M[7];
         csh[tid][0] = (float)(P.s0[2 * j] + g[0] - P.g0[2 * j]); csh[tid][1] = (float)(P.s0[2 * j + 1] + g[1] - P.g0[2 * j + 1]);
         csame[tid] = same;
@@ -128,8 +103,8 @@ __global__ void k_csp_unit_means(const double *__restrict__ out, const int *__re
     mean[i] = s / (double)(hi - lo);
 }
 
-// ---- the compass search's decisions, one thread per active unit (double precision, the same rule as the CPU checker's loop and k_local's
-// compass iteration).  Candidate 0 is the unit as it stands; then +h and -h for every enabled parameter in order.
+// ---- the compass search's decisions, one thread per active unit (double precision): compass_trial / compass_accept of
+// ppm_geom.h, the rule k_local applies as well.  Candidate 0 is the unit as it stands; then +h and -h for every enabled parameter in order.
 struct CspStepP {
     int kind, n_active, ncand;
     const int *active;        // [n_active] index of the unit in the particle / tilt tables (null: the identity)
@@ -141,7 +116,7 @@ struct CspStepP {
     const double *tmean;      // [n_active] unit means of the trial sweep
     double *acc;              // [n_active][6] displacement accumulated so far (bounded by +-tol)
     double *dtrial;           // [n_active][6] trial step
-    double *fpm;              // [n_active][12] f(+h), f(-h) per parameter (-1e300: outside the bounds)
+    double *fpm;              // [n_active][2][6] f(+h) of every parameter, then f(-h) (kNoProbe: outside the bounds)
     double *delta_c;          // [n_slots][ncand][6] candidates of the compass sweep
     double *delta_t;          // [n_slots][6] the trial step as k_csp_eval reads it
     double *Nmat, *pshift, *tl;   // unit state (k_csp_eval's tables; the sub-volume search keeps N and p in one row of 12)
@@ -173,26 +148,9 @@ __global__ void k_csp_step_init(CspStepP P) {
 __global__ void k_csp_step_trial(CspStepP P) {
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= P.n_active) return;
-    const double *mean = P.mean + (size_t)a * P.ncand, *acc = P.acc + (size_t)a * 6;
+    const double *mean = P.mean + (size_t)a * P.ncand;
     double *d = P.dtrial + (size_t)a * 6, *fpm = P.fpm + (size_t)a * 12;
-    const double f0 = mean[0];
-    for (int i = 0, c = 1; i < 6; i++) {
-        d[i] = 0; fpm[2 * i] = fpm[2 * i + 1] = -1e300;
-        if (!P.en[i]) continue;
-        const double h = i < 3 ? P.ha : P.hs, tol = P.tol[i];
-        const bool okp = fabs(acc[i] + h) <= tol + 1e-9, okm = fabs(acc[i] - h) <= tol + 1e-9;
-        const double fp = okp ? mean[c] : -1e300, fm = okm ? mean[c + 1] : -1e300;
-        c += 2;
-        fpm[2 * i] = fp; fpm[2 * i + 1] = fm;
-        if (okp && okm) {
-            const double den = 2.0 * f0 - fp - fm;
-            if (den > 1e-12) { const double t = 0.5 * h * (fp - fm) / den; d[i] = t > h ? h : (t < -h ? -h : t); }
-            else { const double best = fp > fm ? fp : fm; d[i] = best > f0 ? (fp > fm ? h : -h) : 0.0; }
-        } else if (okp) d[i] = fp > f0 ? h : 0.0;
-        else if (okm) d[i] = fm > f0 ? -h : 0.0;
-        if (acc[i] + d[i] > tol) d[i] = tol - acc[i];
-        if (acc[i] + d[i] < -tol) d[i] = -tol - acc[i];
-    }
+    compass_trial<6>(mean[0], mean + 1, nullptr, P.en, P.ha, P.hs, P.acc + (size_t)a * 6, P.tol, d, fpm, fpm + 6);
     double *dt = P.delta_t + (size_t)d_csp_slot(P, d_csp_unit(P, a)) * 6;
     for (int i = 0; i < 6; i++) dt[i] = d[i];
 }
@@ -204,22 +162,14 @@ __global__ void k_csp_step_accept(CspStepP P) {
     const int u = d_csp_unit(P, a);
     const double f0 = P.mean[(size_t)a * P.ncand], ft = P.tmean[a];
     const double *fpm = P.fpm + (size_t)a * 12, *dtr = P.dtrial + (size_t)a * 6;
-    int bi = -1, bs = 0; double fb = f0;
-    for (int i = 0; i < 6; i++) {
-        if (!P.en[i]) continue;
-        if (fpm[2 * i] > fb) { fb = fpm[2 * i]; bi = i; bs = 1; }
-        if (fpm[2 * i + 1] > fb) { fb = fpm[2 * i + 1]; bi = i; bs = -1; }
-    }
+    int bi, bs; double fb;
+    const CompassMove mv = compass_accept<6>(f0, ft, fpm, fpm + 6, P.en, bi, bs, fb);
     double d[6] = { 0, 0, 0, 0, 0, 0 };
-    bool move = false;
-    if (ft > f0 && ft >= fb) { for (int i = 0; i < 6; i++) d[i] = dtr[i]; move = true; }
-    else if (bi >= 0) { d[bi] = bs * (bi < 3 ? P.ha : P.hs); move = true; }
-    if (move) {
+    if (mv == kCompassTrial) for (int i = 0; i < 6; i++) d[i] = dtr[i];
+    else if (mv == kCompassProbe) d[bi] = bs * (bi < 3 ? P.ha : P.hs);
+    if (mv != kCompassStay) {
         if (P.kind == PPM_CSP_PARTICLES) {
-            double *N = P.Nmat + (size_t)u * P.nstride, *p = P.pshift + (size_t)u * P.pstride;
-            for (int k = 0; k < 3; k++)
-                if (d[k] != 0.0) { double R[9], T[9]; d_rot_xyz(k, d[k], R); d_mat_mul3(N, R, T); for (int q = 0; q < 9; q++) N[q] = T[q]; }
-            for (int k = 0; k < 3; k++) p[k] += d[3 + k];
+            unit_apply_delta(P.Nmat + (size_t)u * P.nstride, P.pshift + (size_t)u * P.pstride, d);
         } else {
             double *tl = P.tl + (size_t)u * 4;
             tl[0] += d[0]; tl[1] += d[1]; tl[2] += d[3]; tl[3] += d[4];

@@ -1,5 +1,5 @@
-// ppm_geom.h — host-side derived geometry of a refinement call (band limits, shift grid,
-// orientation grid, ring-ordered sample list).  Plain C++, no HIP types; the constexpr prep_lds is also called by k_prep on the device.
+// ppm_geom.h — derived geometry of a refinement call (band limits, shift grid, orientation grid, ring-ordered sample list) and the rules
+// that host and kernels share: the pose algebra, the compass rule (PPM_HD) and the constexpr prep_lds.  Plain C++, no HIP types.
 //
 // The quantities restate the numeric answers of the refine3d prompt script
 // (src/pyp/refine/frealign/frealign.py:3918-3994) in Fourier-pixel units; the grid is the
@@ -17,6 +17,27 @@
 namespace ppm {
 
 constexpr double kPi = 3.14159265358979323846;
+
+// What the kernels call as well as the host is marked PPM_HD: `__host__ __device__` under hipcc, nothing under a plain C++ compiler
+// (the CPU tests compile this header alone with g++).
+#ifdef __HIPCC__
+#define PPM_HD __host__ __device__
+#define PPM_FORCEINLINE __forceinline__
+#define PPM_UNROLL _Pragma("unroll")
+#else
+#define PPM_HD
+#define PPM_FORCEINLINE inline
+#define PPM_UNROLL
+#endif
+// Sine and cosine of a rotation step (radians; rot_xyz, rot_step), the call each side has always made: sincos in device code,
+// std::sin and std::cos on the host.  Nobody has shown that the two agree to the last bit, and nothing depends on it.
+PPM_HD inline void sincos_rad(double t, double *s, double *c) {
+#ifdef __HIP_DEVICE_COMPILE__
+    ::sincos(t, s, c);
+#else
+    *c = std::cos(t); *s = std::sin(t);
+#endif
+}
 
 struct Geom {
     int N = 0;
@@ -136,10 +157,17 @@ inline void grid_direction(const Geom &g, int dir, double &theta, double &phi) {
     theta = phi = 0;
 }
 
+// ---- pose algebra: one text for the host, the kernels and the CPU tests.  PPM_HD marks what device code calls as well.
 // M = Rz(phi) Ry(theta) Rz(psi), row-major 3x3 ("rotates the reference by PHI -> THETA -> PSI",
 // src/pyp/analysis/geometry/core.py:1186-1187)
-inline void euler_matrix(double psi, double theta, double phi, double M[9]) {
-    double ps = psi * kPi / 180, th = theta * kPi / 180, ph = phi * kPi / 180;
+PPM_HD inline void euler_matrix(double psi, double theta, double phi, double M[9]) {
+    // the kernels have always multiplied by the folded constant pi / 180 here and the host by pi, then divided: one rounding apart,
+    // kept on each side (every other conversion below is the host's text on both)
+#ifdef __HIP_DEVICE_COMPILE__
+    const double d2r = kPi / 180.0, ps = psi * d2r, th = theta * d2r, ph = phi * d2r;
+#else
+    const double ps = psi * kPi / 180, th = theta * kPi / 180, ph = phi * kPi / 180;
+#endif
     double cps = std::cos(ps), sps = std::sin(ps), cth = std::cos(th), sth = std::sin(th), cph = std::cos(ph), sph = std::sin(ph);
     M[0] = cph * cth * cps - sph * sps; M[1] = -cph * cth * sps - sph * cps; M[2] = cph * sth;
     M[3] = sph * cth * cps + cph * sps; M[4] = -sph * cth * sps + cph * cps; M[5] = sph * sth;
@@ -147,7 +175,9 @@ inline void euler_matrix(double psi, double theta, double phi, double M[9]) {
 }
 
 // (psi, theta, phi) in degrees of M = Rz(phi) Ry(theta) Rz(psi); at theta = 0 / 180 everything goes into psi
-inline void angles_from_matrix(const double M[9], double &psi, double &theta, double &phi) {
+// (known defect, as in the oracle and synth.py: at theta = 180 the psi returned is mirrored, phi - psi where M = Ry(180) Rz(psi - phi) has
+// atan2(M[3], -M[0]); tests/test_compass_rule_cpu.py pins it until all copies are corrected together)
+PPM_HD inline void angles_from_matrix(const double M[9], double &psi, double &theta, double &phi) {
     const double r2d = 180.0 / kPi;
     double ct = M[8] > 1 ? 1 : (M[8] < -1 ? -1 : M[8]);
     double st = std::sqrt(M[2] * M[2] + M[5] * M[5]);
@@ -157,32 +187,135 @@ inline void angles_from_matrix(const double M[9], double &psi, double &theta, do
     if (phi < 0) phi += 360;
 }
 
-inline void mat_mul3h(const double *a, const double *b, double *c) {
+PPM_HD inline void mat_mul3(const double *a, const double *b, double *c) {      // c may be a or b
     double t[9];
-    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { double v = 0; for (int k = 0; k < 3; k++) v += a[i * 3 + k] * b[k * 3 + j]; t[i * 3 + j] = v; }
-    std::memcpy(c, t, sizeof(t));
+    PPM_UNROLL
+    for (int i = 0; i < 3; i++)
+        PPM_UNROLL
+        for (int j = 0; j < 3; j++) {
+            double v = 0;
+            PPM_UNROLL
+            for (int k = 0; k < 3; k++) v += a[i * 3 + k] * b[k * 3 + j];
+            t[i * 3 + j] = v;
+        }
+    PPM_UNROLL
+    for (int i = 0; i < 9; i++) c[i] = t[i];
 }
-inline void rot_xyz(int k, double deg, double R[9]) {      // right-handed rotation about x (0), y (1), z (2)
-    double t = deg * kPi / 180, c = std::cos(t), s = std::sin(t);
-    double rx[9] = { 1, 0, 0, 0, c, -s, 0, s, c }, ry[9] = { c, 0, s, 0, 1, 0, -s, 0, c }, rz[9] = { c, -s, 0, s, c, 0, 0, 0, 1 };
-    std::memcpy(R, k == 0 ? rx : (k == 1 ? ry : rz), sizeof(rx));
+PPM_HD inline void rot_xyz(int k, double deg, double R[9]) {      // right-handed rotation about x (0), y (1), z (2)
+    double s, c;
+    sincos_rad(deg * kPi / 180.0, &s, &c);
+    if (k == 0) { R[0] = 1; R[1] = 0; R[2] = 0; R[3] = 0; R[4] = c; R[5] = -s; R[6] = 0; R[7] = s; R[8] = c; }
+    else if (k == 1) { R[0] = c; R[1] = 0; R[2] = s; R[3] = 0; R[4] = 1; R[5] = 0; R[6] = -s; R[7] = 0; R[8] = c; }
+    else { R[0] = c; R[1] = -s; R[2] = 0; R[3] = s; R[4] = c; R[5] = 0; R[6] = 0; R[7] = 0; R[8] = 1; }
 }
 // Row pose of the constrained geometry (include/ppm.h, ppm_csp_cfg): M_row = N Ry(-tilt) Rz(axis),
 // g = [Rz(-axis) Ry(tilt) (-p)]_xy + tilt shift (pixels)
 // the four rotations a tilt contributes to its rows' poses (the trigonometry of csp_row_pose, shared by all rows of the tilt)
 struct TiltRot { double a[9], b[9], ai[9], bi[9]; };     // Ry(-tilt), Rz(axis), Rz(-axis), Ry(tilt)
-inline void tilt_rotations(double tilt, double axis, TiltRot &r) { rot_xyz(1, -tilt, r.a); rot_xyz(2, axis, r.b); rot_xyz(2, -axis, r.ai); rot_xyz(1, tilt, r.bi); }
-inline void csp_row_pose(const double N[9], const double p[3], const TiltRot &r, double tsx, double tsy, double M[9], double g[2]) {
+PPM_HD inline void tilt_rotations(double tilt, double axis, TiltRot &r) { rot_xyz(1, -tilt, r.a); rot_xyz(2, axis, r.b); rot_xyz(2, -axis, r.ai); rot_xyz(1, tilt, r.bi); }
+PPM_HD inline void csp_row_pose(const double N[9], const double p[3], const TiltRot &r, double tsx, double tsy, double M[9], double g[2]) {
     double t[9];
-    mat_mul3h(N, r.a, t); mat_mul3h(t, r.b, M);
-    double q[3] = { -p[0], -p[1], -p[2] }, u[3], v[3];
-    for (int i = 0; i < 3; i++) u[i] = r.bi[i * 3] * q[0] + r.bi[i * 3 + 1] * q[1] + r.bi[i * 3 + 2] * q[2];
-    for (int i = 0; i < 3; i++) v[i] = r.ai[i * 3] * u[0] + r.ai[i * 3 + 1] * u[1] + r.ai[i * 3 + 2] * u[2];
+    mat_mul3(N, r.a, t); mat_mul3(t, r.b, M);
+    const double q0 = -p[0], q1 = -p[1], q2 = -p[2];
+    double u[3], v[2];
+    PPM_UNROLL
+    for (int i = 0; i < 3; i++) u[i] = r.bi[i * 3] * q0 + r.bi[i * 3 + 1] * q1 + r.bi[i * 3 + 2] * q2;
+    PPM_UNROLL
+    for (int i = 0; i < 2; i++) v[i] = r.ai[i * 3] * u[0] + r.ai[i * 3 + 1] * u[1] + r.ai[i * 3 + 2] * u[2];
     g[0] = v[0] + tsx; g[1] = v[1] + tsy;
 }
-inline void csp_row_pose(const double N[9], const double p[3], double tilt, double axis, double tsx, double tsy, double M[9], double g[2]) {
+PPM_HD inline void csp_row_pose(const double N[9], const double p[3], double tilt, double axis, double tsx, double tsy, double M[9], double g[2]) {
     TiltRot r; tilt_rotations(tilt, axis, r);
     csp_row_pose(N, p, r, tsx, tsy, M, g);
+}
+// a displacement d[6] applied to a particle unit: N <- N Rx(d0) Ry(d1) Rz(d2) (a zero angle is skipped, not multiplied in), p += d[3..5]
+PPM_HD inline void unit_apply_delta(double *N, double *p, const double *d) {
+    for (int k = 0; k < 3; k++)
+        if (d[k] != 0.0) { double R[9]; rot_xyz(k, d[k], R); mat_mul3(N, R, N); }
+    for (int k = 0; k < 3; k++) p[k] += d[3 + k];
+}
+
+// One step of the local refinement's search.  which: 0 = in-plane (psi), 1 / 2 = tilt about image x / y when tilt_frame, else
+// theta / phi Euler steps.  The three image-frame steps are right-multiplications by Rz / Rx / Ry: plain column mixes.
+// (column indices are compile-time constants: with run-time indices the 3 x 3 temporaries lived in scratch memory, ~1.2 MB
+// of scratch traffic per particle from the serial set-up sections)
+template <int A, int B, int K>
+PPM_HD PPM_FORCEINLINE void col_mix(const double *M, double s, double c, double *out) {
+    // M R with R rotating the (A, B) coordinate pair: out[:,A] = c M[:,A] + s M[:,B], out[:,B] = -s M[:,A] + c M[:,B]
+    PPM_UNROLL
+    for (int r = 0; r < 3; r++) {
+        const double ma = M[r * 3 + A], mb = M[r * 3 + B];
+        out[r * 3 + A] = ma * c + mb * s;
+        out[r * 3 + B] = mb * c - ma * s;
+        out[r * 3 + K] = M[r * 3 + K];
+    }
+}
+PPM_HD inline void rot_step(const double *M, int which, int tilt_frame, double hdeg, double *out) {
+    double s, c;
+    sincos_rad(hdeg * kPi / 180.0, &s, &c);
+    if (which == 0) { col_mix<0, 1, 2>(M, s, c, out); return; }
+    if (tilt_frame) {
+        if (which == 1) col_mix<1, 2, 0>(M, s, c, out); else col_mix<2, 0, 1>(M, s, c, out);
+        return;
+    }
+    if (which == 2) { double r[9] = { c, -s, 0, s, c, 0, 0, 0, 1 }; mat_mul3(r, M, out); return; }
+    double psi, th, ph; angles_from_matrix(M, psi, th, ph);
+    double cp = std::cos(ph * kPi / 180.0), sp = std::sin(ph * kPi / 180.0);
+    double rz[9] = { cp, -sp, 0, sp, cp, 0, 0, 0, 1 }, rzt[9] = { cp, sp, 0, -sp, cp, 0, 0, 0, 1 }, ry[9] = { c, 0, s, 0, 1, 0, -s, 0, c };
+    double T[9], L[9];
+    mat_mul3(rz, ry, T); mat_mul3(T, rzt, L); mat_mul3(L, M, out);
+}
+
+// ---- the compass rule: what one iteration of every search (k_local; k_csp_step_trial / k_csp_step_accept for the constrained and the
+// sub-tomogram searches) decides from its scores.  It restates the oracle's loops operand for operand; tests/test_compass_rule_cpu.py
+// holds it to them bit for bit.  NP parameters, the first three angles (step ha), the rest shifts (step hs); en[] switches them.
+constexpr double kNoProbe = -1e300;       // score of a probe outside the bounds, and of a disabled parameter's
+// Trial step d[] from the centre's score f0 and the probes' scores: per enabled parameter the vertex of the parabola through f(-h), f0,
+// f(+h), clamped to +-h; without usable curvature (den <= 1e-12) a full step towards the better probe if that beats f0.  The probes
+// come two per enabled parameter, + before -, in parameter order: `pang` those of the angles, `psh` those of the shifts (null: they
+// follow the angles'; k_local's sweep keeps the centre between the two runs).  With bounds (tol != null; acc = the displacement so far) a probe that would
+// leave +-tol counts as kNoProbe, a parameter with one probe left steps towards it if it beats f0, and acc + d is clamped to +-tol;
+// tol == null is the unbounded search: both probes in bounds and no clamp, the same arithmetic and nothing more.
+// fp[] / fm[] receive the probes' scores as compass_accept wants them.
+template <int NP>
+PPM_HD inline void compass_trial(double f0, const double *pang, const double *psh, const int *en, double ha, double hs,
+                                 const double *acc, const double *tol, double *d, double *fp, double *fm) {
+    const double *q = pang;
+    for (int i = 0; i < NP; i++) {
+        d[i] = 0; fp[i] = fm[i] = kNoProbe;
+        if (i == 3 && psh) q = psh;
+        if (!en[i]) continue;
+        const double h = i < 3 ? ha : hs;
+        const bool okp = !tol || std::fabs(acc[i] + h) <= tol[i] + 1e-9, okm = !tol || std::fabs(acc[i] - h) <= tol[i] + 1e-9;
+        const double p = okp ? q[0] : kNoProbe, m = okm ? q[1] : kNoProbe;
+        q += 2;
+        fp[i] = p; fm[i] = m;
+        if (okp && okm) {
+            const double den = 2.0 * f0 - p - m;
+            if (den > 1e-12) { const double t = 0.5 * h * (p - m) / den; d[i] = t > h ? h : (t < -h ? -h : t); }
+            else { const double best = p > m ? p : m; d[i] = best > f0 ? (p > m ? h : -h) : 0.0; }
+        } else if (okp) d[i] = p > f0 ? h : 0.0;
+        else if (okm) d[i] = m > f0 ? -h : 0.0;
+        if (tol) {
+            if (acc[i] + d[i] > tol[i]) d[i] = tol[i] - acc[i];
+            if (acc[i] + d[i] < -tol[i]) d[i] = -tol[i] - acc[i];
+        }
+    }
+}
+// What the iteration does once the trial pose is scored (ft): the trial step if it beats the centre and is no worse than the best probe,
+// else the best single probe (scanned in parameter order, + before -, a later one has to be strictly better), else nothing.
+// bi / bs: parameter and sign of the best probe (bi < 0: none beats f0), fb its score.
+enum CompassMove { kCompassStay = 0, kCompassTrial, kCompassProbe };
+template <int NP>
+PPM_HD inline CompassMove compass_accept(double f0, double ft, const double *fp, const double *fm, const int *en, int &bi, int &bs, double &fb) {
+    bi = -1; bs = 0; fb = f0;
+    for (int i = 0; i < NP; i++) {
+        if (!en[i]) continue;
+        if (fp[i] > fb) { fb = fp[i]; bi = i; bs = 1; }
+        if (fm[i] > fb) { fb = fm[i]; bi = i; bs = -1; }
+    }
+    if (ft > f0 && ft >= fb) return kCompassTrial;
+    return bi >= 0 ? kCompassProbe : kCompassStay;
 }
 
 // Frequency marching: band of one compass iteration from its probe displacement (angle step `ha` degrees at the mask radius `rm_px`,
@@ -291,7 +424,7 @@ inline PrepPlan prep_plan(int N, int B, int W) {
 }
 
 // SCORE / SIGMA / LOGP columns of a row from its correlation over the band r_lo .. r_hi (Fourier pixels)
-inline void score_columns(double cc, double r_lo, double r_hi, double *score, double *sigma, double *logp) {
+PPM_HD inline void score_columns(double cc, double r_lo, double r_hi, double *score, double *sigma, double *logp) {
     double res = 1.0 - cc * cc; if (res < 1e-6) res = 1e-6;
     *score = 100.0 * cc; *sigma = std::sqrt(res);
     *logp = -0.5 * (kPi * (r_hi * r_hi - r_lo * r_lo)) * (std::log(2.0 * kPi * res) + 1.0);
@@ -343,14 +476,6 @@ inline void build_samples(const Geom &g, SampleList &sl) {
 }
 
 // Point-group operators (row-major 3x3 each); "C1","Cn","Dn","T","O","I"
-inline void mat_mul3(const double *a, const double *b, double *c) {
-    double t[9];
-    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) {
-        double v = 0; for (int k = 0; k < 3; k++) v += a[i * 3 + k] * b[k * 3 + j];
-        t[i * 3 + j] = v;
-    }
-    std::memcpy(c, t, sizeof(t));
-}
 inline void rot_axis(const double ax[3], double deg, double *m) {
     double n = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
     double x = ax[0] / n, y = ax[1] / n, z = ax[2] / n, t = deg * kPi / 180, c = std::cos(t), s = std::sin(t), C = 1 - c;

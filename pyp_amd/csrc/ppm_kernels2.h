@@ -8,74 +8,6 @@ namespace ppm {
 // One refinement trajectory.  M = Rz(phi) Ry(theta) Rz(psi) row-major; shifts in pixels.
 struct LState { double M[9]; double sh[2]; double f, ha, hs; int particle; int pad; double fc; };   // fc: score over the classification band (answer 22), set by the final launch
 
-__device__ inline void d_mat_mul3(const double *a, const double *b, double *c) {
-    double t[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            double v = 0;
-#pragma unroll
-            for (int k = 0; k < 3; k++) v += a[i * 3 + k] * b[k * 3 + j];
-            t[i * 3 + j] = v;
-        }
-#pragma unroll
-    for (int i = 0; i < 9; i++) c[i] = t[i];
-}
-
-__device__ inline void d_euler(double psi, double theta, double phi, double *M) {
-    const double d2r = 3.14159265358979323846 / 180.0;
-    double cps = cos(psi * d2r), sps = sin(psi * d2r), cth = cos(theta * d2r), sth = sin(theta * d2r), cph = cos(phi * d2r), sph = sin(phi * d2r);
-    M[0] = cph * cth * cps - sph * sps; M[1] = -cph * cth * sps - sph * cps; M[2] = cph * sth;
-    M[3] = sph * cth * cps + cph * sps; M[4] = -sph * cth * sps + cph * cps; M[5] = sph * sth;
-    M[6] = -sth * cps;                  M[7] = sth * sps;                    M[8] = cth;
-}
-
-__device__ inline void d_angles(const double *M, double &psi, double &theta, double &phi) {
-    const double r2d = 180.0 / 3.14159265358979323846;
-    double ct = M[8] > 1 ? 1 : (M[8] < -1 ? -1 : M[8]);
-    double st = sqrt(M[2] * M[2] + M[5] * M[5]);
-    if (st > 1e-7) {
-        theta = atan2(st, ct) * r2d; phi = atan2(M[5], M[2]) * r2d; psi = atan2(M[7], -M[6]) * r2d;
-    } else {
-        theta = ct > 0 ? 0.0 : 180.0; phi = 0.0;
-        psi = (ct > 0 ? atan2(M[3], M[0]) : atan2(-M[3], -M[0])) * r2d;
-    }
-    if (psi < 0) psi += 360;
-    if (phi < 0) phi += 360;
-}
-
-// which: 0 = in-plane (psi), 1 / 2 = tilt about image x / y when tilt_frame, else theta / phi Euler steps.
-// The three image-frame steps are right-multiplications by Rz / Rx / Ry: plain column mixes.
-// (column indices are compile-time constants: with run-time indices the 3 x 3 temporaries lived in scratch memory, ~1.2 MB
-// of scratch traffic per particle from the serial set-up sections)
-template <int A, int B, int K>
-__device__ __forceinline__ void d_col_mix(const double *M, double s, double c, double *out) {
-    // M R with R rotating the (A, B) coordinate pair: out[:,A] = c M[:,A] + s M[:,B], out[:,B] = -s M[:,A] + c M[:,B]
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        const double ma = M[r * 3 + A], mb = M[r * 3 + B];
-        out[r * 3 + A] = ma * c + mb * s;
-        out[r * 3 + B] = mb * c - ma * s;
-        out[r * 3 + K] = M[r * 3 + K];
-    }
-}
-__device__ inline void d_rot_step(const double *M, int which, int tilt_frame, double hdeg, double *out) {
-    double s, c;
-    sincos(hdeg * 3.14159265358979323846 / 180.0, &s, &c);
-    if (which == 0) { d_col_mix<0, 1, 2>(M, s, c, out); return; }
-    if (tilt_frame) {
-        if (which == 1) d_col_mix<1, 2, 0>(M, s, c, out); else d_col_mix<2, 0, 1>(M, s, c, out);
-        return;
-    }
-    if (which == 2) { double r[9] = { c, -s, 0, s, c, 0, 0, 0, 1 }; d_mat_mul3(r, M, out); return; }
-    double psi, th, ph; d_angles(M, psi, th, ph);
-    double cp = cos(ph * 3.14159265358979323846 / 180.0), sp = sin(ph * 3.14159265358979323846 / 180.0);
-    double rz[9] = { cp, -sp, 0, sp, cp, 0, 0, 0, 1 }, rzt[9] = { cp, sp, 0, -sp, cp, 0, 0, 0, 1 }, ry[9] = { c, 0, s, 0, 1, 0, -s, 0, c };
-    double T[9], L[9];
-    d_mat_mul3(rz, ry, T); d_mat_mul3(T, rzt, L); d_mat_mul3(L, M, out);
-}
-
 constexpr int kMaxIters = 24;
 struct LocalP {
     CubeView cv; const uint32_t *samples; const float2 *Il; const float *cw;
@@ -94,7 +26,7 @@ struct LocalP {
 
 // restraint of one pose (k_local's compass; same expression as the oracle's prior_pen)
 __device__ inline double d_prior_pen(const LocalP &P, const double *M, double shx, double shy) {
-    double v[5]; d_angles(M, v[0], v[1], v[2]); v[3] = shx; v[4] = shy;
+    double v[5]; angles_from_matrix(M, v[0], v[1], v[2]); v[3] = shx; v[4] = shy;
     double pen = 0;
 #pragma unroll
     for (int i = 0; i < 5; i++) {
@@ -335,7 +267,7 @@ __global__ void __launch_bounds__(256, PPM_LOCAL_MINW) k_local(LocalP P) {
                     for (int k = 0; k < i; k++) g += P.en[k] ? 2 : 0;
                     g += sg;
                     double Mq[9];
-                    d_rot_step(st.M, i, tilt, sg ? -st.ha : st.ha, Mq);
+                    rot_step(st.M, i, tilt, sg ? -st.ha : st.ha, Mq);
                     set_rot(g, Mq); plan.nv[g] = 1; plan.slot0[g] = g;
                     plan.sh[g][0] = (float)st.sh[0]; plan.sh[g][1] = (float)st.sh[1];
                     if (P.use_priors) spen[g] = d_prior_pen(P, Mq, st.sh[0], st.sh[1]);
@@ -369,45 +301,27 @@ __global__ void __launch_bounds__(256, PPM_LOCAL_MINW) k_local(LocalP P) {
         sweep_plan<TAB>(plan, SC, tid, nthr);
         if (tid == 0) {
             if (phase == PH_COMPASS) {
-                int q = 0, qc = 0;
+                int qc = 0;                              // slot of the centre: the angles' probes lie before it, the shifts' after it
                 for (int i = 0; i < 3; i++) qc += P.en[i] ? 2 : 0;
                 if (P.use_priors) for (int k = 0; k < plan.nslots; k++) score[k] -= spen[k];
                 const double f0 = score[qc];
                 sf0 = f0;
-                for (int i = 0; i < 5; i++) {
-                    sd[i] = 0; sfp[i] = sfm[i] = -1e300;
-                    if (i == 3) q = qc + 1;
-                    if (!P.en[i]) continue;
-                    double h = i < 3 ? st.ha : st.hs;
-                    sfp[i] = score[q]; sfm[i] = score[q + 1]; q += 2;
-                    double den = 2.0 * f0 - sfp[i] - sfm[i];
-                    if (den > 1e-12) {
-                        double t = 0.5 * h * (sfp[i] - sfm[i]) / den;
-                        sd[i] = t > h ? h : (t < -h ? -h : t);
-                    } else {
-                        double best = sfp[i] > sfm[i] ? sfp[i] : sfm[i];
-                        sd[i] = best > f0 ? (sfp[i] > sfm[i] ? h : -h) : 0.0;
-                    }
-                }
+                compass_trial<5>(f0, score, score + qc + 1, P.en, st.ha, st.hs, nullptr, nullptr, sd, sfp, sfm);      // unbounded
                 double T9[9];
                 for (int k = 0; k < 9; k++) sMt[k] = st.M[k];
-                for (int i = 0; i < 3; i++) if (P.en[i] && sd[i] != 0) { d_rot_step(sMt, i, tilt, sd[i], T9); for (int k = 0; k < 9; k++) sMt[k] = T9[k]; }
+                for (int i = 0; i < 3; i++) if (P.en[i] && sd[i] != 0) { rot_step(sMt, i, tilt, sd[i], T9); for (int k = 0; k < 9; k++) sMt[k] = T9[k]; }
                 sshq[0] = st.sh[0] + sd[3]; sshq[1] = st.sh[1] + sd[4];
                 single(sMt, sshq);                       // band fields stay those of the iteration
             } else if (phase == PH_TRIAL) {
                 const double ft = score[0] - (P.use_priors ? d_prior_pen(P, sMt, sshq[0], sshq[1]) : 0.0), f0 = sf0;
-                int bi = -1, bs = 0; double fb = f0;
-                for (int i = 0; i < 5; i++) {
-                    if (!P.en[i]) continue;
-                    if (sfp[i] > fb) { fb = sfp[i]; bi = i; bs = 1; }
-                    if (sfm[i] > fb) { fb = sfm[i]; bi = i; bs = -1; }
-                }
+                int bi, bs; double fb;
+                const CompassMove mv = compass_accept<5>(f0, ft, sfp, sfm, P.en, bi, bs, fb);
                 st.f = f0;
-                if (ft > f0 && ft >= fb) {
+                if (mv == kCompassTrial) {
                     for (int k = 0; k < 9; k++) st.M[k] = sMt[k];
                     st.sh[0] = sshq[0]; st.sh[1] = sshq[1]; st.f = ft;
-                } else if (bi >= 0) {
-                    if (bi < 3) { double T9[9]; d_rot_step(st.M, bi, tilt, bs * st.ha, T9); for (int k = 0; k < 9; k++) st.M[k] = T9[k]; }
+                } else if (mv == kCompassProbe) {
+                    if (bi < 3) { double T9[9]; rot_step(st.M, bi, tilt, bs * st.ha, T9); for (int k = 0; k < 9; k++) st.M[k] = T9[k]; }
                     else st.sh[bi - 3] += bs * st.hs;
                     st.f = fb;
                 }
@@ -432,7 +346,7 @@ __global__ void k_states_from_hits(const Hit *hits, LState *states, int n, int K
     Hit h = hits[i];
     LState s;
     int dir = h.orient / n_psi, k = h.orient - dir * n_psi;
-    d_euler(k * dpsi, dir_theta[dir], dir_phi[dir], s.M);
+    euler_matrix(k * dpsi, dir_theta[dir], dir_phi[dir], s.M);
     s.sh[0] = h.sx * step; s.sh[1] = h.sy * step;
     s.f = h.cc; s.fc = h.cc; s.ha = ha0; s.hs = hs0; s.particle = i / K; s.pad = 0;
     states[i] = s;
@@ -443,7 +357,7 @@ __global__ void k_states_from_rows(const double *rows, LState *states, int n, do
     if (i >= n) return;
     const double *r = rows + (size_t)i * PPM_NCOL;
     LState s;
-    d_euler(r[PPM_PSI], r[PPM_THETA], r[PPM_PHI], s.M);
+    euler_matrix(r[PPM_PSI], r[PPM_THETA], r[PPM_PHI], s.M);
     s.sh[0] = r[PPM_XSHIFT] / a; s.sh[1] = r[PPM_YSHIFT] / a;
     s.f = 0; s.fc = 0; s.ha = ha0; s.hs = hs0; s.particle = i; s.pad = 0;
     states[i] = s;
@@ -573,15 +487,14 @@ __global__ void k_rows_out(const LState *states, const double *rows_in, double *
     double *o = rows_out + (size_t)i * PPM_NCOL;
     const double *r = rows_in + (size_t)i * PPM_NCOL;
     for (int c = 0; c < PPM_NCOL; c++) o[c] = r[c];
-    double psi, th, ph; d_angles(s.M, psi, th, ph);
+    double psi, th, ph; angles_from_matrix(s.M, psi, th, ph);
     o[PPM_PSI] = psi; o[PPM_THETA] = th; o[PPM_PHI] = ph;
     o[PPM_XSHIFT] = s.sh[0] * a; o[PPM_YSHIFT] = s.sh[1] * a;
     if (ddef) { o[PPM_DF1] = r[PPM_DF1] + (double)ddef[i]; o[PPM_DF2] = r[PPM_DF2] + (double)ddef[i]; }
+    // LOGP / SIGMA over r_lo .. r_cls (answer 22; r_cls = r_hi and fc = f when no classification limit applies); SCORE over the full band
+    double score_cls;
+    score_columns(s.fc, r_lo, r_cls, &score_cls, &o[PPM_SIGMA], &o[PPM_LOGP]);
     o[PPM_SCORE] = 100.0 * s.f;
-    // LOGP / SIGMA over r_lo .. r_cls (answer 22; r_cls = r_hi and fc = f when no classification limit applies)
-    double cc = s.fc, res = 1.0 - cc * cc; if (res < 1e-6) res = 1e-6;
-    o[PPM_SIGMA] = sqrt(res);
-    o[PPM_LOGP] = -0.5 * (3.14159265358979323846 * (r_cls * r_cls - r_lo * r_lo)) * (log(2.0 * 3.14159265358979323846 * res) + 1.0);
 }
 
 // ---------------------------------------------------------------------------------- brick-binned insertion
@@ -623,7 +536,7 @@ __global__ void k_insert_params(const double *rows, PartIns *pp, CullEnt *cull, 
     q.valid = (occ > 0 && !(scr < score_thr)) ? 1 : 0;
     long key = split_by_pind ? (long)row[PPM_PIND] : (long)row[PPM_POS];
     q.half = (int)(((key % 2) + 2) % 2);
-    double M[9]; d_euler(row[PPM_PSI], row[PPM_THETA], row[PPM_PHI], M);
+    double M[9]; euler_matrix(row[PPM_PSI], row[PPM_THETA], row[PPM_PHI], M);
     q.m[0] = (float)M[0]; q.m[1] = (float)M[1]; q.m[2] = (float)M[3]; q.m[3] = (float)M[4]; q.m[4] = (float)M[6]; q.m[5] = (float)M[7];
     q.ctf = ctf_from_row(row, N, a);
     q.sx = (float)(row[PPM_XSHIFT] / a); q.sy = (float)(row[PPM_YSHIFT] / a);

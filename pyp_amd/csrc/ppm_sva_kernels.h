@@ -398,14 +398,14 @@ __global__ void __launch_bounds__(256, PPM_SVA_EVAL_MINW) k_sva_eval(SvaEvalP P)
     const int st = blockIdx.x, part = blockIdx.y, v = P.vmap ? P.vmap[st] : st, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ncand = P.ncand;
     if (tid < ncand) {
         const double *d = P.delta + ((size_t)st * ncand + tid) * 6, *pose = P.poses + (size_t)st * 12;
-        double Nm[9];
+        double Nm[9], p[3];
 #pragma unroll
         for (int k = 0; k < 9; k++) Nm[k] = pose[k];
-        for (int k = 0; k < 3; k++)
-            if (d[k] != 0.0) { double R[9], T[9]; d_rot_xyz(k, d[k], R); d_mat_mul3(Nm, R, T); for (int q = 0; q < 9; q++) Nm[q] = T[q]; }
+        for (int k = 0; k < 3; k++) p[k] = pose[9 + k];
+        unit_apply_delta(Nm, p, d);
 #pragma unroll
         for (int k = 0; k < 9; k++) cm[tid][k] = (float)Nm[k];
-        for (int k = 0; k < 3; k++) csh[tid][k] = (float)(pose[9 + k] + d[3 + k]);
+        for (int k = 0; k < 3; k++) csh[tid][k] = (float)p[k];
     }
     const CubeTab tab = cube_tab_fill(P.cv, tabmem, P.tabR, tid, 256);
     __syncthreads();
