@@ -483,9 +483,10 @@ static void angles_from_matrix(const double M[9], double *psi, double *theta, do
         *theta = atan2(st, ct) * 180 / ORC_PI;
         *phi = atan2(M[5], M[2]) * 180 / ORC_PI;
         *psi = atan2(M[7], -M[6]) * 180 / ORC_PI;
-    } else {               /* theta = 0 or 180: only psi +- phi is defined; put it all in psi */
+    } else {               /* theta = 0 or 180: only psi +- phi is defined; put it all in psi.  At 180 M = Rz(phi) Ry(180) Rz(psi)
+                            * has M[0] = -cos(psi - phi), M[3] = sin(psi - phi) */
         *theta = ct > 0 ? 0.0 : 180.0; *phi = 0.0;
-        *psi = (ct > 0 ? atan2(M[3], M[0]) : atan2(-M[3], -M[0])) * 180 / ORC_PI;
+        *psi = (ct > 0 ? atan2(M[3], M[0]) : atan2(M[3], -M[0])) * 180 / ORC_PI;
     }
     if (*psi < 0) *psi += 360; if (*phi < 0) *phi += 360;
 }

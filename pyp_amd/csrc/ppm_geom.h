@@ -175,14 +175,14 @@ PPM_HD inline void euler_matrix(double psi, double theta, double phi, double M[9
 }
 
 // (psi, theta, phi) in degrees of M = Rz(phi) Ry(theta) Rz(psi); at theta = 0 / 180 everything goes into psi
-// (known defect, as in the oracle and synth.py: at theta = 180 the psi returned is mirrored, phi - psi where M = Ry(180) Rz(psi - phi) has
-// atan2(M[3], -M[0]); tests/test_compass_rule_cpu.py pins it until all copies are corrected together)
+// (theta = 0: M = Rz(phi + psi), M[0] = cos, M[3] = sin; theta = 180: M = Rz(phi) Ry(180) Rz(psi) has M[0] = -cos(psi - phi),
+// M[3] = sin(psi - phi), so psi - phi = atan2(M[3], -M[0]))
 PPM_HD inline void angles_from_matrix(const double M[9], double &psi, double &theta, double &phi) {
     const double r2d = 180.0 / kPi;
     double ct = M[8] > 1 ? 1 : (M[8] < -1 ? -1 : M[8]);
     double st = std::sqrt(M[2] * M[2] + M[5] * M[5]);
     if (st > 1e-7) { theta = std::atan2(st, ct) * r2d; phi = std::atan2(M[5], M[2]) * r2d; psi = std::atan2(M[7], -M[6]) * r2d; }
-    else { theta = ct > 0 ? 0.0 : 180.0; phi = 0.0; psi = (ct > 0 ? std::atan2(M[3], M[0]) : std::atan2(-M[3], -M[0])) * r2d; }
+    else { theta = ct > 0 ? 0.0 : 180.0; phi = 0.0; psi = (ct > 0 ? std::atan2(M[3], M[0]) : std::atan2(M[3], -M[0])) * r2d; }
     if (psi < 0) psi += 360;
     if (phi < 0) phi += 360;
 }

@@ -264,14 +264,15 @@ def rot_xyz(k, deg):
 
 
 def angles_from_matrix(M):
-    """(psi, theta, phi) in [0, 360) of M = euler_matrix(psi, theta, phi)."""
+    """(psi, theta, phi) in [0, 360) of M = euler_matrix(psi, theta, phi); at theta = 0 / 180 everything goes into psi (phi = 0):
+    Rz(phi) Ry(180) Rz(psi) has M[0, 0] = -cos(psi - phi), M[1, 0] = sin(psi - phi)."""
     ct = min(1.0, max(-1.0, M[2, 2]))
     st = math.hypot(M[0, 2], M[1, 2])
     if st > 1e-7:
         theta, phi, psi = math.atan2(st, ct), math.atan2(M[1, 2], M[0, 2]), math.atan2(M[2, 1], -M[2, 0])
     else:
         theta, phi = (0.0 if ct > 0 else math.pi), 0.0
-        psi = math.atan2(M[1, 0], M[0, 0]) if ct > 0 else math.atan2(-M[1, 0], -M[0, 0])
+        psi = math.atan2(M[1, 0], M[0, 0]) if ct > 0 else math.atan2(M[1, 0], -M[0, 0])
     out = np.degrees([psi, theta, phi])
     out[out < 0] += 360.0
     return out

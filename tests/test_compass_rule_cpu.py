@@ -332,16 +332,12 @@ def test_compass_rule_and_pose_algebra_match_their_restatements(tmp_path):
         assert np.abs(M - euler(ps, th, ph)).max() < 1e-14
         if th == 0.0:                                    # everything goes into psi: M = Rz(psi + phi)
             assert rth == 0.0 and rph == 0.0 and circ(rps, ps + ph) < 1e-9, (ps, th, ph, rps, rth, rph)
-        elif th == 180.0:
-            # KNOWN DEFECT, recorded, not endorsed: here M = Ry(180) Rz(psi - phi), M[0] = -cos, M[3] = sin, so the angle is
-            # atan2(M[3], -M[0]); the code (and with it the oracle and pyp_amd/synth.py: one expression in all of them) has
-            # atan2(-M[3], -M[0]) and returns phi - psi, the mirror image: (12.5, 180, 77) comes back as (64.5, 180, 0), not (295.5, 180, 0).
-            # The round trip the issue asks for therefore does NOT hold at theta = 180.  This test pins what the code returns, so that
-            # the correction - a change of its own, in all copies at once, with a theta = 180 pose through k_rows_out and a synth round
-            # trip to check it - has to come here and turn `ph - ps` into `ps - ph`.
-            assert rth == 180.0 and rph == 0.0 and circ(rps, ph - ps) < 1e-9, (ps, th, ph, rps, rth, rph)
+        elif th == 180.0:                                # M = Ry(180) Rz(psi - phi)
+            assert rth == 180.0 and rph == 0.0 and circ(rps, ps - ph) < 1e-9, (ps, th, ph, rps, rth, rph)
         else:
             assert circ(rps, ps) < 1e-9 and abs(rth - th) < 1e-9 and circ(rph, ph) < 1e-9, (ps, th, ph, rps, rth, rph)
+        # the invariant is the rotation, not the angles: what comes back composes to M, at the poles as anywhere else
+        assert np.abs(euler(rps, rth, rph) - M).max() < 1e-12, (ps, th, ph, rps, rth, rph)
 
     # ---- rot_step: every branch, both frames; 1e-13 per entry (entries <= 1, under 30 roundings of 1.1e-16)
     tol = 1e-13
