@@ -279,6 +279,16 @@ typedef struct ppm_sva_cfg {
                                Build-defined: the absent program ranks peaks of a spherical-harmonics correlation instead */
     float global_step;      /* degrees; 0 = 15 */
     int n_candidates;       /* metric/number_of_candidate_peaks_to_search; 0 = 25, at most 64 */
+    char symmetry[8];       /* point group of the reference, read by search_mode 1 only: "" (= "C1"), "Cn", "Dn", "T", "O", "I" - the symbols of
+                               ppm_refine_cfg.symmetry (<mode>_use_symmetrization n of the protocol -> "Cn"); an unknown symbol or one of more
+                               than 60 operators returns -22.  With more than one operator the grid is cut to the group's asymmetric unit
+                               (phi < phi_max, theta <= theta_max as for ppm_refine_cfg: theta_i = theta_max i / (n - 1), n_phi =
+                               round(phi_max sin theta / step), phi_j = phi_max j / n_phi, psi unchanged) and the candidates are G N0 instead
+                               of N0 G: pose N is equivalent to S N for every operator S (F_v(k) = Ref(N k), Ref(S x) = Ref(x)), so the cut
+                               has to act on the left; the grid holds one copy of every peak instead of n, and ppm_refine_last_counts
+                               reports its size.  "" / "C1": the full grid and N0 G, bit for bit as before.  The reference is used as
+                               given (it is not symmetrised here); the average is symmetrised by the ACCUMULATOR's symbol (ppm_sva_insert).
+                               Build-defined: the absent MPI_Classification's own rule is not visible */
 } ppm_sva_cfg;
 /* volumes: n_vol * box^3 floats (x fastest); wedges: n_vol x {lwedge, uwedge} tilt limits in degrees (tilt axis = y);
  * poses: n_vol x 12 doubles {N row-major (9), shift x y z (pixels)}, start values in, refined values out; scores: n_vol. */
@@ -326,7 +336,12 @@ int ppm_accum_reduce(ppm_accum_t *acc, void *comm, int root);
  * (parity of index[v], or of v when index is NULL; odd -> half 1), with its missing-wedge mask as the weight:
  *     num_h(q) += m_v(k) F_v(k) e^{-2 pi i k.p / box} / box,    den_h(q) += m_v(k),    k = N^T q  (trilinear interpolation of F_v)
  * for |q| < box/2 - 1, m_v = 1 where the tilt angle of (k_x, k_z) lies in the sub-volume's lwedge .. uwedge (cfg->use_missing_wedge)
- * and everywhere otherwise.  `acc` = ppm_accum_create(box, pixel, "C1", ...); ppm_accum_count counts sub-volumes; shards on several
+ * and everywhere otherwise.  `acc` = ppm_accum_create(box, pixel, symmetry, ...), and the ACCUMULATOR's symbol decides the average
+ * (cfg->symmetry is not read here): with operators S_1 = 1, S_2 .. S_n every sub-volume enters once per operator at the pose
+ * (S N, p), i.e. at k = N^T S^T q with the shift phase and the wedge mask taken at that k - operators in order, the batch inside,
+ * den_h(q) grows by one per (sub-volume, operator) inside the wedge - which makes the sums invariant under the group (build-defined:
+ * the absent MPI_Classification's own rule is not visible); "C1" is the plain average.  ppm_accum_count counts sub-volumes ONCE each,
+ * whatever the group; shards on several
  * GPUs are summed with ppm_accum_reduce; ppm_finalize turns the sums into the two half-maps, the FSC-weighted average and the
  * statistics table exactly as for a reconstruction.  Of cfg only box and use_missing_wedge are read.  Build-defined (the absent
  * MPI_Classification's weighting is not visible).  Sub-volumes enter the sums in batches of up to 32 and the counters follow every

@@ -89,7 +89,7 @@ static int sva_insert_device(ppm_accum_t *a, const ppm_sva_cfg *cfg, const float
                              const long *index, long index_base) {
     const int N = cfg->box;
     if (!box_ok(N) || N != a->N) return fail(-22, "sub-volume box differs from the accumulator's box (even, 32..512, prime factors 2, 3, 5, 7)");
-    if (a->nsym != 1) return fail(-22, "sub-tomogram averaging needs a C1 accumulator");
+    if (a->nsym < 1 || a->nsym > kSvaInsMaxSym) return fail(-22, "sub-tomogram averaging: the accumulator has more point-group operators than the kernel holds");
     const size_t n3 = (size_t)N * N * N;
     const int NB = std::min(n_vol, kSvaInsBatch);
     SvaXform T;
@@ -130,10 +130,12 @@ static int sva_insert_device(ppm_accum_t *a, const ppm_sva_cfg *cfg, const float
             else { IP.T = T.A; IP.layout = 0; IP.stats = nullptr; }
         }
         IP.N = N; IP.KX = T.KX; IP.KY = T.KY; IP.nv = m; IP.poses = d_poses.p; IP.wedges = d_wedges.p; IP.half = d_half.p;
-        IP.use_wedge = cfg->use_missing_wedge != 0; IP.scale = 1.0f / (float)N; IP.acc = a->acc;
+        IP.use_wedge = cfg->use_missing_wedge != 0; IP.scale = 1.0f / (float)N; IP.acc = a->acc; IP.sym = a->d_sym; IP.nsym = a->nsym;
         {
             ProfScope ps(PPM_K_INSERT);
-            hipLaunchKernelGGL(k_sva_insert, dim3((unsigned)(((long)N * N * (N / 2 + 1) + 255) / 256)), dim3(256), 0, cur_stream(), IP);
+            const dim3 grid((unsigned)(((long)N * N * (N / 2 + 1) + 255) / 256));
+            if (a->nsym == 1) hipLaunchKernelGGL(k_sva_insert<false>, grid, dim3(256), 0, cur_stream(), IP);
+            else hipLaunchKernelGGL(k_sva_insert<true>, grid, dim3(256), 0, cur_stream(), IP);      // every operator's copy of every sub-volume
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(cur_stream()));          // the host tables of the batch are reused
@@ -206,28 +208,13 @@ static int sva_band_plan(ppm_ref *ref, const ppm_sva_cfg *cfg, double rband) {
     return 0;
 }
 
-// rotations of the global search (ppm_sva_cfg.search_mode 1, include/ppm.h), row-major 3x3 each
-static std::vector<double> sva_rotation_grid(double gstep) {
-    std::vector<double> grid_d;
-    int n_theta = (int)std::floor(180.0 / gstep + 0.5) + 1; if (n_theta < 2) n_theta = 2;
-    int n_psi = (int)std::floor(360.0 / gstep + 0.5); if (n_psi < 1) n_psi = 1;
-    for (int i = 0; i < n_theta; i++) {
-        const double th = 180.0 * i / (n_theta - 1);
-        int np = (int)std::floor(360.0 * std::sin(th * kPi / 180.0) / gstep + 0.5); if (np < 1) np = 1;
-        for (int j = 0; j < np; j++) for (int k = 0; k < n_psi; k++) {
-            double G[9]; euler_matrix(k * 360.0 / n_psi, th, 360.0 * j / np, G);
-            grid_d.insert(grid_d.end(), G, G + 9);
-        }
-    }
-    return grid_d;
-}
-
 namespace {
 // search plan of a call (the particle unit of the constrained search: rotations about the specimen axes + 3-D shift)
 struct SvaPlan {
     int en[6]; double tol[6];           // the compass search about the start pose
     int eng[6]; double tolg[6];         // ... and about a grid rotation (global search)
     bool global = false; double gstep = 15.0; std::vector<double> grid_d; int n_grid = 0, Kc = 0;
+    bool left = false;                  // the grid is cut to the asymmetric unit of ppm_sva_cfg.symmetry: candidates are G N0, not N0 G
     int ncand = 1, T = 0; double steptol = 0.05, ha0 = 0, hs0 = 0;
     double rg = 0;                      // coarse band the grid step allows (probe Delta / 2, rotations only)
 };
@@ -329,7 +316,7 @@ static int sva_global_candidates(SvaSearch &Q, const SvaPlan &P, const std::vect
     const SvaEvalP &EP = Q.EP;
     SvaGlobalP GP;
     GP.cv = EP.cv; GP.samples = EP.samples; GP.bandw = EP.bandw; GP.F = EP.F; GP.S = EP.S; GP.N = EP.N; GP.S_used = Q.prefix_of(P.rg); GP.rmax2 = (float)(P.rg * P.rg);
-    GP.use_wedge = EP.use_wedge; GP.wedges = EP.wedges; GP.poses = Q.d_poses; GP.grid = d_grid; GP.n_grid = n_grid; GP.RC = 8; GP.score = d_gscore;
+    GP.use_wedge = EP.use_wedge; GP.wedges = EP.wedges; GP.poses = Q.d_poses; GP.grid = d_grid; GP.n_grid = n_grid; GP.RC = 8; GP.score = d_gscore; GP.left = P.left;
     { ProfScope ps(PPM_K_GLOBAL); hipLaunchKernelGGL(k_sva_global, dim3((n_grid + GP.RC - 1) / GP.RC, nb), dim3(256), 0, cur_stream(), GP); }
     HIPCHK(hipGetLastError());
     std::vector<float> gsc((size_t)nb * n_grid);
@@ -343,7 +330,9 @@ static int sva_global_candidates(SvaSearch &Q, const SvaPlan &P, const std::vect
         std::partial_sort(order.begin(), order.begin() + Kc, order.end(), [&](int x, int y) { return sc_[x] > sc_[y] || (sc_[x] == sc_[y] && x < y); });
         for (int k = 0; k < Kc; k++) {
             CUnit c = st[v];
-            double Nq[9]; mat_mul3(st[v].N, &P.grid_d[(size_t)order[k] * 9], Nq); std::memcpy(c.N, Nq, sizeof(Nq));
+            const double *G = &P.grid_d[(size_t)order[k] * 9];
+            double Nq[9]; if (P.left) mat_mul3(G, st[v].N, Nq); else mat_mul3(st[v].N, G, Nq);
+            std::memcpy(c.N, Nq, sizeof(Nq));
             cand.push_back(c); vm.push_back(v);
         }
     }
@@ -368,12 +357,13 @@ static int sva_search_chunk(SvaSearch &Q, const SvaPlan &P, const ppm_sva_cfg *c
     return sva_compass(Q, st, nullptr, P.eng, P.tolg, ha, hs, compass_iterations(ha, hs, P.steptol, 0));
 }
 
-static SvaPlan sva_search_plan(const ppm_sva_cfg *cfg, double rband, double rm_px, double bf) {
+// (the symbol of the global search's point group: checked by the caller, "" for every other search mode)
+static SvaPlan sva_search_plan(const ppm_sva_cfg *cfg, const char *sym, int nsym, double rband, double rm_px, double bf) {
     SvaPlan P;
     for (int k = 0; k < 3; k++) { P.en[k] = cfg->tol_angle > 0 && cfg->search_mode != 2; P.tol[k] = cfg->tol_angle; P.en[3 + k] = cfg->tol_shift > 0; P.tol[3 + k] = cfg->tol_shift; }
     P.global = cfg->search_mode == 1;
     P.gstep = cfg->global_step > 0 ? cfg->global_step : 15.0;
-    if (P.global) { P.grid_d = sva_rotation_grid(P.gstep); P.n_grid = (int)(P.grid_d.size() / 9); }
+    if (P.global) { P.grid_d = sva_rotation_grid(P.gstep, sym); P.n_grid = (int)(P.grid_d.size() / 9); P.left = nsym > 1; }
     P.Kc = cfg->n_candidates > 0 ? cfg->n_candidates : 25; P.Kc = std::min(std::min(P.Kc, 64), std::max(P.n_grid, 1));
     for (int k = 0; k < 6; k++) { P.eng[k] = k < 3 ? 1 : P.en[k]; P.tolg[k] = k < 3 ? P.gstep : P.tol[k]; }
     const int nrot = (P.en[0] || P.global) ? 6 : 0, nsh = P.en[3] ? 6 : 0;
@@ -447,7 +437,19 @@ static int sva_align_impl(ppm_ref_t *ref, ppm_accum_t *avg, const ppm_sva_cfg *c
     const double bf = cfg->band_factor == 0 ? 3.0 : cfg->band_factor;
     double rm_px = std::max(cfg->window[0], std::max(cfg->window[1], cfg->window[2]));
     if (!(rm_px > 0)) rm_px = 0.4 * N;
-    const SvaPlan P = sva_search_plan(cfg, rband, rm_px, bf);
+    // the reference's point group cuts the global search's grid to the asymmetric unit; no other search mode reads the field
+    char sym[9] = { 0 }; int nsym = 1;
+    if (cfg->search_mode == 1) {
+        std::memcpy(sym, cfg->symmetry, 8);
+        std::vector<double> ops;
+        nsym = symmetry_ops(sym, ops);
+        const char t = sym[0] >= 'a' ? sym[0] - 32 : sym[0];
+        const int order = std::atoi(sym + 1);
+        // (symmetry_ops stops at 60 operators: an axis of a higher order would come back as a group it is not)
+        if (nsym < 1 || (t == 'C' && nsym != order) || (t == 'D' && nsym != 2 * order))
+            return fail(-22, std::string("unknown symmetry symbol '") + sym + "' in the sub-tomogram alignment settings (C1, Cn, Dn, T, O, I; at most 60 operators)");
+    }
+    const SvaPlan P = sva_search_plan(cfg, sym, nsym, rband, rm_px, bf);
     // ---- device buffers (RAII), chunks of sub-volumes
     // chunks of sub-volumes: the search kernel runs one block per sub-volume, so a chunk should fill the chip (>= 256 blocks).  Resident
     // volumes: limited by the band transforms (S float2 each, 4 GB); host volumes: two staging buffers of a chunk each (2 x 7 GB at

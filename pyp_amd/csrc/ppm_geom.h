@@ -208,6 +208,28 @@ PPM_HD inline void rot_xyz(int k, double deg, double R[9]) {      // right-hande
     else if (k == 1) { R[0] = c; R[1] = 0; R[2] = s; R[3] = 0; R[4] = 1; R[5] = 0; R[6] = -s; R[7] = 0; R[8] = c; }
     else { R[0] = c; R[1] = -s; R[2] = 0; R[3] = s; R[4] = c; R[5] = 0; R[6] = 0; R[7] = 0; R[8] = 1; }
 }
+// Rotations of the sub-tomogram global search (ppm_sva_cfg.search_mode 1, include/ppm.h), row-major 3x3 each: G = E(psi, theta, phi)
+// on rings theta = theta_max i / (n - 1), n = round(theta_max / step) + 1, with n_phi = round(phi_max sin theta / step) directions
+// phi = phi_max j / n_phi each and n_psi = round(360 / step) in-plane angles.  (phi_max, theta_max) = sym_limits(sym): the whole of
+// SO(3) for "" / "C1" - candidates N0 G -, the asymmetric unit of the point group otherwise - candidates G N0, because pose N is
+// equivalent to S N for every operator S (F_v(k) = Ref(N k) and Ref(S x) = Ref(x)) and the cut in phi and theta is one on the left.
+inline std::vector<double> sva_rotation_grid(double gstep, const char *sym) {
+    std::vector<double> grid_d;
+    double phi_max, theta_max;
+    sym_limits(sym, phi_max, theta_max);
+    int n_theta = (int)std::floor(theta_max / gstep + 0.5) + 1; if (n_theta < 2) n_theta = 2;
+    int n_psi = (int)std::floor(360.0 / gstep + 0.5); if (n_psi < 1) n_psi = 1;
+    for (int i = 0; i < n_theta; i++) {
+        const double th = theta_max * i / (n_theta - 1);
+        int np = (int)std::floor(phi_max * std::sin(th * kPi / 180.0) / gstep + 0.5); if (np < 1) np = 1;
+        for (int j = 0; j < np; j++) for (int k = 0; k < n_psi; k++) {
+            double G[9]; euler_matrix(k * 360.0 / n_psi, th, phi_max * j / np, G);
+            grid_d.insert(grid_d.end(), G, G + 9);
+        }
+    }
+    return grid_d;
+}
+
 // Row pose of the constrained geometry (include/ppm.h, ppm_csp_cfg): M_row = N Ry(-tilt) Rz(axis),
 // g = [Rz(-axis) Ry(tilt) (-p)]_xy + tilt shift (pixels)
 // the four rotations a tilt contributes to its rows' poses (the trigonometry of csp_row_pose, shared by all rows of the tilt)

@@ -523,6 +523,7 @@ struct SvaGlobalP {
     const float *grid;                            // [n_grid][9] grid rotations G (row-major)
     int n_grid, RC;
     float *score;                                 // [n_vol][n_grid]
+    int left;                                     // candidates are G N0 (a grid cut to the asymmetric unit of a point group), not N0 G
 };
 
 __global__ void __launch_bounds__(256) k_sva_global(SvaGlobalP P) {
@@ -533,10 +534,11 @@ __global__ void __launch_bounds__(256) k_sva_global(SvaGlobalP P) {
     const int q0 = blockIdx.x * P.RC, q1 = min(q0 + P.RC, P.n_grid);
     for (int q = q0; q < q1; q++) {
         __syncthreads();
-        if (tid < 9) {                       // Nq = N0 G in double, like the oracle
+        if (tid < 9) {                       // Nq = N0 G in double, like the oracle (left: G N0)
             const int i = tid / 3, j = tid % 3;
             double a = 0;
-            for (int k = 0; k < 3; k++) a += P.poses[(size_t)v * 12 + i * 3 + k] * (double)P.grid[(size_t)q * 9 + k * 3 + j];
+            if (P.left) for (int k = 0; k < 3; k++) a += (double)P.grid[(size_t)q * 9 + i * 3 + k] * P.poses[(size_t)v * 12 + k * 3 + j];
+            else for (int k = 0; k < 3; k++) a += P.poses[(size_t)v * 12 + i * 3 + k] * (double)P.grid[(size_t)q * 9 + k * 3 + j];
             Nq[tid] = (float)a;
         }
         __syncthreads();
@@ -576,6 +578,10 @@ __global__ void __launch_bounds__(256) k_sva_global(SvaGlobalP P) {
 // value and weight (the sub-volume's missing-wedge mask at k) to its own sums - no atomics, the same sums in the same order whatever
 // the launch shape.  The voxel's cell of the half-map the sub-volume belongs to (parity of its index) is read and written once.
 // T: the batch's full transforms, layout 1 = B[v][kx][kyi][kz] of the two-step passes (KX = N/2 + 1, KY = N), layout 0 = f[v][z][y][KX].
+// SYM (an accumulator with more than one point-group operator): the voxel walks the operators S (outer loop, operator order) and the
+// batch (inner loop, batch order) and gathers at k = N^T S^T q - the sub-volume at pose (S N, p), equivalent to (N, p) on a reference
+// with Ref(S x) = Ref(x).  Shift phase and wedge test are taken at that k, the weight grows by one per (sub-volume, operator) inside
+// the wedge.  SYM = false: the identity alone (C1), without the operator table and the loop over it.
 struct SvaInsP {
     const float2 *T; int layout, N, KX, KY, nv;
     const double *poses;      // [nv][12] N row-major + shift (pixels)
@@ -584,13 +590,19 @@ struct SvaInsP {
     const int *half;          // [nv] 0 / 1
     int use_wedge; float scale;
     float *acc;
+    const float *sym; int nsym;     // SYM only: the accumulator's operators [nsym][9] row-major, nsym <= kSvaInsMaxSym
 };
 constexpr int kSvaInsBatch = 32;
+constexpr int kSvaInsMaxSym = 60;
 
+template <bool SYM>
 __global__ void __launch_bounds__(256) k_sva_insert(SvaInsP P) {
     __shared__ float sNt[kSvaInsBatch][9], ssh[kSvaInsBatch][3], swd[kSvaInsBatch][2], sinv[kSvaInsBatch];
     __shared__ int shalf[kSvaInsBatch];
+    __shared__ float sS[SYM ? kSvaInsMaxSym * 9 : 1];
     const int tid = threadIdx.x, N = P.N, NX = N / 2 + 1;
+    if constexpr (SYM)
+        for (int t = tid; t < P.nsym * 9; t += 256) sS[t] = P.sym[t];
     if (tid < P.nv) {
         const double *pose = P.poses + (size_t)tid * 12;
 #pragma unroll
@@ -627,35 +639,42 @@ __global__ void __launch_bounds__(256) k_sva_insert(SvaInsP P) {
         return make_float2(v.x * sg, mate ? -v.y * sg : v.y * sg);
     };
     const size_t per = P.layout ? (size_t)P.KX * P.KY * N : (size_t)N * N * P.KX;
-    for (int v = 0; v < P.nv; v++) {
-        const float *m = sNt[v];
-        const float kx = m[0] * fqx + m[1] * fqy + m[2] * fqz, ky = m[3] * fqx + m[4] * fqy + m[5] * fqz, kz = m[6] * fqx + m[7] * fqy + m[8] * fqz;
-        if (P.use_wedge) {
-            float a = atan2f(kz, kx) * 57.29577951308232f;
-            if (a > 90.f) a -= 180.f;
-            if (a <= -90.f) a += 180.f;
-            if (!(a >= swd[v][0] && a <= swd[v][1])) continue;
+    for (int so = 0; so < (SYM ? P.nsym : 1); so++) {
+        float gx = fqx, gy = fqy, gz = fqz;
+        if constexpr (SYM) {                     // S^T q
+            const float *S = sS + so * 9;
+            gx = S[0] * fqx + S[3] * fqy + S[6] * fqz; gy = S[1] * fqx + S[4] * fqy + S[7] * fqz; gz = S[2] * fqx + S[5] * fqy + S[8] * fqz;
         }
-        const float xf = floorf(kx), yf = floorf(ky), zf = floorf(kz);
-        const int x0 = (int)xf, y0 = (int)yf, z0 = (int)zf;
-        const float fx = kx - xf, fy = ky - yf, fz = kz - zf;
-        const float2 *Tv = P.T + (size_t)v * per;
-        float sr = 0.f, si = 0.f;
+        for (int v = 0; v < P.nv; v++) {
+            const float *m = sNt[v];
+            const float kx = m[0] * gx + m[1] * gy + m[2] * gz, ky = m[3] * gx + m[4] * gy + m[5] * gz, kz = m[6] * gx + m[7] * gy + m[8] * gz;
+            if (P.use_wedge) {
+                float a = atan2f(kz, kx) * 57.29577951308232f;
+                if (a > 90.f) a -= 180.f;
+                if (a <= -90.f) a += 180.f;
+                if (!(a >= swd[v][0] && a <= swd[v][1])) continue;
+            }
+            const float xf = floorf(kx), yf = floorf(ky), zf = floorf(kz);
+            const int x0 = (int)xf, y0 = (int)yf, z0 = (int)zf;
+            const float fx = kx - xf, fy = ky - yf, fz = kz - zf;
+            const float2 *Tv = P.T + (size_t)v * per;
+            float sr = 0.f, si = 0.f;
 #pragma unroll
-        for (int dz = 0; dz < 2; dz++)
+            for (int dz = 0; dz < 2; dz++)
 #pragma unroll
-            for (int dy = 0; dy < 2; dy++)
+                for (int dy = 0; dy < 2; dy++)
 #pragma unroll
-                for (int dx = 0; dx < 2; dx++) {
-                    const float wt = (dx ? fx : 1.f - fx) * (dy ? fy : 1.f - fy) * (dz ? fz : 1.f - fz);
-                    const float2 t = fetch(Tv, x0 + dx, y0 + dy, z0 + dz);
-                    sr += wt * t.x; si += wt * t.y;
-                }
-        float rev = -(kx * ssh[v][0] + ky * ssh[v][1] + kz * ssh[v][2]) * invN;       // F(k) = Ref(N k) e^{+2 pi i k.p / N}: take the shift out
-        rev -= floorf(rev);
-        const float sn = __sinf(6.283185307179586f * rev), cs = __cosf(6.283185307179586f * rev);
-        const float s = sinv[v], vr = s * (sr * cs - si * sn), vi = s * (sr * sn + si * cs);
-        if (shalf[v]) { ar1 += vr; ai1 += vi; aw1 += 1.f; } else { ar0 += vr; ai0 += vi; aw0 += 1.f; }      // block-uniform branch
+                    for (int dx = 0; dx < 2; dx++) {
+                        const float wt = (dx ? fx : 1.f - fx) * (dy ? fy : 1.f - fy) * (dz ? fz : 1.f - fz);
+                        const float2 t = fetch(Tv, x0 + dx, y0 + dy, z0 + dz);
+                        sr += wt * t.x; si += wt * t.y;
+                    }
+            float rev = -(kx * ssh[v][0] + ky * ssh[v][1] + kz * ssh[v][2]) * invN;       // F(k) = Ref(N k) e^{+2 pi i k.p / N}: take the shift out
+            rev -= floorf(rev);
+            const float sn = __sinf(6.283185307179586f * rev), cs = __cosf(6.283185307179586f * rev);
+            const float s = sinv[v], vr = s * (sr * cs - si * sn), vi = s * (sr * sn + si * cs);
+            if (shalf[v]) { ar1 += vr; ai1 += vi; aw1 += 1.f; } else { ar0 += vr; ai0 += vi; aw0 += 1.f; }      // block-uniform branch
+        }
     }
     const size_t half_sz = tot * 3;
     if (aw0 > 0.f) { float *o = P.acc + i * 3; o[0] += ar0; o[1] += ai0; o[2] += aw0; }

@@ -101,7 +101,8 @@ def particle_from_pose(N, p):
 
 def cfg_from_xml(xml_path, box, pixel_size=1.0, mode=None):
     """ppm_sva_cfg from a 3DAVG protocol file (src/pyp/refine/3DAVG/iteration_*_mode_*.xml as patched by parse_xml,
-    src/pyp/refine/tomo_avg/sub_tomo_avg.py:318-465): image window, band-pass, missing wedge, search ranges of the mode's section."""
+    src/pyp/refine/tomo_avg/sub_tomo_avg.py:318-465): image window, band-pass, missing wedge, search ranges and the C symmetry
+    order (`<section>_use_symmetrization`; 0, 1 or absent = none) of the mode's section."""
     root = ET.parse(xml_path).getroot()
     gen = root.find("general")
     m = int(gen.find("mode").text) if mode is None else int(mode)
@@ -120,11 +121,29 @@ def cfg_from_xml(xml_path, box, pixel_size=1.0, mode=None):
     # metric/alignment_mode (iteration_002_mode_3.xml:29-38): 0 = global rotation and translation search, 1 = refinement only,
     # 2 = translation only -> ppm_sva_cfg.search_mode 1 / 0 / 2; a protocol without the field refines
     search_mode = {0: 1, 1: 0, 2: 2}.get(mval("alignment_mode", 1), 0)
+    # <section>_use_symmetrization (config tabs.sva.symmetry, "C symmetry to apply to reference for alignment (1=no symmetry)",
+    # sub_tomo_avg.py:363,383): the order n of a Cn axis along z.  The point-group operators stop at 60, so a larger order is refused
+    e = sec.find(f"{sec_name}_use_symmetrization") if sec is not None else None
+    symmetry = ""
+    if e is not None and e.text not in (None, "") and e.text.strip() != "":
+        try:
+            order = int(e.text.strip())
+        except ValueError:
+            raise ValueError(f"ERROR: {xml_path}: {sec_name}_use_symmetrization must be an integer 0..60, got '{e.text.strip()}'") from None
+        if order < 0 or order > 60:
+            raise ValueError(f"ERROR: {xml_path}: {sec_name}_use_symmetrization must be an integer 0..60, got {order}")
+        if order >= 2:
+            symmetry = "C%d" % order
     return SvaCfg.make(box, pixel_size, window=(val("image_window_x"), val("image_window_y"), val("image_window_z")),
                        window_sigma=val("image_window_sigma"), highpass=(val("high_pass_cutoff"), val("high_pass_decay")),
                        lowpass=(val("low_pass_cutoff"), val("low_pass_decay")), use_missing_wedge=wedge,
                        tol_angle=val("out_of_plane_search_range"), tol_shift=val("shifts_tolerance"),
-                       search_mode=search_mode, n_candidates=mval("number_of_candidate_peaks_to_search", 25))
+                       search_mode=search_mode, n_candidates=mval("number_of_candidate_peaks_to_search", 25), symmetry=symmetry)
+
+
+def symmetry_of(cfg):
+    """The point-group symbol of a ppm_sva_cfg as ppm_accum_create takes it ("" reads as C1)."""
+    return (cfg.symmetry or b"C1").decode()
 
 
 def band_weights(cfg, n):
@@ -276,7 +295,7 @@ class GpuBackend:
         -> (average, average of the even-index members, of the odd-index members, counts [even, odd]); None where nothing entered."""
         from . import host
         from .abi import FinalCfg
-        acc = host.Accumulator(cfg.box, 1.0, "C1", device=self.device)
+        acc = host.Accumulator(cfg.box, 1.0, symmetry_of(cfg), device=self.device)
         try:
             for lo, hi, vols, wedges, poses, index in chunks:
                 sel = np.where(members[lo:hi])[0]
