@@ -21,6 +21,16 @@ def cfg_for(n, **kw):
     return SvaCfg.make(n, **base)
 
 
+def score_floor(n, poses, vols):
+    """Bound on |GPU - oracle| of a score at a given pose: MAP_K x the float32 floor model of tests/f64_sva.py for the largest shift
+    and the largest |mean| / sigma of the sub-volumes (two-step transforms only: boxes that are multiples of 16), plus the oracle's own
+    2e-8 from float64."""
+    import f64_ref
+    import f64_sva
+    off = max(abs(float(v.mean())) / float(v.std()) for v in vols) if n % 16 == 0 else 0.0
+    return f64_ref.MAP_K * f64_sva.floor_model_sva(n, float(np.abs(poses[:, 9:]).max()), off) + 2e-8
+
+
 def test_oracle_recovers_perturbed_alignments(subtomos):
     n, vol, vols, poses, wedges, O, ref = subtomos
     start = synth.perturb_poses(poses, 3.0, 1.0)
@@ -47,11 +57,23 @@ def test_gpu_alignment_matches_oracle(n, kw):
     wedges[3] = (-40.0, 45.0)                                   # a sub-volume from a series with a narrower tilt range
     c = cfg_for(n, **kw)
     start = synth.perturb_poses(poses, 3.0, 1.0)
-    want, wsc, _ = O.sva_align(O.Reference(vol, n / 2), c, vols.numpy(), wedges, start)
+    oref = O.Reference(vol, n / 2)
+    want, wsc, _ = O.sva_align(oref, c, vols.numpy(), wedges, start)
     g = host.Reference(vol, n / 2)
     got, gsc = g.sva_align(c, vols.numpy(), wedges, start)
     assert synth.pose_angle_error(want, got).max() < 0.1 and np.abs(want[:, 9:] - got[:, 9:]).max() < 0.5, kw
     assert np.abs(wsc - gsc).max() < 2e-3
+    # no search at all (tol_angle = tol_shift = 0): the scores at the start poses, no trajectory in between - within the float32 floor
+    # of the float64 yardstick (tests/test_gpu_sva_f64.py; the oracle is within 2e-8 of float64, tests/test_f64_sva_cpu.py).  Not for
+    # a sub-volume with a limit of 45 degrees: it lies exactly on the samples kx = kz, which atan2f and atan2 may put on different sides
+    c0 = cfg_for(n, **dict(kw, tol_angle=0.0, tol_shift=0.0))
+    _, wsc0, _ = O.sva_align(oref, c0, vols.numpy(), wedges, start)
+    oref.close()
+    back, gsc0 = g.sva_align(c0, vols.numpy(), wedges, start)
+    tie = (np.abs(wedges) == 45.0).any(axis=1)
+    assert tie.sum() == 1
+    assert np.array_equal(back, start) and np.abs(wsc0 - gsc0).max() < 2e-3
+    assert np.abs(wsc0 - gsc0)[~tie].max() < score_floor(n, start, vols.numpy()), kw
     import torch
     got2, gsc2 = g.sva_align(c, vols.cuda(), wedges, start)                   # resident volumes, same bits
     assert np.array_equal(got, got2) and np.array_equal(gsc, gsc2)
@@ -252,10 +274,19 @@ def test_gpu_normalisation_through_the_transform_holds_for_a_large_density_offse
     raw = (vols.numpy() * 7.0 + 280.0).astype(np.float32)
     start = synth.perturb_poses(poses, 3.0, 1.0)
     c = cfg_for(n)
-    want, wsc, _ = O.sva_align(O.Reference(vol, n / 2), c, raw, wedges, start)
+    oref = O.Reference(vol, n / 2)
+    want, wsc, _ = O.sva_align(oref, c, raw, wedges, start)
     g = host.Reference(vol, n / 2)
     got, gsc = g.sva_align(c, raw, wedges, start)
     assert synth.pose_angle_error(want, got).max() < 0.1 and np.abs(want[:, 9:] - got[:, 9:]).max() < 0.5 and np.abs(wsc - gsc).max() < 2e-3
     ref_, rsc = g.sva_align(c, vols.numpy(), wedges, start)
     assert np.abs(rsc - gsc).max() < 5e-4 and synth.pose_angle_error(ref_, got).max() < 0.05
+    # without a search (tol_angle = tol_shift = 0) nothing but float32 rounding separates GPU and oracle: the float32 floor, with the
+    # model's term for the raw-volume transform of a sub-volume 40 sigma off zero
+    c0 = cfg_for(n, tol_angle=0.0, tol_shift=0.0)
+    _, wsc0, _ = O.sva_align(oref, c0, raw, wedges, start)
+    oref.close()
+    _, gsc0 = g.sva_align(c0, raw, wedges, start)
+    floor = score_floor(n, start, raw)
+    assert floor < 2e-3 and np.abs(wsc0 - gsc0).max() < floor, (np.abs(wsc0 - gsc0).max(), floor)
     g.close()

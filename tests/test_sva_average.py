@@ -4,6 +4,8 @@ the oracle's restatement against synthetic truth (CPU), and the HIP path (ppm_sv
 import numpy as np
 import pytest
 
+import f64_ref
+import f64_sva
 from pyp_amd import synth
 from pyp_amd.abi import FinalCfg, SvaCfg
 
@@ -107,6 +109,12 @@ def test_gpu_average_matches_oracle(n, nv, generic, monkeypatch):
     assert np.abs(gg[:, 2] - go[:, 2]).sum() <= 1e-4 * go[:, 2].sum()            # a wedge edge can flip a voxel between float and double
     ok = gg[:, 2] == go[:, 2]
     assert np.linalg.norm((gg - go)[ok, :2]) < 2e-5 * np.linalg.norm(go[:, :2])
+    # ... and shell by shell (f64_ref.compare_by_shell, the bounds of tests/test_gpu_sva_f64.py) over the voxels of equal weight: the oracle
+    # is within 2e-7 (shell) and 2e-6 (voxel) of float64 (tests/test_f64_sva_cpu.py); no density offset here, shifts as the poses have them
+    model = f64_sva.floor_model_sva(n, float(np.abs(poses[:, 9:]).max()), 0.0)
+    rep = f64_ref.compare_by_shell(np.where(ok[:, None], gg, 0).reshape(acc_o.shape), np.where(ok[:, None], go, 0).reshape(acc_o.shape), n)
+    print(f"box {n} x {nv}: {rep}; model {model:.3g}")
+    assert rep.max_shell_rel < f64_ref.SHELL_K * model + 2e-7 and rep.max_voxel_rel < f64_ref.VOXEL_K * model + 2e-6, str(rep)
     h1, h2, fl, st = acc.finalize(FinalCfg(molecular_mass_kda=0.0, inner_radius=0.0, outer_radius=0.0, mask_falloff=0.0))
     acc.close()
     for a, b in ((h1, h1o), (h2, h2o), (fl, flo)):
