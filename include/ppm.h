@@ -186,7 +186,34 @@ typedef struct ppm_csp_cfg {
     int refine_defocus;
     float defocus_range;    /* csp_ToleranceMicrographDefocus1, Angstrom */
     float defocus_step;     /* Angstrom (default 50); at most PPM_MAX_DEFOCUS_STEPS either side */
+    /* Exhaustive particle search (csp_NumberOfRandomIterations, "number of points to evaluate during reference-based exhaustive
+     * search"; particles only - tilt units and mode 4 never search exhaustively).  0 = the compass search from the start pose alone.
+     * > 0: a budget of (rotation, shift) grid points per particle.  The grid (build-defined; pyp_amd/csrc/ppm_csp_search.h, DESIGN.md
+     * section 8) covers the tolerance box about the start pose at the finest step D of {30, 24, 20, 18, 15, 12, 10, 9, 8, 7.5, 6, 5, 4, 3,
+     * 2.5, 2, 1.5, 1} degrees whose point count stays inside the budget; every point is scored on a coarse band, the best shift of
+     * each rotation is kept, the search_candidates best rotations are refined by two compass iterations each (first steps D / 2 and
+     * h_s / 2, bounds +-D / +-h_s about the candidate) and the best of them by the compass search from D / 4 and h_s / 4 down to
+     * step_tolerance.  The result may therefore leave the tolerance box, by at most one and a quarter grid steps (D degrees, h_s =
+     * mask radius x D pi / 180 pixels).  A budget too small for the 30 degree grid, even without its shifts, skips the stage
+     * (ppm_refine_note() says so).  Negative values are refused (-22). */
+    int search_points;
+    int search_candidates;  /* rotations per particle that go on to the compass passes: 0 = 8, at most 32 */
 } ppm_csp_cfg;
+
+/* The plan of the exhaustive particle search (ppm_csp_search_plan). */
+typedef struct ppm_csp_search_info {
+    int active;             /* 0: no exhaustive stage (search_points = 0, tilt units, mode 4, or a budget below the 30 degree grid) */
+    int shift_grid;         /* 0: the single shift 0 (translations off, or dropped because 30 degrees did not fit with it) */
+    double step;            /* D, degrees */
+    double r_g;             /* coarse band, Fourier pixels */
+    double h_s;             /* shift grid step the rule asks for, pixels (the grid itself spans exactly +-tol_shift) */
+    double tol_shift;       /* pixels */
+    int n_angle[3];         /* angles about the specimen x, y, z axes */
+    int full_turn[3];       /* the axis takes n_angle equally spaced angles from 0 over the full turn */
+    int n_shift_axis;       /* points per shift axis */
+    long n_rot, n_shift;    /* n_angle[0] n_angle[1] n_angle[2]; n_shift_axis^3 */
+    int n_candidates;       /* K */
+} ppm_csp_search_info;
 
 #define PPM_STATS_COLS 7 /* shell, resolution A, ring radius, FSC, part-FSC, part-SSNR, rec-SSNR
                             (src/pyp/postprocess/core.py:203-221; frealign.py:2559) */
@@ -224,8 +251,9 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
  * over all local evaluations (frequency marching makes early ones cheaper) */
 int ppm_refine_last_counts(ppm_ref_t *ref, long *n_global, long *n_local, long *samples_global,
                            long *samples_local);
-/* After ppm_csp_refine: 0, sweeps (k_csp_eval launches), in-band samples of the full band, gathered samples per projection summed over
- * the sweeps.  After ppm_sva_align: grid rotations of a global search, sweeps (k_sva_eval launches), samples of the band (half space,
+/* After ppm_csp_refine: grid points per particle of the exhaustive stage (n_rot x n_shift; 0 without one - ppm_csp_search_plan gives
+ * the factors and K), sweeps (k_csp_eval launches), in-band samples of the full band, gathered samples per projection summed over
+ * the sweeps (the exhaustive stage gathers n_rot x S(r_g) per usable row of a searched particle).  After ppm_sva_align: grid rotations of a global search, sweeps (k_sva_eval launches), samples of the band (half space,
  * before the missing wedge), band samples x gathered rotations per sub-volume summed over the sweeps. */
 /* remarks of the last ppm_refine_batch on this reference that the caller should log (e.g. the search band was capped);
  * "" if none */
@@ -248,6 +276,14 @@ int ppm_match_projections(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const doubl
  * and band_factor as in ppm_refine_batch (its search fields are ignored). */
 int ppm_csp_refine(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const ppm_csp_cfg *csp, const void *images, int images_on_device,
                    int n_proj, double *rows, double *particles, int n_part, double *tilts, int n_tilt);
+/* The plan ppm_csp_refine would follow for csp->search_points (pure host: no device, no reference needed). */
+int ppm_csp_search_plan(const ppm_refine_cfg *cfg, const ppm_csp_cfg *csp, ppm_csp_search_info *out);
+/* What the ranking stage of the last ppm_csp_refine on this reference kept for the particle with identifier `unit` (PIND): its best
+ * rotations in rank order (ties to the lower index) with the best shift of each (ties to the lower index) and that point's score on
+ * the coarse band, in SCORE units (100 x the mean correlation of the particle's usable rows).  Indices as ppm_csp_search.h
+ * enumerates them: rotation (ia n_b + ib) n_c + ic, shift (ix n + iy) n + iz.  Returns the number of entries written (<= max_k),
+ * 0 for a particle that was not searched, negative on error. */
+int ppm_csp_search_candidates(ppm_ref_t *ref, long unit, int max_k, long *rot_index, long *shift_index, double *score);
 
 /* Sub-tomogram alignment (3DAVG, `external/TOMO/MPI_Classification`, driven by src/pyp/refine/tomo_avg/sub_tomo_avg.py:318-555
  * with the XML protocols of src/pyp/refine/3DAVG/): every sub-volume is aligned to the reference by a rotation + 3-D shift that

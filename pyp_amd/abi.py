@@ -78,16 +78,27 @@ class CspCfg(C.Structure):
     _fields_ = [("unit", C.c_int), ("refine_rotation", C.c_int), ("refine_translation", C.c_int), ("tol_angle", C.c_float * 3),
                 ("tol_shift", C.c_float), ("step_tolerance", C.c_float), ("max_iterations", C.c_int), ("tind_min", C.c_int),
                 ("tind_max", C.c_int), ("first", C.c_int), ("last", C.c_int), ("refine_defocus", C.c_int),
-                ("defocus_range", C.c_float), ("defocus_step", C.c_float)]
+                ("defocus_range", C.c_float), ("defocus_step", C.c_float), ("search_points", C.c_int), ("search_candidates", C.c_int)]
 
     @classmethod
     def make(cls, unit, refine_rotation=1, refine_translation=1, tol_angle=(30.0, 30.0, 30.0), tol_shift=20.0, step_tolerance=0.01,
-             max_iterations=0, tind_min=0, tind_max=-1, first=0, last=-1, refine_defocus=0, defocus_range=750.0, defocus_step=50.0):
+             max_iterations=0, tind_min=0, tind_max=-1, first=0, last=-1, refine_defocus=0, defocus_range=750.0, defocus_step=50.0,
+             search_points=0, search_candidates=0):
+        """search_points: budget of the exhaustive particle search (csp_NumberOfRandomIterations; 0 = none), search_candidates: rotations
+        per particle that go on to the compass passes (0 = 8)."""
         return cls(unit=int(unit), refine_rotation=int(refine_rotation), refine_translation=int(refine_translation),
                    tol_angle=(C.c_float * 3)(*[float(x) for x in tol_angle]), tol_shift=float(tol_shift),
                    step_tolerance=float(step_tolerance), max_iterations=int(max_iterations), tind_min=int(tind_min),
                    tind_max=int(tind_max), first=int(first), last=int(last), refine_defocus=int(refine_defocus),
-                   defocus_range=float(defocus_range), defocus_step=float(defocus_step))
+                   defocus_range=float(defocus_range), defocus_step=float(defocus_step), search_points=int(search_points),
+                   search_candidates=int(search_candidates))
+
+
+class CspSearchInfo(C.Structure):
+    """ppm_csp_search_info (include/ppm.h)."""
+    _fields_ = [("active", C.c_int), ("shift_grid", C.c_int), ("step", C.c_double), ("r_g", C.c_double), ("h_s", C.c_double),
+                ("tol_shift", C.c_double), ("n_angle", C.c_int * 3), ("full_turn", C.c_int * 3), ("n_shift_axis", C.c_int),
+                ("n_rot", C.c_long), ("n_shift", C.c_long), ("n_candidates", C.c_int)]
 
 
 class SvaCfg(C.Structure):

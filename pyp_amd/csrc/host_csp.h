@@ -53,6 +53,7 @@ struct CspRun {
     Geom gm; SampleList sl; int S_pad = 0, nrings = 0; double rm_px = 0;
     int kind = 0, n_proj = 0, n_part = 0, n_tilt = 0;
     CspEvalP EP; bool tab = false;
+    const double *particles_in = nullptr;           // the caller's particle block (identifiers of the searched particles)
     std::vector<double> hN, hp, htl;                // the units as the device holds them
     double acct_gathers = 0; long acct_sweeps = 0;  // for the roofline (ppm_refine_last_counts)
     double bf() const { return cfg->band_factor == 0 ? 3.0 : cfg->band_factor; }
@@ -310,6 +311,128 @@ static int csp_compass(CspRun &c, CspUnits &U, const CspSearch &P, int ncand_max
     return 0;
 }
 
+// ---- exhaustive particle search (ppm_csp_cfg.search_points; the plan: ppm_csp_search.h)
+constexpr size_t kCspSearchTableBytes = (size_t)256 << 20;      // per-rotation maxima of one particle chunk (score + shift index = 8 bytes per rotation)
+constexpr int kCspSearchRotsPerLaunch = 1 << 16;                // rotations one k_csp_global launch takes (PPM_CSP_SEARCH_ROTS lowers it)
+
+// Stage 1: every grid point of every active particle scored on the coarse band (k_csp_global), the K best rotations of each with their
+// best shifts (k_csp_global_topk) -> the handle's candidate tables, [active unit][K]
+static int csp_global_rank(CspRun &c, const CspUnits &U, const ppm_csp_search_info &G) {
+    ppm_ref *ref = c.ref; const Geom &gm = c.gm;
+    const int na = (int)U.active.size(), K = G.n_candidates;
+    const size_t n_eval = U.eval_rows.size();
+    std::vector<double> rowtab(n_eval * kCspRowTab);
+    for (size_t e = 0; e < n_eval; e++) {
+        const int j = U.eval_rows[e], it = U.row_tilt[j];
+        const TiltRot &r = U.trot[it]; const CUnit &tu = U.tls[it];
+        double *t = &rowtab[e * kCspRowTab], A[9];
+        mat_mul3(r.a, r.b, t); mat_mul3(r.ai, r.bi, A);
+        std::memcpy(t + 9, A, 6 * sizeof(double));
+        t[15] = U.s0[2 * j] - U.g0[2 * j] + tu.tl[2]; t[16] = U.s0[2 * j + 1] - U.g0[2 * j + 1] + tu.tl[3];
+    }
+    if (int rc = ref->c_rowtab.ensure(rowtab.size())) return rc;
+    if (int rc = ref->c_active.ensure((size_t)na)) return rc;
+    HIPCHK(hipMemcpyAsync(ref->c_rowtab.p, rowtab.data(), rowtab.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->c_active.p, U.active.data(), (size_t)na * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->c_eval.p, U.eval_rows.data(), n_eval * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    const size_t n_rot = (size_t)G.n_rot;
+    const int chunk = (int)std::min<size_t>(std::min<size_t>((size_t)na, 65535), std::max<size_t>(1, kCspSearchTableBytes / (n_rot * 8)));
+    if (int rc = ref->c_gbest.ensure((size_t)chunk * n_rot)) return rc;
+    if (int rc = ref->c_gshift.ensure((size_t)chunk * n_rot)) return rc;
+    if (int rc = ref->c_crot.ensure((size_t)na * K)) return rc;
+    if (int rc = ref->c_cshift.ensure((size_t)na * K)) return rc;
+    if (int rc = ref->c_cscore.ensure((size_t)na * K)) return rc;
+    long cap = kCspSearchRotsPerLaunch;
+    if (const char *e = std::getenv("PPM_CSP_SEARCH_ROTS")) { long v = std::atol(e); if (v > 0) cap = std::min(cap, v); }   // tests: force several launches
+    CspGlobalP GP;
+    GP.cv = c.EP.cv; GP.samples = ref->samples.p; GP.Il = ref->c_Il.p; GP.cw = ref->c_cw.p; GP.S_pad = c.S_pad; GP.N = gm.N;
+    GP.rlo2 = c.EP.rlo2; GP.ring_signed = c.EP.ring_signed; GP.S_used = c.prefix_of(G.r_g); GP.rmax2 = (float)(G.r_g * G.r_g);
+    GP.eval_rows = ref->c_eval.p; GP.uoff = ref->c_uoff.p; GP.active = ref->c_active.p; GP.Nmat = ref->c_N.p; GP.pshift = ref->c_p.p;
+    GP.rowtab = ref->c_rowtab.p; GP.G = G; GP.best = ref->c_gbest.p; GP.best_shift = ref->c_gshift.p;
+    GP.edge_ring = (int)std::floor(G.r_g); GP.max_rows = 1;
+    for (int u : U.active) { int n = 0; for (int j : U.urows[u]) n += U.usable[j] ? 1 : 0; GP.max_rows = std::max(GP.max_rows, n); }
+    const size_t lds = csp_global_lds_bytes(GP.S_used, GP.max_rows);
+    if (lds + 256 > (size_t)64 * 1024) return fail(-22, "csp: the coarse band of the exhaustive search does not fit the LDS");
+    for (int a0 = 0; a0 < na; a0 += chunk) {
+        const int npc = std::min(chunk, na - a0);
+        GP.a0 = a0;
+        for (long r0 = 0; r0 < G.n_rot; r0 += cap) {
+            GP.rot0 = r0; GP.nrot = (int)std::min<long>(cap, G.n_rot - r0);
+            GP.rc = (int)std::min<long>(64, std::max<long>(1, (long)GP.nrot * npc / 8192));
+            ProfScope ps(PPM_K_GLOBAL);
+            hipLaunchKernelGGL(k_csp_global, dim3((unsigned)((GP.nrot + GP.rc - 1) / GP.rc), (unsigned)npc), dim3(64), lds, cur_stream(), GP);
+        }
+        hipLaunchKernelGGL(k_csp_global_topk, dim3((unsigned)npc), dim3(256), 0, cur_stream(), ref->c_gbest.p, ref->c_gshift.p, (long)G.n_rot, K,
+                           ref->c_crot.p + (size_t)a0 * K, ref->c_cshift.p + (size_t)a0 * K, ref->c_cscore.p + (size_t)a0 * K);
+        HIPCHK(hipGetLastError());
+    }
+    const long passes = (G.n_shift + 64 * kCspGlobalShifts - 1) / (64 * kCspGlobalShifts);
+    c.acct_gathers += (double)n_eval * (double)G.n_rot * GP.S_used * (double)passes;
+    ref->cand_K = K;
+    ref->cand_unit.resize(na); ref->cand_rot.resize((size_t)na * K); ref->cand_shift.resize((size_t)na * K); ref->cand_score.resize((size_t)na * K);
+    HIPCHK(hipMemcpyAsync(ref->cand_rot.data(), ref->c_crot.p, (size_t)na * K * sizeof(long), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->cand_shift.data(), ref->c_cshift.p, (size_t)na * K * sizeof(int), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->cand_score.data(), ref->c_cscore.p, (size_t)na * K * sizeof(float), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipStreamSynchronize(cur_stream()));
+    return 0;
+}
+
+// mean score of every active unit at its current state on the band `rband` (zero displacement) -> hmean[active unit]
+static int csp_unit_scores(CspRun &c, const CspUnits &U, int ncand_max, double rband, std::vector<double> &hmean) {
+    ppm_ref *ref = c.ref; CspEvalP &EP = c.EP; const int na = (int)U.active.size();
+    HIPCHK(hipMemsetAsync(ref->c_delta.p, 0, (size_t)std::max(U.n_slots, 1) * ncand_max * 6 * sizeof(double), cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->c_eval.p, U.eval_rows.data(), U.eval_rows.size() * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    EP.delta = ref->c_delta.p; EP.ncand = 1; EP.S_used = c.prefix_of(rband); EP.rmax2 = (float)(rband * rband);
+    c.acct_gathers += (double)U.eval_rows.size() * EP.S_used; c.acct_sweeps++;
+    launch_csp_eval(c, U.eval_rows.size());
+    hipLaunchKernelGGL(k_csp_unit_means, dim3((na + 255) / 256), dim3(256), 0, cur_stream(), ref->c_out.p, ref->c_uoff.p, na, 1, ref->c_mean.p);
+    HIPCHK(hipGetLastError());
+    hmean.resize(na);
+    HIPCHK(hipMemcpyAsync(hmean.data(), ref->c_mean.p, (size_t)na * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipStreamSynchronize(cur_stream()));
+    return 0;
+}
+
+// The exhaustive search of the active particles: stage 1 ranks the grid; stage 2 gives the k-th candidate of every particle two compass
+// iterations (first steps D / 2 and h_s / 2, bounds +-D / +-h_s about the candidate) and scores it at the band that pass ended on, the
+// best pass of a particle wins (ties to the lower k); stage 3 is the compass search of the winners from D / 4 and h_s / 4 down to the
+// step tolerance, bounded by +-D / 2 and +-h_s / 2.  csp_compass serves both as it is.
+static int csp_exhaustive(CspRun &c, CspUnits &U, const CspSearch &P, const ppm_csp_search_info &G, int ncand_max) {
+    const ppm_csp_cfg *cc = c.cc; const Geom &gm = c.gm;
+    if (int rc = csp_global_rank(c, U, G)) return rc;
+    ppm_ref *ref = c.ref;
+    const int na = (int)U.active.size(), K = G.n_candidates;
+    for (int a = 0; a < na; a++) ref->cand_unit[a] = (long)c.particles_in[(size_t)U.active[a] * PPM_NPCOL];
+    const double hs_grid = G.shift_grid ? G.h_s : cc->tol_shift;
+    const bool any_ang = P.en[0] || P.en[1] || P.en[2], any_sh = P.en[3] || P.en[4] || P.en[5];
+    CspSearch P2 = P;
+    for (int k = 0; k < 3; k++) { P2.tol[k] = G.step; P2.tol[3 + k] = hs_grid; }
+    P2.ha0 = any_ang ? 0.5 * G.step : 0; P2.hs0 = any_sh ? 0.5 * hs_grid : 0; P2.T = 2;
+    const double band2 = march_band(c.bf(), gm.N, c.rm_px, 0.5 * P2.ha0, 0.5 * P2.hs0, any_ang, any_sh, gm.r_hi);      // of the second iteration
+    const std::vector<CUnit> start = U.parts;
+    std::vector<CUnit> win(na); std::vector<double> fbest(na, -1e300), hmean;
+    for (int k = 0; k < K; k++) {
+        for (int a = 0; a < na; a++) {
+            CUnit q = start[U.active[a]];
+            const long rot = ref->cand_rot[(size_t)a * K + k];
+            if (rot >= 0) { double d[6]; csp_search_delta(G, rot, ref->cand_shift[(size_t)a * K + k], d); unit_apply_delta(q.N, q.p, d); }
+            U.parts[U.active[a]] = q;
+        }
+        if (int rc = csp_upload_units(c, U)) return rc;
+        if (int rc = csp_compass(c, U, P2, ncand_max)) return rc;
+        if (int rc = csp_unit_scores(c, U, ncand_max, band2, hmean)) return rc;
+        for (int a = 0; a < na; a++) if (hmean[a] > fbest[a]) { fbest[a] = hmean[a]; win[a] = U.parts[U.active[a]]; }
+    }
+    for (int a = 0; a < na; a++) U.parts[U.active[a]] = win[a];
+    if (int rc = csp_upload_units(c, U)) return rc;
+    CspSearch P3 = P;
+    for (int k = 0; k < 3; k++) { P3.tol[k] = 0.5 * G.step; P3.tol[3 + k] = 0.5 * hs_grid; }
+    P3.ha0 = 0.5 * P2.ha0; P3.hs0 = 0.5 * P2.hs0;
+    const double steptol = cc->step_tolerance > 0 ? cc->step_tolerance : 0.01;
+    P3.T = cc->max_iterations > 0 ? cc->max_iterations : compass_iterations(P3.ha0, P3.hs0, steptol, 1);
+    return csp_compass(c, U, P3, ncand_max);
+}
+
 // scores of every row of the refined units at the full band, at the units' current state (zero displacement) -> hout[final row]
 static int csp_final_scores(CspRun &c, const CspUnits &U, std::vector<double> &hout) {
     ppm_ref *ref = c.ref; const Geom &gm = c.gm; CspEvalP &EP = c.EP;
@@ -362,9 +485,11 @@ extern "C" int ppm_csp_refine(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const p
     if (!ref || !cfg || !cc || !images || !rows || !particles || !tilts) return fail(-22, "null argument");
     StreamScope ss_(ref->stream, ref->copy);
     if (cc->unit != PPM_CSP_PARTICLES && cc->unit != PPM_CSP_MICROGRAPHS) return fail(-22, "csp: unit must be particles (1) or micrographs (2)");
+    if (cc->search_points < 0 || cc->search_candidates < 0) return fail(-22, "csp: search_points and search_candidates must not be negative");
     if (n_proj <= 0) return 0;
     if (n_part <= 0 || n_tilt <= 0) return fail(-22, "csp: the extended parameters hold no particles or no tilts");
-    CspRun c; c.ref = ref; c.cfg = cfg; c.cc = cc; c.kind = cc->unit; c.n_proj = n_proj; c.n_part = n_part; c.n_tilt = n_tilt;
+    ref->cand_K = 0; ref->cand_unit.clear();       // ppm_csp_search_candidates answers from the last call
+    CspRun c; c.particles_in = particles; c.ref = ref; c.cfg = cfg; c.cc = cc; c.kind = cc->unit; c.n_proj = n_proj; c.n_part = n_part; c.n_tilt = n_tilt;
     const Geom &gm = c.gm;
     ppm_refine_cfg c2 = *cfg; c2.global_search = 0;
     std::string err;
@@ -387,7 +512,22 @@ extern "C" int ppm_csp_refine(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const p
     const int ncand_max = 1 + 2 * P.nfree;
     if (int rc = csp_upload_tables(c, U, ncand_max)) return rc;
     trace_.mark("spectra prepared, units uploaded");
-    if (P.T > 0) if (int rc = csp_compass(c, U, P, ncand_max)) return rc;
+    // the exhaustive stage: particles only, and only where the compass search itself has something to do
+    ppm_csp_search_info G = csp_search_from_cfg(*cfg, *cc, gm);
+    if (cc->search_points > 0 && c.kind == PPM_CSP_PARTICLES && P.T > 0) {
+        char b[320];
+        if (G.active)
+            std::snprintf(b, sizeof(b), "csp: exhaustive search of %ld x %ld grid points per particle (step %g degrees, band %.2f Fourier pixels, %d x %d x %d "
+                          "rotations x %d^3 shifts within a budget of %d), %d candidates each refined", G.n_rot, G.n_shift, G.step, G.r_g, G.n_angle[0], G.n_angle[1],
+                          G.n_angle[2], G.n_shift_axis, cc->search_points, G.n_candidates);
+        else
+            std::snprintf(b, sizeof(b), "csp: search_points = %d is below the %ld rotations of the 30 degree grid: no exhaustive search, the compass search "
+                          "starts from the given poses", cc->search_points, G.n_rot);
+        ref->note = b;
+    }
+    if (P.T <= 0) G.active = 0;
+    if (G.active) { if (int rc = csp_exhaustive(c, U, P, G, ncand_max)) return rc; }
+    else if (P.T > 0) if (int rc = csp_compass(c, U, P, ncand_max)) return rc;
     trace_.mark("searched");
     std::vector<double> hout;
     if (int rc = csp_final_scores(c, U, hout)) return rc;
@@ -395,7 +535,34 @@ extern "C" int ppm_csp_refine(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const p
     csp_write_back(c, U, hout, rows, particles, tilts);
     // ppm_refine_last_counts after a constrained refinement: 0, sweeps (k_csp_eval launches), in-band samples of the full band, gathered
     // samples per projection summed over the sweeps
-    ref->last_counts[0] = 0; ref->last_counts[1] = c.acct_sweeps; ref->last_counts[2] = (long)std::floor(kPi * gm.r_hi * gm.r_hi / 2);
+    ref->last_counts[0] = G.active ? G.n_rot * G.n_shift : 0; ref->last_counts[1] = c.acct_sweeps; ref->last_counts[2] = (long)std::floor(kPi * gm.r_hi * gm.r_hi / 2);
     ref->last_counts[3] = (long)(c.acct_gathers / std::max(n_proj, 1));
     return 0;
 }
+
+extern "C" int ppm_csp_search_plan(const ppm_refine_cfg *cfg, const ppm_csp_cfg *cc, ppm_csp_search_info *out) {
+    if (!cfg || !cc || !out) return fail(-22, "null argument");
+    if (cc->search_points < 0 || cc->search_candidates < 0) return fail(-22, "csp: search_points and search_candidates must not be negative");
+    Geom gm; ppm_refine_cfg c2 = *cfg; c2.global_search = 0;
+    std::string err;
+    if (!geom_init(gm, c2, err)) return fail(-22, err);
+    *out = csp_search_from_cfg(*cfg, *cc, gm);
+    return 0;
+}
+
+extern "C" int ppm_csp_search_candidates(ppm_ref_t *ref, long unit, int max_k, long *rot_index, long *shift_index, double *score) {
+    if (!ref || max_k < 0 || (max_k > 0 && (!rot_index || !shift_index || !score))) return fail(-22, "null argument");
+    for (size_t a = 0; a < ref->cand_unit.size(); a++) {
+        if (ref->cand_unit[a] != unit) continue;
+        const int K = std::min(max_k, ref->cand_K);
+        int n = 0;
+        for (int k = 0; k < K; k++) {
+            const size_t o = a * ref->cand_K + k;
+            if (ref->cand_rot[o] < 0) break;
+            rot_index[n] = ref->cand_rot[o]; shift_index[n] = ref->cand_shift[o]; score[n] = 100.0 * (double)ref->cand_score[o]; n++;
+        }
+        return n;
+    }
+    return 0;
+}
+

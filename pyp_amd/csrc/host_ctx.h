@@ -179,6 +179,10 @@ struct ppm_ref {
     // constrained search (ppm_csp_refine)
     DevBuf<float2> c_Il, c_band; DevBuf<float> c_cw, c_img, c_wring; DevBuf<double> c_rows, c_N, c_p, c_tl, c_delta, c_s0, c_g0, c_out;
     DevBuf<int> c_eval, c_rp, c_rt, c_slot, c_uoff, c_active; DevBuf<LState> c_states; DevBuf<double> c_mean, c_tmean, c_acc, c_dtrial, c_fpm, c_delta_t;
+    // ... its exhaustive stage (k_csp_global): per-row tables, per-rotation maxima of a particle chunk, the kept candidates; and what
+    // ppm_csp_search_candidates answers from (the last call's candidates: PIND of every searched particle, K entries each)
+    DevBuf<double> c_rowtab; DevBuf<float> c_gbest, c_cscore; DevBuf<int> c_gshift, c_cshift; DevBuf<long> c_crot;
+    std::vector<long> cand_unit, cand_rot; std::vector<int> cand_shift; std::vector<float> cand_score; int cand_K = 0;
     // sub-tomogram alignment (ppm_sva_align): the transforms' work array, the band-limited transforms of a chunk, staged host volumes
     // (GBs: allocating and freeing them on every call cost ~20 ms of a 120 ms call)
     DevBuf<float2> s_f, s_g, s_F; DevBuf<float> s_vols;

@@ -84,7 +84,21 @@ def _settings(p):
         tol_m_rot=(float(p.get("csp_ToleranceMicrographTiltAngles", 1.5)), float(p.get("csp_ToleranceMicrographTiltAxisAngles", 1.0)), 0.0),
         tol_m_shift=float(p.get("csp_ToleranceMicrographShifts", 100.0)), tol_defocus=float(p.get("csp_ToleranceMicrographDefocus1", 750.0)),
         normalize=int(bool(p.get("reconstruct_norm", True))), invert=int(bool(p.get("refine_invert", False))),
-        data_set=str(p.get("data_set", "")), running_frames=int(p.get("csp_running_average_frames", 2)))
+        data_set=str(p.get("data_set", "")), running_frames=int(p.get("csp_running_average_frames", 2)),
+        # "Optimizer exhaustive search points" (config/pyp_config.toml:6281-6288), set per step by the caller; csp_GridSearch is accepted
+        # either way: this build always searches a grid
+        search_points=int(schedule(p.get("csp_NumberOfRandomIterations", 0), it)), grid_search=bool(p.get("csp_GridSearch", True)))
+
+
+def make_csp_cfg(s, mode, first, last, px):
+    """CspCfg of refinement mode 0 .. 6 (7 / 8 already mapped to 2 / 1) from the settings; px = pixel size of the rows, Angstrom."""
+    unit = CSP_PARTICLES if mode in (1, 2, 5) else CSP_MICROGRAPHS
+    rot, trans = mode in (0, 1, 5, 6), mode in (2, 3, 5, 6)
+    return CspCfg.make(unit, refine_rotation=rot, refine_translation=trans, refine_defocus=int(mode == 4), defocus_range=s["tol_defocus"],
+                       tol_angle=s["tol_p_rot"] if unit == CSP_PARTICLES else s["tol_m_rot"],
+                       tol_shift=(s["tol_p_shift"] if unit == CSP_PARTICLES else s["tol_m_shift"]) / px,        # the tolerances are in Angstrom
+                       step_tolerance=s["step_tol"], tind_min=s["tind_min"], tind_max=s["tind_max"], first=first, last=last,
+                       search_points=s["search_points"] if unit == CSP_PARTICLES else 0)       # the particle modes 1 / 2 / 5 (7 / 8); others ignore the key
 
 
 def _out_names(param_file, first, last):
@@ -158,7 +172,6 @@ def csp_main(argv=None):
     if mode not in (0, 1, 2, 3, 4, 5, 6):
         _die(f"ERROR: csp: unknown mode {mode}")
     unit = CSP_PARTICLES if mode in (1, 2, 5) else CSP_MICROGRAPHS
-    rot, trans = mode in (0, 1, 5, 6), mode in (2, 3, 5, 6)
     key = C["PIND"] if unit == CSP_PARTICLES else C["TIND"]
     hi = last if last >= 0 else np.inf
     sel = np.where((rows[:, key] >= first) & (rows[:, key] <= hi))[0]
@@ -183,16 +196,17 @@ def csp_main(argv=None):
     px = float(rin[0, C["PIXEL_SIZE"]]) if rin[0, C["PIXEL_SIZE"]] > 0 else s["pixel"]
     cfg = RefineCfg.make(box=box, pixel_size=px, molecular_mass_kda=s["mw"], mask_radius=s["radius"], res_low=s["res_low"], res_high=s["res_high"],
                          res_signed_cc=s["res_signed"], global_search=0, local_refine=1, normalize=s["normalize"], invert=s["invert"])
-    cc = CspCfg.make(unit, refine_rotation=rot, refine_translation=trans, refine_defocus=int(mode == 4), defocus_range=s["tol_defocus"],
-                     tol_angle=s["tol_p_rot"] if unit == CSP_PARTICLES else s["tol_m_rot"],
-                     tol_shift=(s["tol_p_shift"] if unit == CSP_PARTICLES else s["tol_m_shift"]) / px,        # the tolerances are in Angstrom
-                     step_tolerance=s["step_tol"], tind_min=s["tind_min"], tind_max=s["tind_max"], first=first, last=last)
+    cc = make_csp_cfg(s, mode, first, last, px)
+    if cc.search_points < 0:
+        _die(f"ERROR: csp: csp_NumberOfRandomIterations = {cc.search_points} must not be negative")
     from .. import host, lib
     dev = int(os.environ.get("PPM_DEVICE", "0"))
     try:
         with gpu_lock(dev):
             ref = host.Reference(vol, box / 2, device=dev)
             rout, pout, tout = ref.csp_refine(cfg, cc, imgs, rin, particles, tilts)
+            if cc.search_points > 0 and ref.note():
+                print(ref.note())
             ref.close()
     except (lib.PpmError, ValueError) as e:
         _die(str(e))

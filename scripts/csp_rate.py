@@ -5,6 +5,11 @@ import numpy as np, torch
 from pyp_amd import host, synth
 from pyp_amd.abi import RefineCfg, CspCfg, CSP_PARTICLES, CSP_MICROGRAPHS
 
+search_points = 0
+if "--search-points" in sys.argv:          # budget of the exhaustive particle search (CspCfg.search_points); 0 = the compass search alone
+    i = sys.argv.index("--search-points")
+    search_points = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 npart = int(sys.argv[2]) if len(sys.argv) > 2 else 300
 px = 2.0
@@ -22,7 +27,7 @@ for i in range(len(p2)):
 rows2 = synth.csp_rows_from_params(rows, parts, tilts, p2, tilts)
 cfg = RefineCfg.make(box=n, pixel_size=px, mask_radius=0.32 * n * px, res_high=px * n / (0.25 * n), res_signed_cc=30.0, global_search=0)
 ref = host.Reference(vol, n / 2)
-cc = CspCfg.make(CSP_PARTICLES, tol_angle=(8, 8, 8), tol_shift=4.0)
+cc = CspCfg.make(CSP_PARTICLES, tol_angle=(8, 8, 8), tol_shift=4.0, search_points=search_points)
 ref.csp_refine(cfg, cc, stack[:41 * 4], rows2[:41 * 4], p2, tilts)
 host.profile(True, True)
 t0 = time.time()
@@ -35,6 +40,18 @@ print("box %d, %d particles x 41 tilts = %d projections: particle mode %.2f s = 
       % (n, npart, len(rows), dt, npart / dt, len(rows) / dt, prof["prep"]["ms"], prof["local"]["ms"]))
 print("particle angle error %.2f -> %.2f deg (median), shift %.2f -> %.2f px" % (np.median(perr(p2, parts)), np.median(perr(p3, parts)),
       np.median(np.linalg.norm(p2[:, 1:4] - parts[:, 1:4], axis=1)), np.median(np.linalg.norm(p3[:, 1:4] - parts[:, 1:4], axis=1))))
+if search_points:
+    from pyp_amd import csp_search
+    pl, cnt = csp_search.plan(cfg, cc), ref.last_counts()
+    c0 = CspCfg.make(CSP_PARTICLES, tol_angle=(8, 8, 8), tol_shift=4.0)
+    t0 = time.time()
+    ref.csp_refine(cfg, c0, stack, rows2, p2, tilts)
+    dt0 = time.time() - t0
+    evals = float(pl["n_rot"]) * pl["n_shift"] * len(rows)
+    print("exhaustive search: step %g deg, band %.2f px, %d rotations x %d shifts, %d candidates; kernel %.1f ms = %.3g (point, row) evaluations/s; "
+          "the same call without it %.2f s (the stage and its compass passes are %.0f%% of the call); gathered samples per projection %d"
+          % (pl["step"], pl["r_g"], pl["n_rot"], pl["n_shift"], pl["n_candidates"], prof["global"]["ms"], evals / max(prof["global"]["ms"] * 1e-3, 1e-9),
+             dt0, 100.0 * max(dt - dt0, 0.0) / dt, cnt["samples_local"]))
 cm = CspCfg.make(CSP_MICROGRAPHS, tol_angle=(1.5, 1.0, 0), tol_shift=4.0)
 t0 = time.time()
 ref.csp_refine(cfg, cm, stack, r3, p3, t3)
