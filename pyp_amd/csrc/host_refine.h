@@ -182,6 +182,7 @@ struct RefineRun {
     bool focus_on = false, sep_search = false; float focus_px[4] = { 0, 0, 0, 0 };
     // grid search: the window's path and, for k_global, its tiles
     GfftPlan gpl; bool use_fft = false;
+    RowPlan rows = {};                                              // row order of k_global's bank (ppm_rows.h); HsP = rows.HsP
     int Rtx = 0, Rty = 0, Rwin = 0, HsP = 0, nslices = 0; std::vector<int> cxs, cys;
     // ... and the sections of the grid (ppm_sections.h) with the offsets of their hit lists: section s keeps kpre[s + 1] - kpre[s] hits
     std::vector<GridSection> secs; std::vector<int> kpre; int sec_dirs = 0;     // sec_dirs: directions of the largest section
@@ -304,8 +305,10 @@ static int refine_plan(RefineRun &r, int n_img) {
     };
     r.cxs = tile_centres(gm.RSx, r.Rtx); r.cys = tile_centres(gm.RSy, r.Rty);
     r.Rwin = std::max(r.Rtx, r.Rty);
-    // bank rows per slice in the paired order of k_global: row 0 = ky 0, row 1 = empty, rows 2t / 2t+1 = ky +t / -t
-    r.HsP = ((2 * (gm.Bs + 1) + 2 * global_unroll(r.Rwin) - 1) / (2 * global_unroll(r.Rwin))) * (2 * global_unroll(r.Rwin));   // k_global walks 2 U rows per trip
+    // bank rows per slice in the order k_global consumes them (ppm_rows.h): steps of four rows, two steps per trip
+    static_assert(global_unroll(1) == 4 && global_unroll(PPM_MAX_SHIFT_STEPS) == 4, "row_plan lays the bank out in steps of U = 4 rows");
+    r.rows = row_plan(gm.Ns, gm.Bs, global_fold(gm.Bs));
+    r.HsP = r.rows.HsP;
     r.nslices = gm.n_dir * gm.npsi_store;
     if (cfg->global_search) if (int rc = plan_grid_sections(r)) return rc;
     // chunk so that the scratch stays well inside HBM
@@ -357,7 +360,7 @@ static int ensure_bank(RefineRun &r, const GridSection &sec) {
     const std::string key = ref->grid_key + "/d" + std::to_string(sec.d0) + "+" + std::to_string(sec.nd);
     if (ref->bank_key == key) return 0;
     const int nsl = sec.nd * gm.npsi_store;
-    BankP BP; BP.cv = r.cv; BP.mats = ref->mats.p + (size_t)sec.d0 * gm.npsi_store * 6; BP.bank = ref->bank.p; BP.nslices = nsl; BP.Bs = gm.Bs; BP.Hs = r.HsP;
+    BankP BP; BP.cv = r.cv; BP.mats = ref->mats.p + (size_t)sec.d0 * gm.npsi_store * 6; BP.bank = ref->bank.p; BP.nslices = nsl; BP.Bs = gm.Bs; BP.Hs = r.HsP; BP.rows = r.rows;
     BP.r_s2 = (float)(gm.r_s * gm.r_s);
     {
         ProfScope ps(PPM_K_BANK);
@@ -434,8 +437,9 @@ static int ensure_search_tables(RefineRun &r) {
     // row twiddles of the shift window (scalar loads in k_global)
     {
         std::vector<float4> rt((size_t)kRowTwRows * PPM_MAX_SHIFT_STEPS, make_float4(1.f, 1.f, 0.f, 0.f));
-        for (int tp = 0; tp <= gm.Bs && tp < kRowTwRows; tp++) for (int j = 1; j <= PPM_MAX_SHIFT_STEPS; j++) {
-            int t = ((tp * j) % gm.Ns + gm.Ns) % gm.Ns;
+        // one entry per pair slot (stored row / 2) of the bank's row order; a quad's step reads its first slot
+        for (int tp = 0; 2 * tp < HsP && tp < kRowTwRows; tp++) for (int j = 1; j <= PPM_MAX_SHIFT_STEPS; j++) {
+            int t = ((row_slot_t(r.rows, tp) * j) % gm.Ns + gm.Ns) % gm.Ns;
             const float c = (float)std::cos(2.0 * kPi * t / gm.Ns), sn = (float)std::sin(2.0 * kPi * t / gm.Ns);
             rt[(size_t)tp * PPM_MAX_SHIFT_STEPS + j - 1] = make_float4(c, c, sn, sn);
         }
@@ -549,12 +553,12 @@ static int search_section(RefineRun &r, int nb, const GridSection &sec, Hit *hit
     GlobP GP;
     GP.bank = ref->bank.p; GP.Wp = ref->Wp.p; GP.nP = ref->nP.p + sl0; GP.nI = ref->nI.p; GP.twN = ref->twN.p; GP.rowtw = ref->rowtw.p;
     GP.cc = ref->cc.p + o0; GP.sh = ref->sh.p + o0; GP.hits = hits;
-    GP.Bs = gm.Bs; GP.Hs = gm.Hs; GP.HsP = HsP; GP.Ns = gm.Ns; GP.RSx = r.Rtx; GP.RSy = r.Rty;
+    GP.Bs = gm.Bs; GP.Hs = gm.Hs; GP.HsP = HsP; GP.rows = r.rows; GP.Ns = gm.Ns; GP.RSx = r.Rtx; GP.RSy = r.Rty;
     GP.n_dir = sec.nd; GP.n_psi = gm.n_psi; GP.npsi_store = gm.npsi_store; GP.n_orient = sec.nd * gm.n_psi; GP.K = K;
     GP.nP_ld = r.nslices; GP.o_ld = gm.n_orient; GP.o_base = o0;
     {
         ProfScope ps(PPM_K_NORMS);
-        NormP NP; NP.C2 = ref->C2.p; NP.bank = ref->bank.p; NP.nP = ref->nP.p + sl0; NP.n = nb; NP.nslices = nsl; NP.ldn = r.nslices; NP.Bs = gm.Bs; NP.Hs = gm.Hs; NP.HsP = HsP;
+        NormP NP; NP.C2 = ref->C2.p; NP.bank = ref->bank.p; NP.nP = ref->nP.p + sl0; NP.n = nb; NP.nslices = nsl; NP.ldn = r.nslices; NP.Bs = gm.Bs; NP.Hs = gm.Hs; NP.HsP = HsP; NP.rows = r.rows;
         hipLaunchKernelGGL(k_slice_norms, dim3((nb + 127) / 128, (nsl + 127) / 128), dim3(256), 0, cur_stream(), NP);
     }
     if (r.use_fft) {

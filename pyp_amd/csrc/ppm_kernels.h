@@ -13,6 +13,7 @@
 #pragma once
 #include "ppm_dev.h"
 #include "ppm_geom.h"
+#include "ppm_rows.h"
 
 namespace ppm {
 
@@ -552,18 +553,18 @@ __global__ void __launch_bounds__(PT, MINW) k_prep(PrepP P) {
 }
 
 // ---------------------------------------------------------------------------------- slice bank
-struct BankP { CubeView cv; const float *mats; float2 *bank; int nslices, Bs, Hs; float r_s2; };
+struct BankP { CubeView cv; const float *mats; float2 *bank; int nslices, Bs, Hs; float r_s2; RowPlan rows; };      // Hs: stored rows (rows.HsP)
 
 __global__ void __launch_bounds__(256) k_bank(BankP P) {
     size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, per = (size_t)P.Hs * 64;
     if (i >= per * P.nslices) return;
     int sl = (int)(i / per), r = (int)(i - (size_t)sl * per);
-    // rows are stored in the paired order of k_global: row 0 = ky 0, row 1 = empty, row 2t = +t, row 2t+1 = -t
-    int kx = r & 63, rr = r >> 6, t = rr >> 1;
-    int ky = (rr & 1) ? -t : t;
+    // rows are stored in the order k_global consumes them (row_plan, ppm_rows.h)
+    int kx = r & 63, rr = r >> 6, ky = 0;
+    const bool ok = row_ky(P.rows, rr, ky);
     float k2 = (float)(kx * kx + ky * ky);
     float2 v = make_float2(0.f, 0.f);
-    if (rr != 1 && t <= P.Bs && kx <= P.Bs && k2 < P.r_s2) {
+    if (ok && kx <= P.Bs && k2 < P.r_s2) {
         const float *m = P.mats + (size_t)sl * 6;
         float fx = (float)kx, fy = (float)ky;
         v = sample_cube(P.cv, m[0] * fx + m[1] * fy, m[2] * fx + m[3] * fy, m[4] * fx + m[5] * fy);
@@ -580,7 +581,7 @@ __global__ void __launch_bounds__(256) k_bank(BankP P) {
 // operand reads (lane = row, two k per instruction) then touch 32 distinct banks.
 // bank, nslices: the slices of one section of the grid (host_refine.h); nP points at the section's first column of the whole
 // [n][ldn] table (ldn = slices of the whole grid)
-struct NormP { const float *C2; const float2 *bank; float *nP; int n, nslices, ldn, Bs, Hs, HsP; };
+struct NormP { const float *C2; const float2 *bank; float *nP; int n, nslices, ldn, Bs, Hs, HsP; RowPlan rows; };
 typedef float v16f __attribute__((ext_vector_type(16)));
 
 __global__ void __launch_bounds__(256, 2) k_slice_norms(NormP P) {
@@ -599,9 +600,9 @@ __global__ void __launch_bounds__(256, 2) k_slice_norms(NormP P) {
             for (int v = 0; v < 16; v++) acc[a][b][v] = 0.f;
     // this thread's share of a tile load: A 4 x float4 (row = idx / 8), B 8 x float4 = 16 complex (row = idx / 16);
     // rows beyond the tables are clamped (their products are never stored)
-    for (int rr = 0; rr < 2 * P.Bs + 2; rr++) {
-        if (rr == 1) continue;                                     // paired order: row 1 is empty
-        const int t = rr >> 1, ky = (rr & 1) ? -t : t;
+    for (int rr = 0; rr < P.HsP; rr++) {
+        int ky;
+        if (!row_ky(P.rows, rr, ky)) continue;                     // the bank's row order (ppm_rows.h): empty rows hold zeros
         const size_t aoff = (size_t)(ky + P.Bs) * 64, boff = (size_t)rr * 64;
         for (int h = 0; h < nhalf; h++) {
             float4 av[4], bv[8];
@@ -746,6 +747,12 @@ constexpr int kRowTwRows = 64;
 #ifndef PPM_GLOBAL_UNROLL
 #define PPM_GLOBAL_UNROLL 4
 #endif
+// 1: the bank pairs the row pairs t and Ns/2 - t of bands beyond Ns/4 in quads and k_global folds them ahead of the shift-row FMAs
+// (ppm_rows.h); 0: the paired order and one step body
+#ifndef PPM_GLOBAL_FOLD
+#define PPM_GLOBAL_FOLD 1
+#endif
+constexpr bool global_fold(int Bs) { return PPM_GLOBAL_FOLD != 0 && Bs > 31; }     // bands of at most 32 pixels run k_global<.., TWO>, which keeps the paired order
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(4))) v4f *RowTwPtr;
@@ -762,6 +769,7 @@ struct GlobP {
     // grid, whose rows are nP_ld / o_ld apart; o_base = d0 * n_psi turns the section's orientation index into the grid's in the hits.
     // The whole grid in one section: nP_ld = n_dir * npsi_store, o_ld = n_orient, o_base = 0.
     int nP_ld, o_ld, o_base;
+    RowPlan rows;         // row order of the bank (ppm_rows.h); rows.HsP = HsP
 };
 
 // The same for pairs of values held in packed registers (both orientations of a stored slice): the swaps and DPP steps work
@@ -863,6 +871,9 @@ __device__ __forceinline__ float reduce_halving(float (&v)[NV], int lane) {
 // row pair: sum_ky Q e^{i 2 pi ky j/Ns} = sum_t (Q(+t) + Q(-t)) cos + i (Q(+t) - Q(-t)) sin, accumulated in the
 // (A, Bq) basis — 8 FMA per shift row j and row PAIR for both orientations — and recombined once per slice;
 // the sum over kx of the shift window is a wavefront halving reduction.
+// Bands beyond Ns/4: the pairs t and t' = Ns/2 - t share their twiddles up to a sign (-1)^j and are stored as one QUAD of rows
+// (ppm_rows.h); the quad's step folds E(t) +- E(t'), O(t) -+ O(t') first — eight adds that serve every shift row of their parity —
+// and then spends the 8 FMA per shift row once for the two pairs.  The plain steps come first in a slice, then the quads.
 // TWO (search bands of at most 32 pixels, e.g. PYP's default 10 A limit on a 256 box): a wave takes TWO slices at once, lanes 0-31 one,
 // lanes 32-63 the other (kx = lane & 31), so that no lane sits beyond the band; every cross-lane step then stays inside a half.
 template <int R, bool HALF, bool TWO>
@@ -874,6 +885,9 @@ __global__ void __launch_bounds__(global_threads(R)) k_global(GlobP P) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // scalar: slice addresses stay in SGPRs
     const int Hs = P.Hs, HsP = P.HsP, Bs = P.Bs, Ns = P.Ns, nsampP = HsP * 64;
     const int nslices = P.n_dir * P.npsi_store;
+    constexpr bool kFold = !TWO && PPM_GLOBAL_FOLD != 0;
+    static_assert(!kFold || U == 4, "a step is one quad of rows");
+    const int plain_rows = kFold ? 4 * P.rows.plain_steps : HsP;     // the rest of the slice's rows are quads
     float2 *Wl = (float2 *)smem;                                    // [NQ][nsampP]
     int pq[NQ];                                                     // a short last block computes its last particle twice
 #pragma unroll
@@ -882,8 +896,8 @@ __global__ void __launch_bounds__(global_threads(R)) k_global(GlobP P) {
     for (int q = 0; q < NQ; q++) {
         const float2 *src = P.Wp + (size_t)pq[q] * Hs * 64;
         for (int i = tid; i < nsampP; i += NT) {
-            const int rr = i >> 6, t = rr >> 1, ky = (rr & 1) ? -t : t;
-            const bool ok = rr != 1 && t <= Bs;
+            int ky = 0;
+            const bool ok = row_ky(P.rows, i >> 6, ky);                  // the bank's row order
             const int srow = ky + Bs;
             Wl[q * nsampP + i] = ok ? src[srow * 64 + (i & 63)] : make_float2(0.f, 0.f);
         }
@@ -979,8 +993,54 @@ __global__ void __launch_bounds__(global_threads(R)) k_global(GlobP P) {
                 for (int q = 0; q < NQ; q++) { wa[q] = wan[q]; wb[q] = wbn[q]; }
             }
         };
+        // One quad (+t, -t, +t', -t'), t' = Ns/2 - t, per step: the even / odd parts of both pairs, their folds, and one set of FMAs
+        // with the twiddles of t.  Shift row j takes the "+" fold of the even parts and the "-" fold of the odd parts when j is even,
+        // the other two when j is odd; the row sums (j = 0) take the "+" folds.
+        auto qstep = [&](int row0, const float2 (&cur)[U], float2 (&nxt)[U]) {
+            {
+                const float2 *np = (row0 + U < HsP) ? Pp + (row0 + U) * 64 : Pnext;
+#pragma unroll
+                for (int u = 0; u < U; u++) nxt[u] = np[u * 64 + kxl];
+            }
+            v4f tw[R];
+#pragma unroll
+            for (int j = 0; j < R; j++) tw[j] = c_rowtw[(row0 >> 1) * PPM_MAX_SHIFT_STEPS + j];
+            float2 w[NQ][U];
+#pragma unroll
+            for (int q = 0; q < NQ; q++)
+#pragma unroll
+                for (int u = 0; u < U; u++) w[q][u] = Wl[q * nsampP + (row0 + u) * 64 + kxl];
+#pragma unroll
+            for (int q = 0; q < NQ; q++) {
+                v2f as2[2], ad2[2], bs2[2], bd2[2];
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const v2f wav = { w[q][2 * h].x, w[q][2 * h].y }, wbv = { w[q][2 * h + 1].x, w[q][2 * h + 1].y };
+                    const v2f aa = wav * cur[2 * h].x, ab = wbv * cur[2 * h + 1].x, ba = wav * cur[2 * h].y, bb = wbv * cur[2 * h + 1].y;
+                    as2[h] = aa + ab; ad2[h] = aa - ab; bs2[h] = ba + bb; bd2[h] = ba - bb;
+                }
+                // [0]: what the even shift rows take, [1]: the odd ones
+                const v2f ea[2] = { as2[0] + as2[1], as2[0] - as2[1] }, eb[2] = { bs2[0] + bs2[1], bs2[0] - bs2[1] };
+                const v2f oa[2] = { ad2[0] - ad2[1], ad2[0] + ad2[1] }, ob[2] = { bd2[0] - bd2[1], bd2[0] + bd2[1] };
+                sa[q] += ea[0]; sb[q] += eb[0];
+#pragma unroll
+                for (int j = 0; j < R; j++) {
+                    const v4f t = tw[j];
+                    const v2f tc = { t.x, t.y }, ts = { t.z, t.w };
+                    const int par = (j + 1) & 1;                                     // tw[j] belongs to shift row j + 1
+                    ua[q][j] += ea[par] * tc; ub[q][j] += eb[par] * tc;
+                    va[q][j] += oa[par] * ts; vb[q][j] += ob[par] * ts;
+                }
+            }
+        };
         __builtin_amdgcn_s_setprio(3);
-        for (int row0 = 0; row0 < HsP; row0 += 2 * U) { step(row0, pv, pn); step(row0 + U, pn, pv); }      // HsP is a multiple of 2 U
+        // plain steps, then quads; two steps per trip (the prefetch ping-pong), an odd count of plain steps shares a trip with the first quad
+        int row0 = 0;
+        for (; row0 + 2 * U <= plain_rows; row0 += 2 * U) { step(row0, pv, pn); step(row0 + U, pn, pv); }
+        if constexpr (kFold) {
+            if (row0 < plain_rows) { step(row0, pv, pn); qstep(row0 + U, pn, pv); row0 += 2 * U; }
+            for (; row0 < HsP; row0 += 2 * U) { qstep(row0, pv, pn); qstep(row0 + U, pn, pv); }      // HsP is a multiple of 2 U
+        }
         __builtin_amdgcn_s_setprio(0);          // the reduction tail is a chain of dependent cross-lane steps: let it issue first
         const int dir = msl / P.npsi_store, ks = msl - dir * P.npsi_store;
 #pragma unroll
