@@ -398,6 +398,20 @@ int ppm_sva_align_average(ppm_ref_t *ref, ppm_accum_t *acc, const ppm_sva_cfg *c
 int ppm_finalize(ppm_accum_t *acc, const ppm_final_cfg *cfg, float *half1, float *half2,
                  float *filtered, double *stats);
 
+/* Shape masking of a reference map: the work of frealign_v9.11/bin/apply_mask.exe, which PYP runs on last iteration's map at the
+ * top of every refinement iteration (src/pyp/align/core.py:783-856, answers in the order of :788-799).  Build-defined (the binary
+ * is absent from the reference checkout):
+ *   core = {mask >= 0.5}; d = Euclidean distance in voxels to the nearest core voxel, no wrap-around at the faces of the box;
+ *   s    = max(clamp(mask, 0, 1), (1 + cos(pi d / edge_width)) / 2 for d < edge_width, else 0)     (edge_width 0: the clamp alone)
+ *   O    = map (filter 0), or the map low-passed in Fourier space (filter 2): 1 up to r_c - e/2 Fourier pixels, a raised cosine to 0
+ *          at r_c + e/2, with r_c = n pixel_size / filter_radius_A and e = filter_edge_px (e = 0: a step at r_c)
+ *   out  = s map + (1 - s) outside_weight O
+ * map, mask, out: n^3 floats, x fastest; on_device != 0: all three are device pointers; out may equal map.  n: 8..512; filter 2
+ * needs a box the transforms take (even, 32..512, prime factors 2, 3, 5, 7); edge_width: 0..64.  Anything else returns -22. */
+typedef struct ppm_mask_cfg { double pixel_size; int edge_width; double outside_weight;
+                              int filter; double filter_radius_A; double filter_edge_px; } ppm_mask_cfg;
+int ppm_mask_volume(const void *map, const void *mask, int on_device, int n, const ppm_mask_cfg *cfg, void *out);
+
 /* Particle extraction straight into a (resident) stack — the step before the path:
  * crop `box` x `box` windows around the picked coordinates, fill what falls outside the micrograph with the mean
  * of the inside part, replace empty boxes by white noise, subtract the background mean and divide by the background

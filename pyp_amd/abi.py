@@ -127,3 +127,16 @@ class SvaCfg(C.Structure):
 class FinalCfg(C.Structure):
     _fields_ = [("molecular_mass_kda", C.c_float), ("inner_radius", C.c_float), ("outer_radius", C.c_float),
                 ("mask_falloff", C.c_float)]
+
+
+class MaskCfg(C.Structure):
+    """ppm_mask_cfg (include/ppm.h)."""
+    _fields_ = [("pixel_size", C.c_double), ("edge_width", C.c_int), ("outside_weight", C.c_double), ("filter", C.c_int),
+                ("filter_radius_A", C.c_double), ("filter_edge_px", C.c_double)]
+
+    @classmethod
+    def make(cls, pixel_size, edge_width=3, outside_weight=0.0, filter=0, filter_radius_A=10.0, filter_edge_px=10.0):
+        """edge_width: cosine edge added to the mask (voxels, 0 = none); outside_weight: weight of the density outside the mask;
+        filter: low-pass of that density (0 = none, 2 = cosine edge at filter_radius_A Angstrom, filter_edge_px Fourier pixels wide)."""
+        return cls(pixel_size=float(pixel_size), edge_width=int(edge_width), outside_weight=float(outside_weight), filter=int(filter),
+                   filter_radius_A=float(filter_radius_A), filter_edge_px=float(filter_edge_px))

@@ -28,6 +28,7 @@
 #include "ppm_csp_kernels.h"
 #include "ppm_sva_kernels.h"
 #include "ppm_gfft.h"
+#include "ppm_mask_kernels.h"
 
 using namespace ppm;
 
@@ -36,3 +37,4 @@ using namespace ppm;
 #include "host_recon.h"
 #include "host_csp.h"
 #include "host_sva.h"
+#include "host_mask.h"

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import lib
-from .abi import NCOL, STATS_COLS, K_NAMES, FinalCfg, ReconCfg, RefineCfg  # noqa: F401
+from .abi import NCOL, STATS_COLS, K_NAMES, FinalCfg, MaskCfg, ReconCfg, RefineCfg  # noqa: F401
 
 
 def _sync_producer(t):
@@ -301,6 +301,40 @@ def extract_boxes(micrograph, coords, box, radius_A, pixel_size, coordinate_binn
     lib.check(lib.load().ppm_extract_boxes(ip, idev, int(rows), int(cols), lib.ptr(coords), m, int(box), float(coordinate_binning),
                                            radius_px, int(bool(normalize)), int(bool(fix_empty)), op, odev))
     del keep
+    return res
+
+
+def mask_volume(vol, mask, cfg, out=None, device=0):
+    """Shape-mask a map (ppm_mask_volume, what apply_mask.exe does to last iteration's map): vol, mask = N^3 float32, both numpy
+    arrays or both CUDA torch tensors; cfg: abi.MaskCfg.  Returns an array of the kind it was given; `out` (same kind and shape, may
+    be `vol` itself) receives the result in place of a new array."""
+    lib.init(device)
+    on_dev = bool(getattr(vol, "is_cuda", False))
+    if on_dev != bool(getattr(mask, "is_cuda", False)) or (out is not None and on_dev != bool(getattr(out, "is_cuda", False))):
+        raise ValueError("ERROR: mask_volume: map, mask and out must all be on the host or all on the device")
+    if not on_dev:
+        vol = np.ascontiguousarray(vol.numpy() if hasattr(vol, "numpy") else vol, dtype=np.float32)
+        mask = np.ascontiguousarray(mask.numpy() if hasattr(mask, "numpy") else mask, dtype=np.float32)
+    shape = tuple(int(x) for x in vol.shape)
+    if len(shape) != 3 or len(set(shape)) != 1:
+        raise ValueError("ERROR: mask_volume: the map must be a cubic volume")
+    if tuple(int(x) for x in mask.shape) != shape:
+        raise ValueError("ERROR: mask_volume: map and mask have different dimensions")
+    n = shape[0]
+    if on_dev:
+        import torch
+        res = torch.empty_like(vol) if out is None else out
+        if tuple(res.shape) != shape:
+            raise ValueError("ERROR: mask_volume: out has the wrong shape")
+        pv, _, _ = _volumes_arg(vol, 1, n)
+        pm, _, _ = _volumes_arg(mask, 1, n)
+        po, _, _ = _volumes_arg(res, 1, n)
+    else:
+        res = np.empty_like(vol) if out is None else out
+        if not isinstance(res, np.ndarray) or res.dtype != np.float32 or res.shape != shape or not res.flags.c_contiguous:
+            raise ValueError("ERROR: mask_volume: out must be a contiguous float32 array of the map's shape")
+        pv, pm, po = lib.ptr(vol), lib.ptr(mask), lib.ptr(res)
+    lib.check(lib.load().ppm_mask_volume(pv, pm, 1 if on_dev else 0, n, C.byref(cfg), po))
     return res
 
 

@@ -16,7 +16,7 @@ EXPORTS = [
     "ppm_insert_batch", "ppm_accum_download", "ppm_accum_download_range", "ppm_accum_add", "ppm_accum_count", "ppm_accum_set_count",
     "ppm_finalize", "ppm_profile_enable", "ppm_profile_reset", "ppm_profile_get", "ppm_device_alloc",
     "ppm_device_free", "ppm_device_upload", "ppm_device_sync", "ppm_extract_boxes", "ppm_host_alloc", "ppm_host_free", "ppm_host_read",
-    "ppm_comm_unique_id", "ppm_comm_create", "ppm_comm_count", "ppm_comm_destroy", "ppm_accum_reduce", "ppm_sva_insert", "ppm_sva_align_average",
+    "ppm_comm_unique_id", "ppm_comm_create", "ppm_comm_count", "ppm_comm_destroy", "ppm_accum_reduce", "ppm_sva_insert", "ppm_sva_align_average", "ppm_mask_volume",
 ]
 
 
@@ -83,6 +83,7 @@ def load():
     L.ppm_comm_count.argtypes = [vp]; L.ppm_comm_count.restype = ci
     L.ppm_comm_destroy.argtypes = [vp]; L.ppm_comm_destroy.restype = None
     L.ppm_accum_reduce.argtypes = [vp, vp, ci]; L.ppm_accum_reduce.restype = ci
+    L.ppm_mask_volume.argtypes = [vp, vp, ci, ci, vp, vp]; L.ppm_mask_volume.restype = ci
     _lib = L
     return L
 

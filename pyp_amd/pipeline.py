@@ -5,16 +5,24 @@ Sharded runs call this once per rank and reduce the accumulator with `pyp_amd.di
 import numpy as np
 
 from . import host, select
-from .abi import FinalCfg, ReconCfg
+from .abi import FinalCfg, MaskCfg, ReconCfg
 from .formats.cistem import COL
 
 
 def iteration(vol, stack, rows, refine_cfg, *, pixel_size, molecular_mass_kda, symmetry="C1", keep_fraction=1.0,
-              score_weight_bfactor=0.0, outer_radius=None, split_by_pind=False):
+              score_weight_bfactor=0.0, outer_radius=None, split_by_pind=False, mask=None, mask_cfg=None):
     """vol: current reference (N^3 float32); stack: [M, N, N] float32 (numpy or a CUDA torch tensor); rows: [M, 32].
+    mask (N^3 float32, of the same kind as vol) with mask_cfg (abi.MaskCfg; default: PYP's edge of 3 voxels, weight 0): the
+    reference is shape-masked on the device first, as `shape_mask_reference` (align/core.py:783-856) does with apply_mask.exe.
     Returns dict(rows=refined table incl. OCC after selection, half1, half2, filtered, stats=[N/2-1, 7] statistics table).
     """
     n = int(refine_cfg.box)
+    if mask is not None:
+        vol = host.mask_volume(vol, mask, mask_cfg if mask_cfg is not None else MaskCfg.make(pixel_size=pixel_size))
+        if getattr(vol, "is_cuda", False):          # map and mask were device tensors: Reference takes a host array
+            vol = vol.cpu().numpy()
+    elif mask_cfg is not None:
+        raise ValueError("ERROR: iteration: mask_cfg given without a mask")
     ref = host.Reference(vol, n / 2)
     try:
         refined = ref.refine(refine_cfg, stack, rows)

@@ -13,7 +13,7 @@ import time
 
 import numpy as np
 
-from ..abi import FinalCfg, ReconCfg, RefineCfg
+from ..abi import FinalCfg, MaskCfg, ReconCfg, RefineCfg
 from ..formats import cistem, mrc, parfile
 from . import prompts
 
@@ -792,4 +792,65 @@ def merge3d_main(argv=None, stdin=None):
     for line in format_stats_table(stats):
         print(line)
     print("\n\nMerge3D: Normal termination\n", flush=True)
+    return 0
+
+
+# ------------------------------------------------------------------------------------------ apply_mask.exe
+def apply_mask_main(argv=None, stdin=None, backend=None):
+    """frealign_v9.11's apply_mask.exe as PYP runs it on last iteration's map (src/pyp/align/core.py:783-856): both files are read in
+    full before anything is written (the output may be the input map, :1613), the result appears under its name only when complete.
+    backend: what computes (vol, mask, MaskCfg) -> masked map; default host.mask_volume on the GPU, under the per-GPU lock."""
+    t0 = time.time()
+    try:
+        d = prompts.parse_apply_mask(prompts.read_answers(stdin or sys.stdin))
+    except prompts.PromptError as e:
+        _die(str(e))
+    print("\n        **   Welcome to ApplyMask (MI355X / libpypmatch)   **\n")
+    for k, v in d.items():
+        print(f"{k:28s}: {v}")
+    for p in (d["map"], d["mask"]):
+        if not os.path.exists(p):
+            _die(f"ERROR: apply_mask: input file {p} does not exist")
+    try:
+        head = mrc.read_header(d["map"])
+        vol = mrc.read(d["map"]).astype(np.float32)
+        mask = mrc.read(d["mask"]).astype(np.float32)
+    except (IOError, ValueError) as e:
+        _die(str(e))
+    if vol.ndim != 3 or len(set(vol.shape)) != 1:
+        _die(f"ERROR: apply_mask: the input map is {vol.shape}, only cubic maps are supported")
+    if mask.shape != vol.shape:
+        _die(f"ERROR: apply_mask: the map is {vol.shape}, the mask {mask.shape}")
+    px = d["pixel_size"] if d["pixel_size"] is not None else float(head["pixel_size"])
+    if not px > 0:
+        _die(f"ERROR: apply_mask: pixel size {px:g} is not positive")
+    cfg = MaskCfg.make(pixel_size=px, edge_width=d["edge_width"], outside_weight=d["outside_weight"], filter=d["filter"],
+                       filter_radius_A=d["filter_radius"] if d["filter"] == 2 else 1.0, filter_edge_px=d["filter_edge"])
+    t1 = time.time()
+    try:
+        if backend is not None:
+            out = backend(vol, mask, cfg)
+        else:
+            from .. import host, lib
+            dev = int(os.environ.get("PPM_DEVICE", "0"))
+            try:
+                with gpu_lock(dev):
+                    out = host.mask_volume(vol, mask, cfg, device=dev)
+            except lib.PpmError as e:
+                _die(str(e))
+    except ValueError as e:
+        _die(str(e))
+    t2 = time.time()
+    tmp = d["output"] + ".tmp%d" % os.getpid()
+    try:
+        mrc.write(np.asarray(out, dtype=np.float32), tmp, pixel_size=px)
+        os.replace(tmp, d["output"])
+    except OSError as e:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        _die(f"ERROR: apply_mask: could not write {d['output']}: {e}")
+    print(f"\nMasked a {vol.shape[0]}^3 map at {px:g} A/pixel: edge {d['edge_width']} pixels, weight outside {d['outside_weight']:g}, filter {d['filter']}")
+    print(f"Timing: inputs {t1 - t0:.2f} s, device {t2 - t1:.2f} s, output {time.time() - t2:.2f} s")
+    _release_warm()
+    print("\nApplyMask: Normal termination\n", flush=True)
     return 0

@@ -2,8 +2,8 @@
 
 The caller never parses prompts; it pipes a here-doc of answers, one per line, `yes`/`no` for
 booleans (src/pyp/refine/frealign/frealign.py:3918-3994 refine3d, :1780-1824 reconstruct3d,
-:1878-1888 local_merge3d, :2075-2093 merge3d; the `.par`-surface refine3d script is preserved at
-src/pyp/system/wrapper_functions.py:512-561).  Answer order: SURVEY.md §9.1-§9.3.
+:1878-1888 local_merge3d, :2075-2093 merge3d; src/pyp/align/core.py:811-850 apply_mask.exe; the `.par`-surface refine3d script
+is preserved at src/pyp/system/wrapper_functions.py:512-561).  Answer order: SURVEY.md §9.1-§9.3.
 """
 
 
@@ -146,6 +146,49 @@ def parse_merge3d(answers):
 
 def parse_local_merge3d(answers):
     return _take(answers, LOCAL_MERGE3D, "local_merge3d")
+
+
+def parse_apply_mask(answers):
+    """apply_mask.exe (frealign_v9.11), answers in the order of the questions at src/pyp/align/core.py:788-799: image format, input
+    map, pixel size, input mask, width of the cosine edge, weight outside, outside filter, [filter radius in A, filter edge in pixels,]
+    output map.  Two layouts: 10 answers, or the 8 PYP sends with filter `0` / `0.0` (:833-850: no radius, no filter edge).  The
+    filter answer is a number (`0` and `0.0` both mean none).  pixel_size None: `*`, the map header's value.  Refused here: what
+    can be told from the answers alone (format other than M, the Gaussian filter 1, ranges ppm_mask_volume refuses, include/ppm.h)."""
+    prog = "apply_mask"
+    a = list(answers)
+    if len(a) < 8:
+        raise PromptError(f"ERROR: {prog}: expected 8 or 10 answers, got {len(a)}")
+    d = _take(a, [("format", str), ("map", str), ("pixel", str), ("mask", str), ("edge_width", float), ("outside_weight", float),
+                  ("filter", float)], prog)
+    if d["format"].upper() != "M":
+        raise PromptError(f"ERROR: {prog}: image format '{d['format']}' is not supported by this build (only M, MRC)")
+    d["pixel_size"] = None if d.pop("pixel") == "*" else _num(a[2], "pixel_size")
+    if d["pixel_size"] is not None and not d["pixel_size"] > 0:
+        raise PromptError(f"ERROR: {prog}: pixel size must be positive or *, got '{a[2]}'")
+    if d["edge_width"] != int(d["edge_width"]) or not 0 <= d["edge_width"] <= 64:
+        raise PromptError(f"ERROR: {prog}: width of the cosine edge must be a whole number of pixels, 0..64, got '{a[4]}'")
+    d["edge_width"] = int(d["edge_width"])
+    if d["filter"] == 1:
+        raise PromptError(f"ERROR: {prog}: the Gaussian low-pass filter outside (1) is not supported by this build (0 = none, 2 = cosine edge)")
+    if d["filter"] not in (0, 2):
+        raise PromptError(f"ERROR: {prog}: low-pass filter outside must be 0 or 2, got '{a[6]}'")
+    d["filter"] = int(d["filter"])
+    if d["filter"] == 0 and len(a) == 8:
+        d.update(filter_radius=0.0, filter_edge=0.0)
+        rest = a[7:]
+    else:
+        if len(a) < 10:
+            raise PromptError(f"ERROR: {prog}: expected 10 answers (filter radius and filter edge before the output), got {len(a)}")
+        d.update(_take(a[7:], [("filter_radius", float), ("filter_edge", float)], prog))
+        rest = a[9:]
+    if len(rest) != 1:
+        raise PromptError(f"ERROR: {prog}: expected 8 or 10 answers, got {len(a)}")
+    d.update(_take(rest, [("output", str)], prog))
+    if d["filter"] == 2 and not d["filter_radius"] > 0:
+        raise PromptError(f"ERROR: {prog}: cosine edge filter radius must be positive, got '{a[7]}'")
+    if d["filter"] == 2 and not d["filter_edge"] >= 0:
+        raise PromptError(f"ERROR: {prog}: width of the filter edge must not be negative, got '{a[8]}'")
+    return d
 
 
 def dump_name(seed, k):
