@@ -263,6 +263,11 @@ const char *ppm_refine_note(ppm_ref_t *ref);
  * pass 4 GB on the transform path or their share of the device's memory; the result does not depend on the sectioning.  With more
  * than one section ppm_refine_note() says so. */
 int ppm_refine_last_sections(ppm_ref_t *ref);
+/* Whether the last ppm_refine_batch on this reference ran the refinement of a chunk's hits on a second stream beside the grid search of
+ * the next chunk: the number of hit-stage blocks a compute unit takes beside one block of the search, 0 when the call kept the serial
+ * order (one chunk, a search by transform, tiles or sections, no grid search, no room on a compute unit, or PPM_REFINE_OVERLAP=0).
+ * The result does not depend on it. */
+int ppm_refine_last_overlap(ppm_ref_t *ref);
 
 /* refine3d answers 8 / 43 "matching projections" (frealign.py:3929-3931, refine_fmatch): out[i] (box * box floats, host) = the
  * reference projected at row i's pose, times the row's CTF, moved to the row's X / Y shift and band-limited at cfg->res_high — the

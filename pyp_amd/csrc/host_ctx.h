@@ -33,6 +33,8 @@ struct Ctx {
     struct PlanDev { FftPlan plan; bool ready = false; };
     PlanDev plans[513];             // FFT plans by length (tables live in device memory)
     size_t total_mem = 0;           // of the device (hipDeviceProp_t::totalGlobalMem): what the byte budgets of the workspaces are shares of
+    int cu_count = 0;               // compute units: the resident grid of k_global (launch_global)
+    size_t lds_per_cu = 0;          // bytes of LDS a CU shares among its blocks (ppm_overlap.h)
     bool prof_on = false;
     double prof_ms[PPM_K_COUNT] = { 0 };
     long prof_n[PPM_K_COUNT] = { 0 };
@@ -171,6 +173,7 @@ struct DevTmp {
 
 struct ppm_ref {
     hipStream_t stream = nullptr, copy = nullptr;       // this handle's compute and copy streams (StreamScope)
+    hipStream_t local = nullptr;                        // second compute stream: the local stage of chunk i beside the search of chunk i + 1 (made on first use)
     int N = 0, B = 0, CX = 0, CY = 0, NBX = 0, NBY = 0, pad = 1; unsigned LB = 0;   // B, CX, CY count samples of the padded transform
     float2 *cube = nullptr;
     // workspaces (grown on demand, reused across calls)
@@ -197,11 +200,15 @@ struct ppm_ref {
     DevBuf<int> tile_c;
     DevBuf<Hit> hits_s; DevBuf<int> sec_k;      // grid search in sections: the sections' top-K lists of a chunk and the offsets of the lists
     DevBuf<LState> states, states2;
+    // the second set of the per-chunk workspaces the local stage reads: chunks of odd index take it when ppm_refine_batch overlaps the
+    // local stage of a chunk with the search of the next (ppm_overlap.h); allocated by the first call that does
+    struct Lane { DevBuf<double> rows_in, rows_out; DevBuf<float> wring, cw, ddef; DevBuf<float2> Il; DevBuf<Hit> hits; DevBuf<LState> states, states2; } alt;
     // full-window correlation (k_gfft): the bank in the column pass's layout, window maxima per (particle, orientation), column penalties
     DevBuf<float4> bank4; DevBuf<float> part, gtw;       // gtw: twiddle tables of the search grid (butterfly table, line table), then the window's column penalties
     std::string grid_key, bank_key, bank4_key; int gtw_ns = 0, gtw_rsx = -1;     // what mats / dir_* / twN / rowtw and the two banks hold (grid; grid + section)
     long last_counts[4] = { 0, 0, 0, 0 };
     int last_sections = 0;           // sections of the last call's grid search (0: it had none)
+    int last_overlap = 0;            // hit-stage blocks per CU beside k_global in the last call (0: serial order)
     std::string note;
 };
 
@@ -297,6 +304,8 @@ int ppm_init(int device) {
     if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
         return fail(-19, std::string("device is ") + prop.gcnArchName + ", libpypmatch is built for gfx950 only");
     g.total_mem = prop.totalGlobalMem;
+    g.cu_count = std::max(1, prop.multiProcessorCount);
+    g.lds_per_cu = std::max((size_t)prop.maxSharedMemoryPerMultiProcessor, (size_t)160 * 1024);     // gfx950: 160 KB, what the kernels' launches are sized for
     if (!g.stream) HIPCHK(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
     if (!g.copy) HIPCHK(hipStreamCreateWithFlags(&g.copy, hipStreamNonBlocking));
     if (!g.upload) HIPCHK(hipStreamCreateWithFlags(&g.upload, hipStreamNonBlocking));

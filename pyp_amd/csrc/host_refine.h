@@ -55,9 +55,40 @@ template <int R, bool HALF, bool TWO>
 static int launch_global_k(const GlobP &P, int n_img, size_t lds) {
     static bool set = false;
     { std::lock_guard<std::mutex> lk_attr(g_mu); if (!set) { HIPCHK(hipFuncSetAttribute((const void *)k_global<R, HALF, TWO>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } }
-    hipLaunchKernelGGL((k_global<R, HALF, TWO>), dim3((n_img + global_particles(R) - 1) / global_particles(R)), dim3(global_threads(R)), lds, cur_stream(), P);
+    // resident grid: every block takes most of a CU's LDS, so a CU holds one; the blocks walk the particle groups in strides of the grid
+    const int ngroups = (n_img + global_particles(R) - 1) / global_particles(R);
+    hipLaunchKernelGGL((k_global<R, HALF, TWO>), dim3(std::min(ngroups, g.cu_count)), dim3(global_threads(R)), lds, cur_stream(), P);
     HIPCHK(hipGetLastError());
     return 0;
+}
+template <int R>
+static const void *global_kernel_r(bool half, bool two) {
+    if (two) return half ? (const void *)k_global<R, true, true> : (const void *)k_global<R, false, true>;
+    return half ? (const void *)k_global<R, true, false> : (const void *)k_global<R, false, false>;
+}
+// the instantiation launch_global runs for a window of R steps (ppm_overlap.h reads its registers and LDS)
+static const void *global_kernel(int R, bool half, int Bs) {
+    const bool two = Bs <= 31;
+    switch (R) {
+        case 1: return global_kernel_r<1>(half, two);
+        case 2: return global_kernel_r<2>(half, two);
+        case 3: return global_kernel_r<3>(half, two);
+        case 4: return global_kernel_r<4>(half, two);
+        case 5: return global_kernel_r<5>(half, two);
+        default: return global_kernel_r<6>(half, two);
+    }
+}
+// dynamic LDS of a k_global launch: the W tables of a block's particles, or the top-K pass's copy of a particle's scores when that is larger
+static size_t global_lds_bytes(int HsP, int n_orient, int R, int *topk_lds) {
+    size_t lds = (size_t)HsP * 64 * sizeof(float2) * global_particles(R);
+    if (lds < 1024) lds = 1024;
+    // the top-K pass re-uses the block's LDS for a copy of the particle's scores of this launch (one section of the grid) when they
+    // fit (160 KB = 40 928 orientations, e.g. 8 deg at C1 in one section); larger sections select on the global scratch instead
+    const size_t lds_topk = (size_t)(32 + n_orient) * sizeof(float);
+    const int fits = lds_topk <= (size_t)160 * 1024 ? 1 : 0;
+    if (topk_lds) *topk_lds = fits;
+    if (fits && lds_topk > lds) lds = lds_topk;
+    return lds;
 }
 template <int R>
 static int launch_global_r(const GlobP &P, int n_img, bool half, size_t lds) {
@@ -67,14 +98,8 @@ static int launch_global_r(const GlobP &P, int n_img, bool half, size_t lds) {
 }
 
 static int launch_global(GlobP &P, int n_img, bool half, int R) {
-    size_t lds = (size_t)P.HsP * 64 * sizeof(float2) * global_particles(R);
     P.n = n_img;
-    if (lds < 1024) lds = 1024;
-    // the top-K pass re-uses the block's LDS for a copy of the particle's scores of this launch (one section of the grid) when they
-    // fit (160 KB = 40 928 orientations, e.g. 8 deg at C1 in one section); larger sections select on the global scratch instead
-    const size_t lds_topk = (size_t)(32 + P.n_orient) * sizeof(float);
-    P.topk_lds = lds_topk <= (size_t)160 * 1024 ? 1 : 0;
-    if (P.topk_lds && lds_topk > lds) lds = lds_topk;
+    const size_t lds = global_lds_bytes(P.HsP, P.n_orient, R, &P.topk_lds);
     ProfScope ps(PPM_K_GLOBAL);
     switch (R) {
         case 1: return launch_global_r<1>(P, n_img, half, lds);
@@ -172,6 +197,12 @@ static void launch_defocus(const CubeView &cv, const Geom &gm, const uint32_t *s
 }
 
 namespace {
+// the per-chunk workspaces the local stage reads, as one chunk sees them: the handle's own set, or its second one (ppm_ref::alt)
+struct LaneV { double *rows_in, *rows_out; float *wring, *cw, *ddef; float2 *Il; Hit *hits; LState *states, *states2; };
+LaneV lane_view(ppm_ref *ref, int lane) {
+    if (lane) { auto &a = ref->alt; return { a.rows_in.p, a.rows_out.p, a.wring.p, a.cw.p, a.ddef.p, a.Il.p, a.hits.p, a.states.p, a.states2.p }; }
+    return { ref->rows_in.p, ref->rows_out.p, ref->wring.p, ref->cw.p, ref->ddef.p, ref->Il.p, ref->hits.p, ref->states.p, ref->states2.p };
+}
 // what a ppm_refine_batch call works out before its chunk loop, shared by its stages
 struct RefineRun {
     ppm_ref *ref = nullptr; const ppm_refine_cfg *cfg = nullptr;
@@ -192,6 +223,9 @@ struct RefineRun {
     int ndef = 0;                       // defocus offsets tried on either side of the row's values
     int per_iter = 0; bool cls_on = false;
     double sample_evals = 0;            // in-band samples summed over all local score evaluations of one particle
+    // the local stage of chunk i on a second stream beside the search of chunk i + 1 (ppm_overlap.h)
+    bool overlap = false; int tenants = 0;
+    hipEvent_t ev_pre = nullptr;        // recorded ahead of k_global when set: the other stream's hit stage starts with it, not before it
 
     int ntiles() const { return (int)(cxs.size() * cys.size()); }
     int nsec() const { return (int)secs.size(); }
@@ -199,6 +233,8 @@ struct RefineRun {
     size_t bank4_slice() const { return use_fft ? (size_t)gpl.L * gpl.L : 0; }              // float4 per stored slice of k_gfft's
     size_t HS() const { return (size_t)gm.Hs * 64; }
     int prefix_of(double rband) const { int rg = (int)std::ceil(rband); if (rg > gm.B + 1) rg = gm.B + 1; return sl.ring_off[rg]; }
+    // the highest ring a list prefix of S samples holds (a prefix ends with a whole band of rings, build_samples): its samples lie at |k| < ring + 1
+    int reach_of(int S) const { int b = gm.B + 2; while (b > 1 && sl.ring_off[b] > S) b--; return std::min(gm.B, b - 1); }
 };
 constexpr int kTileR = 6;               // k_global keeps its shift window in registers: up to kTileR steps either side without scratch
 constexpr int kFinalThreads = 256;      // block of the final (one pose per particle) k_local launch
@@ -351,6 +387,21 @@ static int ensure_chunk_buffers(RefineRun &r, bool images_on_device) {
     if (int rc = ref->states2.ensure(CH)) return rc;
     return 0;
 }
+// ... and the second set of those the local stage reads, for a call that overlaps it with the next chunk's search
+static int ensure_alt_buffers(RefineRun &r) {
+    ppm_ref *ref = r.ref; const Geom &gm = r.gm; const int CH = r.CH;
+    auto &a = ref->alt;
+    if (int rc = a.rows_in.ensure((size_t)CH * PPM_NCOL)) return rc;
+    if (int rc = a.rows_out.ensure((size_t)CH * PPM_NCOL)) return rc;
+    if (int rc = a.wring.ensure((size_t)CH * (gm.B + 2))) return rc;
+    if (int rc = a.Il.ensure((size_t)CH * r.S_pad)) return rc;
+    if (int rc = a.cw.ensure((size_t)CH * r.S_pad)) return rc;
+    if (int rc = a.hits.ensure((size_t)CH * r.K)) return rc;
+    if (int rc = a.states.ensure((size_t)CH * r.K)) return rc;
+    if (int rc = a.states2.ensure(CH)) return rc;
+    if (r.ndef > 0) if (int rc = a.ddef.ensure(CH)) return rc;
+    return 0;
+}
 
 // k_global's bank of one section of the grid (rebuilt only when the grid, the band or the section changes: a call of one section finds
 // the bank of the call before; with several, every chunk rebuilds every section, and the key keeps the first section of a chunk from
@@ -497,7 +548,7 @@ static int local_setup(RefineRun &r) {
     if (cfg->refine_defocus && cfg->defocus_step > 0 && cfg->defocus_range >= cfg->defocus_step)
         r.ndef = std::min((int)std::floor(cfg->defocus_range / cfg->defocus_step + 1e-6), PPM_MAX_DEFOCUS_STEPS);
     LP.cv = r.cv; LP.samples = ref->samples.p; LP.Il = ref->Il.p; LP.cw = ref->cw.p; LP.S_pad = r.S_pad; LP.nrings = r.nrings; LP.N = gm.N;
-    LP.tabR = cube_tab_radius(gm.B, r.cv.scale);
+    LP.tabR = cube_tab_radius(gm.B, r.cv.scale);        // of the full band: decides between tables and arithmetic; a launch sizes its own (local_shape)
     r.local_tab = local_tables_wanted(LP.tabR);
     LP.rlo2 = (float)(gm.r_lo * gm.r_lo); LP.ring_signed = (float)std::min(gm.ring_signed, 1e30);
     LP.en[0] = cfg->refine_psi; LP.en[1] = cfg->refine_theta; LP.en[2] = cfg->refine_phi; LP.en[3] = cfg->refine_x; LP.en[4] = cfg->refine_y;
@@ -522,13 +573,29 @@ static int local_setup(RefineRun &r) {
     return 0;
 }
 
-static void launch_local(const RefineRun &r, unsigned grid, int threads) {
+// Dynamic LDS of a k_local launch of r.LP (schedule filled) with `threads` per block, whether it takes its tap addresses from LDS tables,
+// and the radius of those.  The choice between tables and arithmetic is that of the full band (the two round differently, so a stage
+// must not change sides with its band); the tables themselves cover the largest marching band of THIS launch — the coordinates its
+// sample-list prefixes reach — so that the one-wave blocks of the hit stage stay small (ppm_overlap.h).  Same entries, fewer of them.
+struct LocalShape { size_t lds; bool tab; int tabR; };
+static LocalShape local_shape(const RefineRun &r, int threads) {
     const LocalP &LP = r.LP;
     const size_t ring = ring_lds_bytes8(threads / 64, kMaxCand, LP.nr);
-    const bool tab = r.local_tab && tables_fit_lds(ring, LP.tabR);
-    const size_t lds = ring + (tab ? cube_tab_bytes(LP.tabR) : 0);
-    if (tab) hipLaunchKernelGGL(k_local<true>, dim3(grid), dim3(threads), lds, cur_stream(), LP);
-    else hipLaunchKernelGGL(k_local<false>, dim3(grid), dim3(threads), lds, cur_stream(), LP);
+    LocalShape s;
+    s.tab = r.local_tab && tables_fit_lds(ring, LP.tabR);
+    int S = 0;
+    for (int t = 0; t < LP.T; t++) S = std::max(S, LP.S_it[t]);
+    if (LP.final_rescore) S = std::max(S, std::max(LP.S_final, LP.S_class));
+    s.tabR = std::min(LP.tabR, cube_tab_radius(r.reach_of(S), r.cv.scale));
+    s.lds = ring + (s.tab ? cube_tab_bytes(s.tabR) : 0);
+    return s;
+}
+static void launch_local(const RefineRun &r, unsigned grid, int threads) {
+    LocalP LP = r.LP;
+    const LocalShape s = local_shape(r, threads);
+    LP.tabR = s.tabR;
+    if (s.tab) hipLaunchKernelGGL(k_local<true>, dim3(grid), dim3(threads), s.lds, cur_stream(), LP);
+    else hipLaunchKernelGGL(k_local<false>, dim3(grid), dim3(threads), s.lds, cur_stream(), LP);
 }
 
 // bands and sample-list prefixes of T compass iterations from the steps (ha, hs), halved after each; `mult` poses per particle run them
@@ -570,6 +637,7 @@ static int search_section(RefineRun &r, int nb, const GridSection &sec, Hit *hit
         FP.nP_ld = r.nslices; FP.o_ld = gm.n_orient; FP.o_base = o0;
         if (int rc = launch_gfft(FP, nb, r.gpl)) return rc;
     } else if (ntiles == 1) {
+        if (r.ev_pre) HIPCHK(hipEventRecord(r.ev_pre, cur_stream()));
         if (int rc = launch_global(GP, nb, gm.half != 0, r.Rwin)) return rc;
     } else {
         // tiles of the shift window (one section: plan_grid_sections): ramp the search tables to the tile's centre, search, keep the
@@ -595,41 +663,56 @@ static int search_section(RefineRun &r, int nb, const GridSection &sec, Hit *hit
 }
 
 // grid search of one chunk: the sections of the grid one after another (one section: straight into the chunk's hits; several: every
-// section's K best into its list, then the K best of the lists) -> states from the hits -> refinement of every hit over the search
-// band -> the best hit, refined at the full band into states2
-static int global_stage(RefineRun &r, int nb) {
-    ppm_ref *ref = r.ref; const ppm_refine_cfg *cfg = r.cfg; const Geom &gm = r.gm; LocalP &LP = r.LP;
-    const int K = r.K, Tb = r.Tb, Tc = r.Tc;
+// section's K best into its list, then the K best of the lists) -> states from the hits.  `L`: the chunk's set of the workspaces the
+// local stage reads (hits_local_stage, which may run on another stream beside the next chunk's search_stage)
+static int search_stage(RefineRun &r, int nb, const LaneV &L) {
+    ppm_ref *ref = r.ref; const Geom &gm = r.gm;
+    const int K = r.K;
     if (r.nsec() == 1) {
-        if (int rc = search_section(r, nb, r.secs[0], ref->hits.p, K)) return rc;
+        if (int rc = search_section(r, nb, r.secs[0], L.hits, K)) return rc;
     } else {
         for (int s = 0; s < r.nsec(); s++)
             if (int rc = search_section(r, nb, r.secs[s], ref->hits_s.p + (size_t)r.kpre[s] * nb, r.kpre[s + 1] - r.kpre[s])) return rc;
         ProfScope ps(PPM_K_TOPK);
-        hipLaunchKernelGGL(k_merge_sections, dim3(nb), dim3(64), 0, cur_stream(), ref->hits_s.p, ref->hits.p, nb, K, r.nsec(), ref->sec_k.p);
+        hipLaunchKernelGGL(k_merge_sections, dim3(nb), dim3(64), 0, cur_stream(), ref->hits_s.p, L.hits, nb, K, r.nsec(), ref->sec_k.p);
         HIPCHK(hipGetLastError());
     }
     {
         ProfScope ps(PPM_K_TOPK);
-        hipLaunchKernelGGL(k_states_from_hits, dim3((nb * K + 255) / 256), dim3(256), 0, cur_stream(), ref->hits.p, ref->states.p, nb, K,
+        hipLaunchKernelGGL(k_states_from_hits, dim3((nb * K + 255) / 256), dim3(256), 0, cur_stream(), L.hits, L.states, nb, K,
                            ref->dir_theta.p, ref->dir_phi.p, gm.n_psi, gm.dpsi, gm.step, 0.5 * gm.dstep, gm.step);
     }
+    return 0;
+}
+
+// LocalP of the hit stage (every hit refined over the search band) and the threads of its blocks: one wave up to 1 024 samples per sweep
+// (no cross-wave steps, 64-sample granularity: k_local 83.9 -> 80.9 ms per 28 672 particles against two waves, 93.2 with four;
+// CHANGELOG.md, Round 5, "one-wave blocks for the hit stage"), two waves above
+static int hit_stage_setup(RefineRun &r, const LaneV &L) {
+    const Geom &gm = r.gm; LocalP &LP = r.LP;
+    LP.Il = L.Il; LP.cw = L.cw;
+    LP.states = L.states; LP.T = r.Tb; LP.final_rescore = 0;
+    LP.nr = std::min(r.nrings, (int)std::ceil(gm.r_s) + 1);
+    fill_schedule(r, 0.5 * gm.dstep, gm.step, r.Tb, gm.r_s, (double)r.K);
+    return LP.S_it[0] <= 1024 ? 64 : 128;
+}
+
+// the states of one chunk's hits -> refinement of every hit over the search band -> the best hit, refined at the full band into states2
+static int hits_local_stage(RefineRun &r, int nb, const LaneV &L) {
+    const ppm_refine_cfg *cfg = r.cfg; const Geom &gm = r.gm; LocalP &LP = r.LP;
+    const int K = r.K, Tb = r.Tb, Tc = r.Tc;
     r.sample_evals = 0;
     if (Tb > 0) {
-        LP.states = ref->states.p; LP.T = Tb; LP.final_rescore = 0;
-        LP.nr = std::min(r.nrings, (int)std::ceil(gm.r_s) + 1);
-        fill_schedule(r, 0.5 * gm.dstep, gm.step, Tb, gm.r_s, (double)K);
+        const int threads = hit_stage_setup(r, L);
         ProfScope ps(PPM_K_LOCAL);
-        // small blocks for the hit stage: one wave up to 1 024 samples per sweep (no cross-wave steps, 64-sample granularity: k_local
-        // 83.9 -> 80.9 ms per 28 672 particles against two waves, 93.2 with four; CHANGELOG.md, Round 5, "one-wave blocks for the hit
-        // stage"), two waves above; 256 threads below
-        launch_local(r, (unsigned)(nb * K), LP.S_it[0] <= 1024 ? 64 : 128);
+        launch_local(r, (unsigned)(nb * K), threads);
     }
     {
         ProfScope ps(PPM_K_TOPK);
-        hipLaunchKernelGGL(k_select_best, dim3((nb + 255) / 256), dim3(256), 0, cur_stream(), ref->states.p, ref->states2.p, nb, K);
+        hipLaunchKernelGGL(k_select_best, dim3((nb + 255) / 256), dim3(256), 0, cur_stream(), L.states, L.states2, nb, K);
     }
-    LP.states = ref->states2.p; LP.T = cfg->local_refine ? Tc : 0; LP.final_rescore = 1; LP.nr = r.nrings;
+    LP.Il = L.Il; LP.cw = L.cw;
+    LP.states = L.states2; LP.T = cfg->local_refine ? Tc : 0; LP.final_rescore = 1; LP.nr = r.nrings;
     fill_schedule(r, 0.5 * gm.dstep / (double)(1 << Tb), gm.step / (double)(1 << Tb), LP.T, gm.r_hi, 1.0);
     r.sample_evals += std::floor(kPi * gm.r_hi * gm.r_hi / 2);
     ProfScope ps(PPM_K_LOCAL);
@@ -638,12 +721,13 @@ static int global_stage(RefineRun &r, int nb) {
 }
 
 // no grid search: the rows' own poses, refined at the full band into states2
-static void rows_stage(RefineRun &r, int nb) {
-    ppm_ref *ref = r.ref; const ppm_refine_cfg *cfg = r.cfg; const Geom &gm = r.gm; LocalP &LP = r.LP;
+static void rows_stage(RefineRun &r, int nb, const LaneV &L) {
+    const ppm_refine_cfg *cfg = r.cfg; const Geom &gm = r.gm; LocalP &LP = r.LP;
     double ha0 = cfg->local_angle_step > 0 ? cfg->local_angle_step : 2.5, hs0 = cfg->local_shift_step > 0 ? cfg->local_shift_step : 2.0;
-    hipLaunchKernelGGL(k_states_from_rows, dim3((nb + 255) / 256), dim3(256), 0, cur_stream(), ref->rows_in.p, ref->states2.p, nb, gm.a, ha0, hs0);
+    hipLaunchKernelGGL(k_states_from_rows, dim3((nb + 255) / 256), dim3(256), 0, cur_stream(), L.rows_in, L.states2, nb, gm.a, ha0, hs0);
     r.sample_evals = 0;
-    LP.states = ref->states2.p; LP.T = cfg->local_refine ? r.Tb + r.Tc : 0; LP.final_rescore = 1; LP.nr = r.nrings;
+    LP.Il = L.Il; LP.cw = L.cw;
+    LP.states = L.states2; LP.T = cfg->local_refine ? r.Tb + r.Tc : 0; LP.final_rescore = 1; LP.nr = r.nrings;
     fill_schedule(r, ha0, hs0, LP.T, gm.r_hi, 1.0);
     r.sample_evals += std::floor(kPi * gm.r_hi * gm.r_hi / 2);
     ProfScope ps(PPM_K_LOCAL);
@@ -651,19 +735,76 @@ static void rows_stage(RefineRun &r, int nb) {
 }
 
 // defocus offsets at the final pose (states2), then the output rows
-static int finish_chunk(RefineRun &r, int nb) {
+static int finish_chunk(RefineRun &r, int nb, const LaneV &L) {
     ppm_ref *ref = r.ref; const Geom &gm = r.gm;
     const float *d_ddef = nullptr;
     if (r.ndef > 0) {
-        if (int rc = ref->ddef.ensure(r.CH)) return rc;
-        launch_defocus(r.cv, gm, ref->samples.p, r.S_pad, ref->Il.p, ref->wring.p, ref->rows_in.p, ref->states2.p, nb, r.ndef, r.cfg->defocus_step,
-                       ref->ddef.p, nullptr, r.cls_on ? (float)(gm.r_cls * gm.r_cls) : 0.f);
-        d_ddef = ref->ddef.p;
+        launch_defocus(r.cv, gm, ref->samples.p, r.S_pad, L.Il, L.wring, L.rows_in, L.states2, nb, r.ndef, r.cfg->defocus_step,
+                       L.ddef, nullptr, r.cls_on ? (float)(gm.r_cls * gm.r_cls) : 0.f);
+        d_ddef = L.ddef;
     }
-    hipLaunchKernelGGL(k_rows_out, dim3((nb + 255) / 256), dim3(256), 0, cur_stream(), ref->states2.p, ref->rows_in.p, ref->rows_out.p, nb, gm.a, gm.r_cls, gm.r_lo, d_ddef);
+    hipLaunchKernelGGL(k_rows_out, dim3((nb + 255) / 256), dim3(256), 0, cur_stream(), L.states2, L.rows_in, L.rows_out, nb, gm.a, gm.r_cls, gm.r_lo, d_ddef);
     HIPCHK(hipGetLastError());
     return 0;
 }
+
+// Whether this call runs the back of chunk i beside the front of chunk i + 1, by the one rule of ppm_overlap.h: the registers and LDS of
+// the two kernels as the runtime reports them for THIS build, plus the dynamic LDS of their launches, against a CU's.
+// PPM_REFINE_OVERLAP=0 keeps the serial order (A/B runs, tests).
+static int plan_overlap(RefineRun &r, int n_img) {
+    ppm_ref *ref = r.ref; const Geom &gm = r.gm;
+    r.overlap = false; r.tenants = 0;
+    OverlapCall c;
+    c.global_search = r.cfg->global_search != 0; c.use_fft = r.use_fft; c.ntiles = r.ntiles(); c.nsections = r.nsec();
+    c.nchunks = (n_img + r.CH - 1) / r.CH; c.hit_stage = r.Tb > 0;
+    const char *e = std::getenv("PPM_REFINE_OVERLAP");
+    c.forced_off = e && std::atoi(e) == 0;
+    if (!overlap_on(1, c)) return 0;            // not a call the rule overlaps, whatever fits on a CU
+    const int threads = hit_stage_setup(r, lane_view(ref, 0));
+    const LocalShape ls = local_shape(r, threads);
+    hipFuncAttributes ga, la;
+    HIPCHK(hipFuncGetAttributes(&ga, global_kernel(r.Rwin, gm.half != 0, gm.Bs)));
+    HIPCHK(hipFuncGetAttributes(&la, ls.tab ? (const void *)k_local<true> : (const void *)k_local<false>));
+    const OverlapKernel host = { ga.numRegs, global_threads(r.Rwin), (long)ga.sharedSizeBytes + (long)global_lds_bytes(r.HsP, r.secs[0].nd * gm.n_psi, r.Rwin, nullptr) };
+    const OverlapKernel tenant = { la.numRegs, threads, (long)la.sharedSizeBytes + (long)ls.lds };
+    // gfx950 (the only device ppm_init accepts): 512 registers per lane and SIMD handed out in eights, four SIMDs, LDS in blocks of 1 280 bytes
+    const OverlapDevice dev = { 512, 4, (long)g.lds_per_cu, 8, 1280 };
+    r.tenants = overlap_tenants(host, tenant, dev);
+    r.overlap = overlap_on(r.tenants, c);
+    if (std::getenv("PPM_TRACE"))
+        fprintf(stderr, "ppm_refine_batch: k_global %d VGPRs / %ld B LDS, hit stage %d threads, %d VGPRs / %ld B LDS: %d blocks per CU beside the search, overlap %s\n",
+                host.vgprs, host.lds_bytes, tenant.threads, tenant.vgprs, tenant.lds_bytes, r.tenants, r.overlap ? "on" : "off");
+    if (!r.overlap) return 0;
+    if (int rc = ensure_alt_buffers(r)) return rc;
+    if (!ref->local) {      // the tenants' stream yields to the search's where the dispatcher has a choice
+        int lo = 0, hi = 0;
+        HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
+        HIPCHK(hipStreamCreateWithPriority(&ref->local, hipStreamNonBlocking, lo));
+    }
+    return 0;
+}
+
+// the events of the two-stream chunk loop (one per workspace set); both streams are drained before the loop's frame goes away,
+// on the error returns too
+struct OverlapStreams {
+    ppm_ref *ref = nullptr; hipEvent_t ready[2] = { nullptr, nullptr }, pre[2] = { nullptr, nullptr }, done[2] = { nullptr, nullptr };
+    int open(ppm_ref *ref_) {
+        ref = ref_;
+        for (int i = 0; i < 2; i++) { ready[i] = ev_get(); pre[i] = ev_get(); done[i] = ev_get(); if (!ready[i] || !pre[i] || !done[i]) return fail(-12, "out of events"); }
+        return 0;
+    }
+    int drain() {
+        HIPCHK(hipStreamSynchronize(ref->local));
+        HIPCHK(hipStreamSynchronize(ref->stream));
+        return 0;
+    }
+    ~OverlapStreams() {
+        if (!ref) return;
+        (void)hipStreamSynchronize(ref->local); (void)hipStreamSynchronize(ref->stream);
+        std::lock_guard<std::mutex> lk(g_mu);
+        for (int i = 0; i < 2; i++) for (hipEvent_t e : { ready[i], pre[i], done[i] }) if (e) g.pool.push_back(e);
+    }
+};
 
 // evaluation counts per particle, for the roofline's algorithmic bytes (ppm_refine_last_counts)
 static void refine_counts(RefineRun &r) {
@@ -741,6 +882,9 @@ void ppm_reference_destroy(ppm_ref_t *r) {
     r->c_delta.release(); r->c_s0.release(); r->c_g0.release(); r->c_out.release(); r->c_eval.release(); r->c_rp.release(); r->c_rt.release(); r->c_slot.release(); r->c_states.release(); r->c_uoff.release(); r->c_mean.release(); r->c_active.release(); r->c_tmean.release(); r->c_acc.release(); r->c_dtrial.release(); r->c_fpm.release(); r->c_delta_t.release(); r->c_rowtab.release(); r->c_gbest.release(); r->c_cscore.release(); r->c_gshift.release(); r->c_cshift.release(); r->c_crot.release(); r->cc.release(); r->mats.release(); r->ddef.release();
     r->band.release(); r->spill.release(); r->Il.release(); r->Wp.release(); r->bank.release(); r->twN.release(); r->rowtw.release(); r->sh.release(); r->samples.release();
     r->hits.release(); r->states.release(); r->states2.release();
+    r->alt.rows_in.release(); r->alt.rows_out.release(); r->alt.wring.release(); r->alt.cw.release(); r->alt.ddef.release(); r->alt.Il.release();
+    r->alt.hits.release(); r->alt.states.release(); r->alt.states2.release();
+    if (r->local) (void)hipStreamDestroy(r->local);
     r->hits_t.release(); r->tile_c.release(); r->hits_s.release(); r->sec_k.release(); r->bank4.release(); r->part.release(); r->gtw.release();
     if (r->stream) (void)hipStreamDestroy(r->stream);
     if (r->copy) (void)hipStreamDestroy(r->copy);
@@ -816,28 +960,85 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
     HIPCHK(hipStreamSynchronize(cur_stream()));
     if (int rc = local_setup(r)) return rc;
 
+    if (r.ndef > 0) if (int rc = ref->ddef.ensure(r.CH)) return rc;
+    if (int rc = plan_overlap(r, n_img)) return rc;
+    ref->last_overlap = r.overlap ? r.tenants : 0;
+
     const int CH = r.CH;
     const size_t NN = (size_t)gm.N * gm.N;
     const ChunkStager stage{ (const float *)images, ref->images.p, images_on_device != 0, n_img, CH, NN };
     if (int rc = stage.prime()) return rc;
-    for (int c0 = 0, ci = 0; c0 < n_img; c0 += CH, ci++) {
-        const int nb = std::min(CH, n_img - c0);
-        HIPCHK(hipMemcpyAsync(ref->rows_in.p, rows_in + (size_t)c0 * PPM_NCOL, (size_t)nb * PPM_NCOL * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    // front of a chunk: rows upload, refinement spectra (+ search tables when the same mask serves both), grid search -> the states of the hits
+    auto front = [&](int c0, int ci, int nb, const LaneV &L) -> int {
+        HIPCHK(hipMemcpyAsync(L.rows_in, rows_in + (size_t)c0 * PPM_NCOL, (size_t)nb * PPM_NCOL * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
         const float *d_img = stage.chunk_ptr(c0, ci);
-        // refinement spectra (+ search tables when the same mask serves both)
-        if (int rc = launch_prep(ref->spill, d_img, ref->rows_in.p, nb, gm, r.Rm_px, r.fall_px, cfg->normalize, cfg->invert, 1, 1, ref->band.p, ref->wring.p,
-                                 ref->samples.p, r.S_pad, ref->Il.p, ref->cw.p,
+        if (int rc = launch_prep(ref->spill, d_img, L.rows_in, nb, gm, r.Rm_px, r.fall_px, cfg->normalize, cfg->invert, 1, 1, ref->band.p, L.wring,
+                                 ref->samples.p, r.S_pad, L.Il, L.cw,
                                  (cfg->global_search && !r.sep_search) ? ref->Wp.p : nullptr, ref->C2.p, ref->nI.p, nullptr, r.focus_on ? r.focus_px : nullptr)) return rc;
         if (r.sep_search)
-            if (int rc = launch_prep(ref->spill, d_img, ref->rows_in.p, nb, gm, cfg->search_mask_radius / gm.a, r.fall_px, cfg->normalize, cfg->invert, 1, 1,
+            if (int rc = launch_prep(ref->spill, d_img, L.rows_in, nb, gm, cfg->search_mask_radius / gm.a, r.fall_px, cfg->normalize, cfg->invert, 1, 1,
                                      ref->band.p, nullptr, nullptr, 0, nullptr, nullptr, ref->Wp.p, ref->C2.p, ref->nI.p)) return rc;
-        if (cfg->global_search) { if (int rc = global_stage(r, nb)) return rc; }
-        else rows_stage(r, nb);
-        if (int rc = finish_chunk(r, nb)) return rc;
-        if (int rc = stage.prefetch_next(c0, ci)) return rc;     // next chunk's images travel while this chunk computes
-        HIPCHK(hipMemcpyAsync(rows_out + (size_t)c0 * PPM_NCOL, ref->rows_out.p, (size_t)nb * PPM_NCOL * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
-        if (int rc = stage.sync()) return rc;
+        if (cfg->global_search) if (int rc = search_stage(r, nb, L)) return rc;
+        return 0;
+    };
+    // back of a chunk: local refinement (of the hits, or of the rows' own poses), defocus, output rows
+    auto back = [&](int nb, const LaneV &L) -> int {
+        if (cfg->global_search) { if (int rc = hits_local_stage(r, nb, L)) return rc; }
+        else rows_stage(r, nb, L);
+        return finish_chunk(r, nb, L);
+    };
+    auto download = [&](int c0, int nb, const LaneV &L) -> int {
+        HIPCHK(hipMemcpyAsync(rows_out + (size_t)c0 * PPM_NCOL, L.rows_out, (size_t)nb * PPM_NCOL * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
+        return 0;
+    };
+    if (!r.overlap) {
+        const LaneV L = lane_view(ref, 0);
+        for (int c0 = 0, ci = 0; c0 < n_img; c0 += CH, ci++) {
+            const int nb = std::min(CH, n_img - c0);
+            if (int rc = front(c0, ci, nb, L)) return rc;
+            if (int rc = back(nb, L)) return rc;
+            if (int rc = stage.prefetch_next(c0, ci)) return rc;     // next chunk's images travel while this chunk computes
+            if (int rc = download(c0, nb, L)) return rc;
+            if (int rc = stage.sync()) return rc;
+        }
+        refine_counts(r);
+        return 0;
     }
+    // Software pipeline over two streams and two sets of the workspaces the local stage reads (chunk parity).  This handle's stream (A)
+    // runs the front of chunk i + 1 while the second stream (B) runs the back of chunk i: the hit stage's one-wave blocks move in beside
+    // the resident blocks of k_global (ppm_overlap.h), the final stage follows when those have left.  Ordering is by events alone:
+    //   A -> B  `ready`: the states of a chunk's hits are written;  `pre`: the next chunk's k_global is next in A's queue (B's hit stage
+    //           waits for it too, so that its blocks do not fill the CUs ahead of the search's)
+    //   B -> A  `done`: the back of the chunk that used a workspace set has finished, the set may be written again
+    // The host drains A and the copy stream at the end of every chunk as before (the image stager's double buffer) and B at the end.
+    OverlapStreams os;
+    if (int rc = os.open(ref)) return rc;
+    const LaneV lanes[2] = { lane_view(ref, 0), lane_view(ref, 1) };
+    int prev_c0 = 0, prev_nb = 0;
+    for (int c0 = 0, ci = 0; ; c0 += CH, ci++) {
+        const bool more = c0 < n_img;
+        const int lane = ci & 1, nb = more ? std::min(CH, n_img - c0) : 0;
+        if (more) {
+            if (ci >= 2) HIPCHK(hipStreamWaitEvent(cur_stream(), os.done[lane], 0));
+            r.ev_pre = os.pre[lane];
+            if (int rc = front(c0, ci, nb, lanes[lane])) return rc;
+            r.ev_pre = nullptr;
+            HIPCHK(hipEventRecord(os.ready[lane], cur_stream()));
+        }
+        if (ci >= 1) {
+            StreamScope sb(ref->local, ref->copy);
+            HIPCHK(hipStreamWaitEvent(cur_stream(), os.ready[lane ^ 1], 0));
+            if (more) HIPCHK(hipStreamWaitEvent(cur_stream(), os.pre[lane], 0));
+            if (int rc = back(prev_nb, lanes[lane ^ 1])) return rc;
+            if (int rc = download(prev_c0, prev_nb, lanes[lane ^ 1])) return rc;
+            HIPCHK(hipEventRecord(os.done[lane ^ 1], cur_stream()));
+        }
+        if (!more) break;
+        if (int rc = stage.prefetch_next(c0, ci)) return rc;
+        if (int rc = stage.sync()) return rc;
+        prev_c0 = c0; prev_nb = nb;
+    }
+    if (int rc = os.drain()) return rc;
     refine_counts(r);
     return 0;
 }
@@ -846,6 +1047,7 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
 const char *ppm_refine_note(ppm_ref_t *ref) { return ref ? ref->note.c_str() : ""; }
 
 int ppm_refine_last_sections(ppm_ref_t *ref) { return ref ? ref->last_sections : 0; }
+int ppm_refine_last_overlap(ppm_ref_t *ref) { return ref ? ref->last_overlap : 0; }
 
 int ppm_refine_last_counts(ppm_ref_t *ref, long *n_global, long *n_local, long *samples_global, long *samples_local) {
     if (!ref) return fail(-22, "null reference");

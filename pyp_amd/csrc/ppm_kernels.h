@@ -880,7 +880,7 @@ template <int R, bool HALF, bool TWO>
 __global__ void __launch_bounds__(global_threads(R)) k_global(GlobP P) {
     constexpr int NT = global_threads(R), NW = NT / 64, U = global_unroll(R), NS = 2 * R + 1, NQ = global_particles(R);
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, p0 = blockIdx.x * NQ;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int sub = TWO ? lane >> 5 : 0, kxl = TWO ? lane & 31 : lane;       // which of the wave's two slices, and the column, this lane works on
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // scalar: slice addresses stay in SGPRs
     const int Hs = P.Hs, HsP = P.HsP, Bs = P.Bs, Ns = P.Ns, nsampP = HsP * 64;
@@ -889,7 +889,19 @@ __global__ void __launch_bounds__(global_threads(R)) k_global(GlobP P) {
     static_assert(!kFold || U == 4, "a step is one quad of rows");
     const int plain_rows = kFold ? 4 * P.rows.plain_steps : HsP;     // the rest of the slice's rows are quads
     float2 *Wl = (float2 *)smem;                                    // [NQ][nsampP]
-    int pq[NQ];                                                     // a short last block computes its last particle twice
+    float txc[R + 1], txs[R + 1];      // per-lane x twiddles e^{+2 pi i kx j / Ns}
+#pragma unroll
+    for (int j = 0; j <= R; j++) {
+        float2 t = P.twN[(kxl * j) & (Ns - 1)];
+        txc[j] = t.x; txs[j] = t.y;
+    }
+    const RowTwPtr c_rowtw = (RowTwPtr)P.rowtw;
+    // Resident grid (launch_global: at most one block per CU): a block walks the particle groups blockIdx.x, blockIdx.x + gridDim.x,
+    // ..., each of them what one block of a full grid did — W tables into LDS, slice loop, top-K.  No block waits for another.
+    const int ngroups = (P.n + NQ - 1) / NQ;
+    for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+    const int p0 = grp * NQ;
+    int pq[NQ];                                                     // a short last group computes its last particle twice
 #pragma unroll
     for (int q = 0; q < NQ; q++) pq[q] = min(p0 + q, P.n - 1);
 #pragma unroll
@@ -910,13 +922,6 @@ __global__ void __launch_bounds__(global_threads(R)) k_global(GlobP P) {
         nI[q] = P.nI[pq[q]];
         c_nP[q] = (const __attribute__((address_space(4))) float *)P.nP + (size_t)pq[q] * P.nP_ld;
     }
-    float txc[R + 1], txs[R + 1];      // per-lane x twiddles e^{+2 pi i kx j / Ns}
-#pragma unroll
-    for (int j = 0; j <= R; j++) {
-        float2 t = P.twN[(kxl * j) & (Ns - 1)];
-        txc[j] = t.x; txs[j] = t.y;
-    }
-    const RowTwPtr c_rowtw = (RowTwPtr)P.rowtw;
     // The first rows of a wave's NEXT slice are requested by the last step of the current one (and those of its first slice
     // here): no load stall at a slice start, and the prefetch of every step is unconditional (a conditional one made the
     // compiler copy the 8 row registers of the untouched set on every step).
@@ -1250,6 +1255,8 @@ __global__ void __launch_bounds__(global_threads(R)) k_global(GlobP P) {
             __threadfence_block();
             __syncthreads();
         }
+    }
+    __syncthreads();                    // the next group's W tables overwrite the LDS the top-K pass worked in
     }
 }
 

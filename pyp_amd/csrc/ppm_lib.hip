@@ -24,6 +24,7 @@
 #include "../../include/ppm.h"
 #include "ppm_geom.h"
 #include "ppm_sections.h"
+#include "ppm_overlap.h"
 #include "ppm_kernels2.h"
 #include "ppm_csp_kernels.h"
 #include "ppm_sva_kernels.h"

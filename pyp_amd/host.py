@@ -134,6 +134,10 @@ class Reference:
         """Sections of the orientation grid the last refine()'s grid search ran in (ppm_refine_last_sections); 0: it had none."""
         return int(lib.load().ppm_refine_last_sections(self.h))
 
+    def last_overlap(self):
+        """Hit-stage blocks per compute unit beside the grid search in the last refine() (ppm_refine_last_overlap); 0: serial order."""
+        return int(lib.load().ppm_refine_last_overlap(self.h))
+
     def close(self):
         if getattr(self, "h", None):
             lib.load().ppm_reference_destroy(self.h)
