@@ -143,9 +143,14 @@ int fft3d(float2 *d, int n, bool inverse) {
     return fft_lines_pass(d, n, nlines, nlines, 1, 0, nlines, 1, inverse);
 }
 
+// device buffer of a handle: grown on demand, freed with the handle (ppm_reference_destroy / ppm_accum_destroy list no buffers)
 template <typename T>
 struct DevBuf {
     T *p = nullptr; size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
     int ensure(size_t n) {
         if (n <= cap) return 0;
         if (p) (void)hipFree(p);
@@ -154,8 +159,17 @@ struct DevBuf {
         cap = n;
         return 0;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
+
+// a kernel's limit of dynamic LDS, raised ahead of its first launch: one hipFuncSetAttribute per kernel and process, whoever launches it
+int raise_lds_limit(const void *fn, int bytes) {
+    static std::vector<const void *> raised;
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (std::find(raised.begin(), raised.end(), fn) != raised.end()) return 0;
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    raised.push_back(fn);
+    return 0;
+}
 
 // device temporary freed on every exit path (error returns included)
 template <typename T>
@@ -171,14 +185,20 @@ struct DevTmp {
 
 }  // namespace
 
+// The per-chunk workspaces the local stage of ppm_refine_batch reads, as a set.  A handle has two: every chunk of a serial call takes
+// lane[0]; when the call runs the local stage of a chunk beside the search of the next (ppm_overlap.h), chunks of odd index take lane[1],
+// which the first such call allocates (ensure_lane, host_refine.h).
+struct Lane { DevBuf<double> rows_in, rows_out; DevBuf<float> wring, cw, ddef; DevBuf<float2> Il; DevBuf<Hit> hits; DevBuf<LState> states, states2; };
+
 struct ppm_ref {
     hipStream_t stream = nullptr, copy = nullptr;       // this handle's compute and copy streams (StreamScope)
     hipStream_t local = nullptr;                        // second compute stream: the local stage of chunk i beside the search of chunk i + 1 (made on first use)
     int N = 0, B = 0, CX = 0, CY = 0, NBX = 0, NBY = 0, pad = 1; unsigned LB = 0;   // B, CX, CY count samples of the padded transform
     float2 *cube = nullptr;
     // workspaces (grown on demand, reused across calls)
-    DevBuf<double> rows_in, rows_out, dir_theta, dir_phi;
-    DevBuf<float> images, wring, cw, C2, nP, nI, cc, mats, ddef;
+    Lane lane[2];
+    DevBuf<double> dir_theta, dir_phi;
+    DevBuf<float> images, C2, nP, nI, cc, mats;
     // constrained search (ppm_csp_refine)
     DevBuf<float2> c_Il, c_band; DevBuf<float> c_cw, c_img, c_wring; DevBuf<double> c_rows, c_N, c_p, c_tl, c_delta, c_s0, c_g0, c_out;
     DevBuf<int> c_eval, c_rp, c_rt, c_slot, c_uoff, c_active; DevBuf<LState> c_states; DevBuf<double> c_mean, c_tmean, c_acc, c_dtrial, c_fpm, c_delta_t;
@@ -191,18 +211,14 @@ struct ppm_ref {
     DevBuf<float2> s_f, s_g, s_F; DevBuf<float> s_vols;
     // the band's sample list (built and sorted on the host: ~25 ms at 192^3 / 452 k samples) is kept while the band-pass settings stay
     struct { bool valid = false; float key[5] = { 0, 0, 0, 0, 0 }; int S = 0; std::vector<int> shell_off; DevBuf<uint32_t> samples, pos; DevBuf<float> bandw; DevBuf<float2> Fw; bool fw_valid = false; float wkey[4] = { 0, 0, 0, 0 }; } s_plan;    // Fw: the window's transform at the samples
-    DevBuf<float2> band, Il, Wp, bank, twN;
+    DevBuf<float2> band, Wp, bank, twN;
     DevBuf<float2> spill;            // k_prep outside the scratch-free path: the half spectrum between the row and the column phase, [n][N][W]
     DevBuf<float4> rowtw;            // k_global's row-pair twiddles for this reference's current search grid
     DevBuf<int> sh;
     DevBuf<uint32_t> samples;
-    DevBuf<Hit> hits, hits_t;        // hits_t: per-tile top-K lists of a shift window wider than the kernel's
+    DevBuf<Hit> hits_t;              // per-tile top-K lists of a shift window wider than the kernel's
     DevBuf<int> tile_c;
     DevBuf<Hit> hits_s; DevBuf<int> sec_k;      // grid search in sections: the sections' top-K lists of a chunk and the offsets of the lists
-    DevBuf<LState> states, states2;
-    // the second set of the per-chunk workspaces the local stage reads: chunks of odd index take it when ppm_refine_batch overlaps the
-    // local stage of a chunk with the search of the next (ppm_overlap.h); allocated by the first call that does
-    struct Lane { DevBuf<double> rows_in, rows_out; DevBuf<float> wring, cw, ddef; DevBuf<float2> Il; DevBuf<Hit> hits; DevBuf<LState> states, states2; } alt;
     // full-window correlation (k_gfft): the bank in the column pass's layout, window maxima per (particle, orientation), column penalties
     DevBuf<float4> bank4; DevBuf<float> part, gtw;       // gtw: twiddle tables of the search grid (butterfly table, line table), then the window's column penalties
     std::string grid_key, bank_key, bank4_key; int gtw_ns = 0, gtw_rsx = -1;     // what mats / dir_* / twN / rowtw and the two banks hold (grid; grid + section)

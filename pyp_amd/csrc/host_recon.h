@@ -63,8 +63,8 @@ size_t ppm_accum_floats(int box) { return (size_t)2 * box * box * (box / 2 + 1) 
 ppm_accum_t *ppm_accum_create(int box, float pixel_size, const char *symmetry, void *ext) {
     if (!g.inited) { fail(-1, "ppm_init has not been called"); return nullptr; }
     if (!box_ok(box) || !(pixel_size > 0)) { fail(-22, "box must be even, 32..512, with prime factors 2, 3, 5, 7, and the pixel size positive"); return nullptr; }
-    std::unique_ptr<ppm_accum, void (*)(ppm_accum_t *)> guard(new ppm_accum(), ppm_accum_destroy);      // freed on every error return
-    ppm_accum *a = guard.get();
+    struct Undo { ppm_accum *p; ~Undo() { ppm_accum_destroy(p); } } guard{ new ppm_accum() };          // freed on every error return
+    ppm_accum *a = guard.p;
     HIPCHKP(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));
     HIPCHKP(hipStreamCreateWithFlags(&a->copy, hipStreamNonBlocking));
     a->N = box; a->pixel = pixel_size;
@@ -82,19 +82,17 @@ ppm_accum_t *ppm_accum_create(int box, float pixel_size, const char *symmetry, v
     HIPCHKP(hipMalloc(&a->d_counts, 2 * sizeof(unsigned long long)));
     HIPCHKP(hipMemset(a->d_counts, 0, 2 * sizeof(unsigned long long)));
     HIPCHKP(hipMalloc(&a->d_max, 2 * sizeof(unsigned)));
-    static bool attr_set = false;
-    std::lock_guard<std::mutex> lk_attr(g_mu);
-    if (!attr_set) { HIPCHKP(hipFuncSetAttribute((const void *)k_insert_bricks<16, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 17 * (17 * 52 + 3) * 8)); attr_set = true; }
-    return guard.release();
+    if (raise_lds_limit((const void *)k_insert_bricks<16, 16>, 17 * (17 * 52 + 3) * 8)) return nullptr;
+    return std::exchange(guard.p, nullptr);
 }
 
+// the workspaces (DevBuf) go with `delete`, after the streams: see ppm_reference_destroy
 void ppm_accum_destroy(ppm_accum_t *a) {
     if (!a) return;
     if (a->acc && !a->external) (void)hipFree(a->acc);
     if (a->d_sym) (void)hipFree(a->d_sym);
     if (a->d_counts) (void)hipFree(a->d_counts);
     if (a->d_max) (void)hipFree(a->d_max);
-    a->rows.release(); a->images.release(); a->dose.release(); a->band.release(); a->spill.release(); a->s_f.release(); a->s_g.release(); a->s_vols.release(); a->pp.release(); a->cull.release(); a->items.release();
     if (a->stream) (void)hipStreamDestroy(a->stream);
     if (a->copy) (void)hipStreamDestroy(a->copy);
     delete a;

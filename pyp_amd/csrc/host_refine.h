@@ -36,14 +36,7 @@ static int launch_prep(DevBuf<float2> &spill /* the calling handle's scratch */,
         if (int rc = spill.ensure((size_t)n_img * gm.N * gm.W)) return rc;
         P.spill = spill.p;
     }
-    static bool attr_set = false;
-    std::unique_lock<std::mutex> lk_attr(g_mu);
-    if (!attr_set) {
-        HIPCHK(hipFuncSetAttribute((const void *)k_prep<512, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHK(hipFuncSetAttribute((const void *)k_prep<256, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-        attr_set = true;
-    }
-    lk_attr.unlock();
+    if (int rc = pl.scratch_free ? raise_lds_limit((const void *)k_prep<512, 2>, 160 * 1024) : raise_lds_limit((const void *)k_prep<256, 3>, 80 * 1024)) return rc;
     ProfScope ps(PPM_K_PREP);
     if (pl.scratch_free) hipLaunchKernelGGL((k_prep<512, 2>), dim3(n_img), dim3(512), pl.lds.total, cur_stream(), P);
     else hipLaunchKernelGGL((k_prep<256, 3>), dim3(n_img), dim3(256), pl.lds.total, cur_stream(), P);
@@ -51,32 +44,17 @@ static int launch_prep(DevBuf<float2> &spill /* the calling handle's scratch */,
     return 0;
 }
 
-template <int R, bool HALF, bool TWO>
-static int launch_global_k(const GlobP &P, int n_img, size_t lds) {
-    static bool set = false;
-    { std::lock_guard<std::mutex> lk_attr(g_mu); if (!set) { HIPCHK(hipFuncSetAttribute((const void *)k_global<R, HALF, TWO>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } }
-    // resident grid: every block takes most of a CU's LDS, so a CU holds one; the blocks walk the particle groups in strides of the grid
-    const int ngroups = (n_img + global_particles(R) - 1) / global_particles(R);
-    hipLaunchKernelGGL((k_global<R, HALF, TWO>), dim3(std::min(ngroups, g.cu_count)), dim3(global_threads(R)), lds, cur_stream(), P);
-    HIPCHK(hipGetLastError());
-    return 0;
+// The k_global instantiation for a shift window of R steps either side (1 .. 6; anything else takes 6: wider windows go to k_gfft, or to
+// tiles of this one), one or both halves of psi, and a search band of Bs: launch_global runs this pointer and ppm_overlap.h reads
+// its registers and LDS
+template <int... I>
+static const void *global_kernel_at(int i, std::integer_sequence<int, I...>) {
+    static const void *const fn[] = { (const void *)k_global<I / 4 + 1, (I & 2) != 0, (I & 1) != 0>... };
+    return fn[i];
 }
-template <int R>
-static const void *global_kernel_r(bool half, bool two) {
-    if (two) return half ? (const void *)k_global<R, true, true> : (const void *)k_global<R, false, true>;
-    return half ? (const void *)k_global<R, true, false> : (const void *)k_global<R, false, false>;
-}
-// the instantiation launch_global runs for a window of R steps (ppm_overlap.h reads its registers and LDS)
 static const void *global_kernel(int R, bool half, int Bs) {
-    const bool two = Bs <= 31;
-    switch (R) {
-        case 1: return global_kernel_r<1>(half, two);
-        case 2: return global_kernel_r<2>(half, two);
-        case 3: return global_kernel_r<3>(half, two);
-        case 4: return global_kernel_r<4>(half, two);
-        case 5: return global_kernel_r<5>(half, two);
-        default: return global_kernel_r<6>(half, two);
-    }
+    const bool two = Bs <= 31;          // search bands of at most 32 pixels: two slices per wave (k_global<.., TWO>)
+    return global_kernel_at(((R >= 1 && R <= 5 ? R : 6) - 1) * 4 + (half ? 2 : 0) + (two ? 1 : 0), std::make_integer_sequence<int, 24>());
 }
 // dynamic LDS of a k_global launch: the W tables of a block's particles, or the top-K pass's copy of a particle's scores when that is larger
 static size_t global_lds_bytes(int HsP, int n_orient, int R, int *topk_lds) {
@@ -90,25 +68,17 @@ static size_t global_lds_bytes(int HsP, int n_orient, int R, int *topk_lds) {
     if (fits && lds_topk > lds) lds = lds_topk;
     return lds;
 }
-template <int R>
-static int launch_global_r(const GlobP &P, int n_img, bool half, size_t lds) {
-    const bool two = P.Bs <= 31;        // search bands of at most 32 pixels: two slices per wave (k_global<.., TWO>)
-    if (two) return half ? launch_global_k<R, true, true>(P, n_img, lds) : launch_global_k<R, false, true>(P, n_img, lds);
-    return half ? launch_global_k<R, true, false>(P, n_img, lds) : launch_global_k<R, false, false>(P, n_img, lds);
-}
-
 static int launch_global(GlobP &P, int n_img, bool half, int R) {
     P.n = n_img;
     const size_t lds = global_lds_bytes(P.HsP, P.n_orient, R, &P.topk_lds);
+    const void *fn = global_kernel(R, half, P.Bs);
+    if (int rc = raise_lds_limit(fn, 160 * 1024)) return rc;
     ProfScope ps(PPM_K_GLOBAL);
-    switch (R) {
-        case 1: return launch_global_r<1>(P, n_img, half, lds);
-        case 2: return launch_global_r<2>(P, n_img, half, lds);
-        case 3: return launch_global_r<3>(P, n_img, half, lds);
-        case 4: return launch_global_r<4>(P, n_img, half, lds);
-        case 5: return launch_global_r<5>(P, n_img, half, lds);
-        default: return launch_global_r<6>(P, n_img, half, lds);      // wider windows: k_gfft, or tiles of this one (ppm_refine_batch)
-    }
+    // resident grid: every block takes most of a CU's LDS, so a CU holds one; the blocks walk the particle groups in strides of the grid
+    const int ngroups = (n_img + global_particles(R) - 1) / global_particles(R);
+    void *args[] = { &P };
+    HIPCHK(hipLaunchKernel(fn, dim3(std::min(ngroups, g.cu_count)), dim3(global_threads(R)), args, lds, cur_stream()));
+    return 0;
 }
 
 // Full-window correlation (ppm_gfft.h): LDS plan and launch.  Returns -1 when the search grid is outside what the kernel is built
@@ -139,12 +109,19 @@ static void gfft_plan_topk(GfftPlan &pl, int n_orient) {
     else if (pl.fixed + topk <= (size_t)160 * 1024) { pl.topk_lds = 1; pl.t_bytes = (topk + 15) & ~(size_t)15; }
     pl.lds = pl.fixed + pl.t_bytes;
 }
-template <int LN, bool CHUNKED>
-static int launch_gfft_k(const GfftP &P, int n_img, size_t lds) {
-    static bool set = false;
-    { std::lock_guard<std::mutex> lk_attr(g_mu); if (!set) { HIPCHK(hipFuncSetAttribute((const void *)k_gfft<LN, CHUNKED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } }
-    hipLaunchKernelGGL((k_gfft<LN, CHUNKED>), dim3(n_img), dim3(256), lds, cur_stream(), P);
-    HIPCHK(hipGetLastError());
+// the k_gfft instantiation for a search grid of 2^LN points (4 .. 7, gfft_plan), its shift rows in one piece or in chunks
+static const void *gfft_kernel(int LN, bool chunked) {
+    static const void *const fn[] = { (const void *)k_gfft<4, false>, (const void *)k_gfft<4, true>, (const void *)k_gfft<5, false>, (const void *)k_gfft<5, true>,
+                                      (const void *)k_gfft<6, false>, (const void *)k_gfft<6, true>, (const void *)k_gfft<7, false>, (const void *)k_gfft<7, true> };
+    return fn[((LN >= 4 && LN <= 6 ? LN : 7) - 4) * 2 + (chunked ? 1 : 0)];
+}
+static int launch_gfft(GfftP &P, int n_img, const GfftPlan &pl) {
+    P.n = n_img; P.RC = pl.RC; P.nchunk = pl.nchunk; P.t_bytes = (int)pl.t_bytes; P.topk_lds = pl.topk_lds;
+    const void *fn = gfft_kernel(pl.LN, pl.nchunk > 1);
+    if (int rc = raise_lds_limit(fn, 160 * 1024)) return rc;
+    ProfScope ps(PPM_K_GLOBAL);
+    void *args[] = { &P };
+    HIPCHK(hipLaunchKernel(fn, dim3(n_img), dim3(256), args, pl.lds, cur_stream()));
 #ifdef PPM_GFFT_STAMPS
     {   // diagnostic build: cycles per phase and wave of blocks 0 .. 3 (ppm_gfft.h)
         float st[4 * 4 * 12];
@@ -160,24 +137,6 @@ static int launch_gfft_k(const GfftP &P, int n_img, size_t lds) {
     }
 #endif
     return 0;
-}
-static int launch_gfft(GfftP &P, int n_img, const GfftPlan &pl) {
-    P.n = n_img; P.RC = pl.RC; P.nchunk = pl.nchunk; P.t_bytes = (int)pl.t_bytes; P.topk_lds = pl.topk_lds;
-    ProfScope ps(PPM_K_GLOBAL);
-    if (pl.nchunk > 1) {
-        switch (pl.LN) {
-            case 4: return launch_gfft_k<4, true>(P, n_img, pl.lds);
-            case 5: return launch_gfft_k<5, true>(P, n_img, pl.lds);
-            case 6: return launch_gfft_k<6, true>(P, n_img, pl.lds);
-            default: return launch_gfft_k<7, true>(P, n_img, pl.lds);
-        }
-    }
-    switch (pl.LN) {
-        case 4: return launch_gfft_k<4, false>(P, n_img, pl.lds);
-        case 5: return launch_gfft_k<5, false>(P, n_img, pl.lds);
-        case 6: return launch_gfft_k<6, false>(P, n_img, pl.lds);
-        default: return launch_gfft_k<7, false>(P, n_img, pl.lds);
-    }
 }
 
 // ------------------------------------------------------------------------------ refine
@@ -197,13 +156,11 @@ static void launch_defocus(const CubeView &cv, const Geom &gm, const uint32_t *s
 }
 
 namespace {
-// the per-chunk workspaces the local stage reads, as one chunk sees them: the handle's own set, or its second one (ppm_ref::alt)
-struct LaneV { double *rows_in, *rows_out; float *wring, *cw, *ddef; float2 *Il; Hit *hits; LState *states, *states2; };
-LaneV lane_view(ppm_ref *ref, int lane) {
-    if (lane) { auto &a = ref->alt; return { a.rows_in.p, a.rows_out.p, a.wring.p, a.cw.p, a.ddef.p, a.Il.p, a.hits.p, a.states.p, a.states2.p }; }
-    return { ref->rows_in.p, ref->rows_out.p, ref->wring.p, ref->cw.p, ref->ddef.p, ref->Il.p, ref->hits.p, ref->states.p, ref->states2.p };
-}
-// what a ppm_refine_batch call works out before its chunk loop, shared by its stages
+// One k_local launch of a call, the same for every chunk: LocalP but for the chunk's pointers (Il, cw, states: launch_local takes them from
+// the chunk's Lane), the threads of a block, the poses per particle (blocks = particles x per_particle) and the in-band samples summed
+// over the launch's score evaluations of one particle
+struct LocalLaunch { LocalP P = {}; int threads = 0, per_particle = 1; double evals = 0; };
+// what a ppm_refine_batch call works out before its chunk loop; the loop's stages read it and write none of it
 struct RefineRun {
     ppm_ref *ref = nullptr; const ppm_refine_cfg *cfg = nullptr;
     Geom gm; SampleList sl; CubeView cv;
@@ -218,14 +175,15 @@ struct RefineRun {
     // ... and the sections of the grid (ppm_sections.h) with the offsets of their hit lists: section s keeps kpre[s + 1] - kpre[s] hits
     std::vector<GridSection> secs; std::vector<int> kpre; int sec_dirs = 0;     // sec_dirs: directions of the largest section
     // local refinement
-    LocalP LP; bool local_tab = false;
+    LocalP base = {}; bool local_tab = false;   // base: what the call's k_local launches share (local_setup)
     double bf = 3.0; bool any_ang = false, any_sh = false;
+    double ha0 = 0, hs0 = 0;            // no grid search: the first compass steps about the rows' own poses
     int ndef = 0;                       // defocus offsets tried on either side of the row's values
     int per_iter = 0; bool cls_on = false;
-    double sample_evals = 0;            // in-band samples summed over all local score evaluations of one particle
+    LocalLaunch hit, fin;               // every hit refined over the search band; one pose per particle (the best hit, or the row's) at the full band
+    double sample_evals = 0;            // in-band samples summed over all k_local score evaluations of one particle
     // the local stage of chunk i on a second stream beside the search of chunk i + 1 (ppm_overlap.h)
     bool overlap = false; int tenants = 0;
-    hipEvent_t ev_pre = nullptr;        // recorded ahead of k_global when set: the other stream's hit stage starts with it, not before it
 
     int ntiles() const { return (int)(cxs.size() * cys.size()); }
     int nsec() const { return (int)secs.size(); }
@@ -373,40 +331,33 @@ static int refine_plan(RefineRun &r, int n_img) {
     return 0;
 }
 
-// per-chunk workspaces of every call
+// per-chunk workspaces of every call that no local stage reads: one set serves both lanes
 static int ensure_chunk_buffers(RefineRun &r, bool images_on_device) {
-    ppm_ref *ref = r.ref; const Geom &gm = r.gm; const int CH = r.CH;
-    const size_t NN = (size_t)gm.N * gm.N, HW = (size_t)gm.H * gm.W;
-    if (int rc = ref->rows_in.ensure((size_t)CH * PPM_NCOL)) return rc;
-    if (int rc = ref->rows_out.ensure((size_t)CH * PPM_NCOL)) return rc;
-    if (!images_on_device) if (int rc = ref->images.ensure((size_t)2 * CH * NN)) return rc;     // double-buffered staging
-    if (int rc = ref->band.ensure((size_t)CH * HW)) return rc;
-    if (int rc = ref->wring.ensure((size_t)CH * (gm.B + 2))) return rc;
-    if (int rc = ref->Il.ensure((size_t)CH * r.S_pad)) return rc;
-    if (int rc = ref->cw.ensure((size_t)CH * r.S_pad)) return rc;
-    if (int rc = ref->states2.ensure(CH)) return rc;
-    return 0;
+    ppm_ref *ref = r.ref; const Geom &gm = r.gm;
+    if (!images_on_device) if (int rc = ref->images.ensure((size_t)2 * r.CH * gm.N * gm.N)) return rc;     // double-buffered staging
+    return ref->band.ensure((size_t)r.CH * gm.H * gm.W);
 }
-// ... and the second set of those the local stage reads, for a call that overlaps it with the next chunk's search
-static int ensure_alt_buffers(RefineRun &r) {
-    ppm_ref *ref = r.ref; const Geom &gm = r.gm; const int CH = r.CH;
-    auto &a = ref->alt;
-    if (int rc = a.rows_in.ensure((size_t)CH * PPM_NCOL)) return rc;
-    if (int rc = a.rows_out.ensure((size_t)CH * PPM_NCOL)) return rc;
-    if (int rc = a.wring.ensure((size_t)CH * (gm.B + 2))) return rc;
-    if (int rc = a.Il.ensure((size_t)CH * r.S_pad)) return rc;
-    if (int rc = a.cw.ensure((size_t)CH * r.S_pad)) return rc;
-    if (int rc = a.hits.ensure((size_t)CH * r.K)) return rc;
-    if (int rc = a.states.ensure((size_t)CH * r.K)) return rc;
-    if (int rc = a.states2.ensure(CH)) return rc;
-    if (r.ndef > 0) if (int rc = a.ddef.ensure(CH)) return rc;
+// ... and one set of those the local stage reads (after local_setup: ndef)
+static int ensure_lane(const RefineRun &r, int i) {
+    Lane &L = r.ref->lane[i]; const size_t CH = r.CH;
+    if (int rc = L.rows_in.ensure(CH * PPM_NCOL)) return rc;
+    if (int rc = L.rows_out.ensure(CH * PPM_NCOL)) return rc;
+    if (int rc = L.wring.ensure(CH * (r.gm.B + 2))) return rc;
+    if (int rc = L.Il.ensure(CH * r.S_pad)) return rc;
+    if (int rc = L.cw.ensure(CH * r.S_pad)) return rc;
+    if (int rc = L.states2.ensure(CH)) return rc;
+    if (r.cfg->global_search) {
+        if (int rc = L.hits.ensure(CH * r.K)) return rc;
+        if (int rc = L.states.ensure(CH * r.K)) return rc;
+    }
+    if (r.ndef > 0) if (int rc = L.ddef.ensure(CH)) return rc;
     return 0;
 }
 
 // k_global's bank of one section of the grid (rebuilt only when the grid, the band or the section changes: a call of one section finds
 // the bank of the call before; with several, every chunk rebuilds every section, and the key keeps the first section of a chunk from
 // taking the last section of the chunk before for its own)
-static int ensure_bank(RefineRun &r, const GridSection &sec) {
+static int ensure_bank(const RefineRun &r, const GridSection &sec) {
     ppm_ref *ref = r.ref; const Geom &gm = r.gm;
     const std::string key = ref->grid_key + "/d" + std::to_string(sec.d0) + "+" + std::to_string(sec.nd);
     if (ref->bank_key == key) return 0;
@@ -424,7 +375,7 @@ static int ensure_bank(RefineRun &r, const GridSection &sec) {
 }
 
 // ... and k_gfft's, in the column pass's layout
-static int ensure_bank4(RefineRun &r, const GridSection &sec) {
+static int ensure_bank4(const RefineRun &r, const GridSection &sec) {
     ppm_ref *ref = r.ref; const Geom &gm = r.gm; const int L = r.gpl.L;
     const std::string key = ref->grid_key + "/d" + std::to_string(sec.d0) + "+" + std::to_string(sec.nd) + "/L" + std::to_string(L);
     if (ref->bank4_key == key) return 0;
@@ -438,10 +389,10 @@ static int ensure_bank4(RefineRun &r, const GridSection &sec) {
     return 0;
 }
 
-// grid search: per-chunk workspaces; twiddles, direction tables and rotation matrices of the whole grid (rebuilt only when the grid /
+// grid search: per-chunk workspaces but the lanes' own; twiddles, direction tables and rotation matrices of the whole grid (rebuilt only when the grid /
 // band changes); the banks' storage, sized for the largest section
 static int ensure_search_tables(RefineRun &r) {
-    ppm_ref *ref = r.ref; const Geom &gm = r.gm; const int CH = r.CH, K = r.K, nslices = r.nslices, HsP = r.HsP;
+    ppm_ref *ref = r.ref; const Geom &gm = r.gm; const int CH = r.CH, nslices = r.nslices, HsP = r.HsP;
     const size_t HS = r.HS(), HSP = (size_t)HsP * 64;
     if (int rc = ref->Wp.ensure((size_t)CH * HS)) return rc;
     if (int rc = ref->C2.ensure((size_t)CH * HS)) return rc;
@@ -449,8 +400,6 @@ static int ensure_search_tables(RefineRun &r) {
     if (int rc = ref->nI.ensure(CH)) return rc;
     if (int rc = ref->cc.ensure((size_t)CH * gm.n_orient)) return rc;
     if (int rc = ref->sh.ensure((size_t)CH * gm.n_orient)) return rc;
-    if (int rc = ref->hits.ensure((size_t)CH * K)) return rc;
-    if (int rc = ref->states.ensure((size_t)CH * K)) return rc;
     {   // a bank that had to grow is empty again
         const size_t cap = ref->bank.cap;
         if (int rc = ref->bank.ensure((size_t)r.sec_dirs * gm.npsi_store * HSP)) return rc;
@@ -538,16 +487,17 @@ static int ensure_gfft_tables(RefineRun &r) {
     return 0;
 }
 
-// LocalP but for its per-launch fields (states, T, nr, schedule): band constants, free parameters, priors, the classification band
+// r.base, LocalP but for its per-launch fields (T, nr, schedule) and the chunk's pointers: band constants, free parameters, priors, the
+// classification band
 static int local_setup(RefineRun &r) {
-    ppm_ref *ref = r.ref; const ppm_refine_cfg *cfg = r.cfg; const Geom &gm = r.gm; LocalP &LP = r.LP;
+    ppm_ref *ref = r.ref; const ppm_refine_cfg *cfg = r.cfg; const Geom &gm = r.gm; LocalP &LP = r.base;
     r.bf = cfg->band_factor == 0 ? 3.0 : cfg->band_factor;
     r.any_ang = cfg->refine_psi || cfg->refine_theta || cfg->refine_phi; r.any_sh = cfg->refine_x || cfg->refine_y;
-    r.sample_evals = 0;
+    r.ha0 = cfg->local_angle_step > 0 ? cfg->local_angle_step : 2.5; r.hs0 = cfg->local_shift_step > 0 ? cfg->local_shift_step : 2.0;
     r.ndef = 0;
     if (cfg->refine_defocus && cfg->defocus_step > 0 && cfg->defocus_range >= cfg->defocus_step)
         r.ndef = std::min((int)std::floor(cfg->defocus_range / cfg->defocus_step + 1e-6), PPM_MAX_DEFOCUS_STEPS);
-    LP.cv = r.cv; LP.samples = ref->samples.p; LP.Il = ref->Il.p; LP.cw = ref->cw.p; LP.S_pad = r.S_pad; LP.nrings = r.nrings; LP.N = gm.N;
+    LP.cv = r.cv; LP.samples = ref->samples.p; LP.S_pad = r.S_pad; LP.nrings = r.nrings; LP.N = gm.N;
     LP.tabR = cube_tab_radius(gm.B, r.cv.scale);        // of the full band: decides between tables and arithmetic; a launch sizes its own (local_shape)
     r.local_tab = local_tables_wanted(LP.tabR);
     LP.rlo2 = (float)(gm.r_lo * gm.r_lo); LP.ring_signed = (float)std::min(gm.ring_signed, 1e30);
@@ -573,14 +523,49 @@ static int local_setup(RefineRun &r) {
     return 0;
 }
 
-// Dynamic LDS of a k_local launch of r.LP (schedule filled) with `threads` per block, whether it takes its tap addresses from LDS tables,
-// and the radius of those.  The choice between tables and arithmetic is that of the full band (the two round differently, so a stage
-// must not change sides with its band); the tables themselves cover the largest marching band of THIS launch — the coordinates its
-// sample-list prefixes reach — so that the one-wave blocks of the hit stage stay small (ppm_overlap.h).  Same entries, fewer of them.
+// `L` with the bands and sample-list prefixes of its L.P.T compass iterations from the steps (ha, hs), halved after each, and the
+// in-band samples of their evaluations
+static LocalLaunch with_schedule(const RefineRun &r, LocalLaunch L, double ha, double hs, double rcap) {
+    for (int t = 0; t < L.P.T; t++) {
+        double rb = march_band(r.bf, r.gm.N, r.Rm_px, ha, hs, r.any_ang, r.any_sh, rcap);
+        L.P.rmax2_it[t] = (float)(rb * rb); L.P.S_it[t] = r.prefix_of(rb);
+        L.evals += (double)L.per_particle * r.per_iter * std::floor(kPi * rb * rb / 2);
+        ha *= 0.5; hs *= 0.5;
+    }
+    return L;
+}
+// Every hit refined over the search band.  One wave per block up to 1 024 samples per sweep (no cross-wave steps, 64-sample granularity:
+// k_local 83.9 -> 80.9 ms per 28 672 particles against two waves, 93.2 with four; CHANGELOG.md, Round 5, "one-wave blocks for the hit
+// stage"), two waves above
+static LocalLaunch hit_launch(const RefineRun &r) {
+    const Geom &gm = r.gm;
+    LocalLaunch L; L.P = r.base; L.per_particle = r.K;
+    L.P.T = r.Tb; L.P.final_rescore = 0; L.P.nr = std::min(r.nrings, (int)std::ceil(gm.r_s) + 1);
+    L = with_schedule(r, L, 0.5 * gm.dstep, gm.step, gm.r_s);
+    L.threads = r.Tb > 0 && L.P.S_it[0] > 1024 ? 128 : 64;
+    return L;
+}
+// one pose per particle for T iterations from the steps (ha, hs), then scored at the full band
+static LocalLaunch full_band_launch(const RefineRun &r, int T, double ha, double hs) {
+    LocalLaunch L; L.P = r.base; L.threads = kFinalThreads;
+    L.P.T = r.cfg->local_refine ? T : 0; L.P.final_rescore = 1; L.P.nr = r.nrings;
+    L = with_schedule(r, L, ha, hs, r.gm.r_hi);
+    L.evals += std::floor(kPi * r.gm.r_hi * r.gm.r_hi / 2);
+    return L;
+}
+// ... the best hit, from the steps the hit stage ended with
+static LocalLaunch final_launch(const RefineRun &r) { return full_band_launch(r, r.Tc, 0.5 * r.gm.dstep / (double)(1 << r.Tb), r.gm.step / (double)(1 << r.Tb)); }
+// ... the row's own pose (no grid search)
+static LocalLaunch rows_launch(const RefineRun &r) { return full_band_launch(r, r.Tb + r.Tc, r.ha0, r.hs0); }
+
+// Dynamic LDS of a k_local launch, whether it takes its tap addresses from LDS tables, and the radius of those.  The choice between tables
+// and arithmetic is that of the full band (the two round differently, so a stage must not change sides with its band); the tables
+// themselves cover the largest marching band of THIS launch — the coordinates its sample-list prefixes reach — so that the one-wave
+// blocks of the hit stage stay small (ppm_overlap.h).  Same entries, fewer of them.
 struct LocalShape { size_t lds; bool tab; int tabR; };
-static LocalShape local_shape(const RefineRun &r, int threads) {
-    const LocalP &LP = r.LP;
-    const size_t ring = ring_lds_bytes8(threads / 64, kMaxCand, LP.nr);
+static LocalShape local_shape(const RefineRun &r, const LocalLaunch &L) {
+    const LocalP &LP = L.P;
+    const size_t ring = ring_lds_bytes8(L.threads / 64, kMaxCand, LP.nr);
     LocalShape s;
     s.tab = r.local_tab && tables_fit_lds(ring, LP.tabR);
     int S = 0;
@@ -590,29 +575,23 @@ static LocalShape local_shape(const RefineRun &r, int threads) {
     s.lds = ring + (s.tab ? cube_tab_bytes(s.tabR) : 0);
     return s;
 }
-static void launch_local(const RefineRun &r, unsigned grid, int threads) {
-    LocalP LP = r.LP;
-    const LocalShape s = local_shape(r, threads);
+// `L` for the nb particles of the chunk in `ln`, their poses in `states`
+static void launch_local(const RefineRun &r, const LocalLaunch &L, const Lane &ln, LState *states, int nb) {
+    LocalP LP = L.P;
+    LP.Il = ln.Il.p; LP.cw = ln.cw.p; LP.states = states;
+    const LocalShape s = local_shape(r, L);
     LP.tabR = s.tabR;
-    if (s.tab) hipLaunchKernelGGL(k_local<true>, dim3(grid), dim3(threads), s.lds, cur_stream(), LP);
-    else hipLaunchKernelGGL(k_local<false>, dim3(grid), dim3(threads), s.lds, cur_stream(), LP);
-}
-
-// bands and sample-list prefixes of T compass iterations from the steps (ha, hs), halved after each; `mult` poses per particle run them
-static void fill_schedule(RefineRun &r, double ha, double hs, int T, double rcap, double mult) {
-    for (int t = 0; t < T; t++) {
-        double rb = march_band(r.bf, r.gm.N, r.Rm_px, ha, hs, r.any_ang, r.any_sh, rcap);
-        r.LP.rmax2_it[t] = (float)(rb * rb); r.LP.S_it[t] = r.prefix_of(rb);
-        r.sample_evals += mult * r.per_iter * std::floor(kPi * rb * rb / 2);
-        ha *= 0.5; hs *= 0.5;
-    }
+    const dim3 grid((unsigned)(nb * L.per_particle)), block(L.threads);
+    ProfScope ps(PPM_K_LOCAL);
+    if (s.tab) hipLaunchKernelGGL(k_local<true>, grid, block, s.lds, cur_stream(), LP);
+    else hipLaunchKernelGGL(k_local<false>, grid, block, s.lds, cur_stream(), LP);
 }
 
 // one section of the grid for one chunk: the section's banks (built unless they are the ones in place), slice norms -> k_gfft | one
 // k_global tile | tiles + merge -> the section's K best in `hits`.  The per-orientation tables (nP, cc, sh, part) are those of the
 // whole grid: the kernels get pointers to the section's first column and the tables' row lengths, and name the grid's orientations
-// in their hits.
-static int search_section(RefineRun &r, int nb, const GridSection &sec, Hit *hits, int K) {
+// in their hits.  `ev_pre`, when set, is recorded ahead of k_global: the other stream's hit stage starts with it, not before it.
+static int search_section(const RefineRun &r, int nb, const GridSection &sec, Hit *hits, int K, hipEvent_t ev_pre) {
     ppm_ref *ref = r.ref; const Geom &gm = r.gm;
     const int HsP = r.HsP, ntiles = r.ntiles(), nsl = sec.nd * gm.npsi_store, sl0 = sec.d0 * gm.npsi_store, o0 = sec.d0 * gm.n_psi;
     if (int rc = ensure_bank(r, sec)) return rc;
@@ -637,7 +616,7 @@ static int search_section(RefineRun &r, int nb, const GridSection &sec, Hit *hit
         FP.nP_ld = r.nslices; FP.o_ld = gm.n_orient; FP.o_base = o0;
         if (int rc = launch_gfft(FP, nb, r.gpl)) return rc;
     } else if (ntiles == 1) {
-        if (r.ev_pre) HIPCHK(hipEventRecord(r.ev_pre, cur_stream()));
+        if (ev_pre) HIPCHK(hipEventRecord(ev_pre, cur_stream()));
         if (int rc = launch_global(GP, nb, gm.half != 0, r.Rwin)) return rc;
     } else {
         // tiles of the shift window (one section: plan_grid_sections): ramp the search tables to the tile's centre, search, keep the
@@ -665,85 +644,52 @@ static int search_section(RefineRun &r, int nb, const GridSection &sec, Hit *hit
 // grid search of one chunk: the sections of the grid one after another (one section: straight into the chunk's hits; several: every
 // section's K best into its list, then the K best of the lists) -> states from the hits.  `L`: the chunk's set of the workspaces the
 // local stage reads (hits_local_stage, which may run on another stream beside the next chunk's search_stage)
-static int search_stage(RefineRun &r, int nb, const LaneV &L) {
+static int search_stage(const RefineRun &r, int nb, const Lane &L, hipEvent_t ev_pre) {
     ppm_ref *ref = r.ref; const Geom &gm = r.gm;
     const int K = r.K;
     if (r.nsec() == 1) {
-        if (int rc = search_section(r, nb, r.secs[0], L.hits, K)) return rc;
+        if (int rc = search_section(r, nb, r.secs[0], L.hits.p, K, ev_pre)) return rc;
     } else {
         for (int s = 0; s < r.nsec(); s++)
-            if (int rc = search_section(r, nb, r.secs[s], ref->hits_s.p + (size_t)r.kpre[s] * nb, r.kpre[s + 1] - r.kpre[s])) return rc;
+            if (int rc = search_section(r, nb, r.secs[s], ref->hits_s.p + (size_t)r.kpre[s] * nb, r.kpre[s + 1] - r.kpre[s], ev_pre)) return rc;
         ProfScope ps(PPM_K_TOPK);
-        hipLaunchKernelGGL(k_merge_sections, dim3(nb), dim3(64), 0, cur_stream(), ref->hits_s.p, L.hits, nb, K, r.nsec(), ref->sec_k.p);
+        hipLaunchKernelGGL(k_merge_sections, dim3(nb), dim3(64), 0, cur_stream(), ref->hits_s.p, L.hits.p, nb, K, r.nsec(), ref->sec_k.p);
         HIPCHK(hipGetLastError());
     }
     {
         ProfScope ps(PPM_K_TOPK);
-        hipLaunchKernelGGL(k_states_from_hits, dim3((nb * K + 255) / 256), dim3(256), 0, cur_stream(), L.hits, L.states, nb, K,
+        hipLaunchKernelGGL(k_states_from_hits, dim3((nb * K + 255) / 256), dim3(256), 0, cur_stream(), L.hits.p, L.states.p, nb, K,
                            ref->dir_theta.p, ref->dir_phi.p, gm.n_psi, gm.dpsi, gm.step, 0.5 * gm.dstep, gm.step);
     }
     return 0;
 }
 
-// LocalP of the hit stage (every hit refined over the search band) and the threads of its blocks: one wave up to 1 024 samples per sweep
-// (no cross-wave steps, 64-sample granularity: k_local 83.9 -> 80.9 ms per 28 672 particles against two waves, 93.2 with four;
-// CHANGELOG.md, Round 5, "one-wave blocks for the hit stage"), two waves above
-static int hit_stage_setup(RefineRun &r, const LaneV &L) {
-    const Geom &gm = r.gm; LocalP &LP = r.LP;
-    LP.Il = L.Il; LP.cw = L.cw;
-    LP.states = L.states; LP.T = r.Tb; LP.final_rescore = 0;
-    LP.nr = std::min(r.nrings, (int)std::ceil(gm.r_s) + 1);
-    fill_schedule(r, 0.5 * gm.dstep, gm.step, r.Tb, gm.r_s, (double)r.K);
-    return LP.S_it[0] <= 1024 ? 64 : 128;
-}
-
 // the states of one chunk's hits -> refinement of every hit over the search band -> the best hit, refined at the full band into states2
-static int hits_local_stage(RefineRun &r, int nb, const LaneV &L) {
-    const ppm_refine_cfg *cfg = r.cfg; const Geom &gm = r.gm; LocalP &LP = r.LP;
-    const int K = r.K, Tb = r.Tb, Tc = r.Tc;
-    r.sample_evals = 0;
-    if (Tb > 0) {
-        const int threads = hit_stage_setup(r, L);
-        ProfScope ps(PPM_K_LOCAL);
-        launch_local(r, (unsigned)(nb * K), threads);
-    }
+static void hits_local_stage(const RefineRun &r, int nb, const Lane &L) {
+    if (r.Tb > 0) launch_local(r, r.hit, L, L.states.p, nb);
     {
         ProfScope ps(PPM_K_TOPK);
-        hipLaunchKernelGGL(k_select_best, dim3((nb + 255) / 256), dim3(256), 0, cur_stream(), L.states, L.states2, nb, K);
+        hipLaunchKernelGGL(k_select_best, dim3((nb + 255) / 256), dim3(256), 0, cur_stream(), L.states.p, L.states2.p, nb, r.K);
     }
-    LP.Il = L.Il; LP.cw = L.cw;
-    LP.states = L.states2; LP.T = cfg->local_refine ? Tc : 0; LP.final_rescore = 1; LP.nr = r.nrings;
-    fill_schedule(r, 0.5 * gm.dstep / (double)(1 << Tb), gm.step / (double)(1 << Tb), LP.T, gm.r_hi, 1.0);
-    r.sample_evals += std::floor(kPi * gm.r_hi * gm.r_hi / 2);
-    ProfScope ps(PPM_K_LOCAL);
-    launch_local(r, (unsigned)nb, kFinalThreads);
-    return 0;
+    launch_local(r, r.fin, L, L.states2.p, nb);
 }
 
 // no grid search: the rows' own poses, refined at the full band into states2
-static void rows_stage(RefineRun &r, int nb, const LaneV &L) {
-    const ppm_refine_cfg *cfg = r.cfg; const Geom &gm = r.gm; LocalP &LP = r.LP;
-    double ha0 = cfg->local_angle_step > 0 ? cfg->local_angle_step : 2.5, hs0 = cfg->local_shift_step > 0 ? cfg->local_shift_step : 2.0;
-    hipLaunchKernelGGL(k_states_from_rows, dim3((nb + 255) / 256), dim3(256), 0, cur_stream(), L.rows_in, L.states2, nb, gm.a, ha0, hs0);
-    r.sample_evals = 0;
-    LP.Il = L.Il; LP.cw = L.cw;
-    LP.states = L.states2; LP.T = cfg->local_refine ? r.Tb + r.Tc : 0; LP.final_rescore = 1; LP.nr = r.nrings;
-    fill_schedule(r, ha0, hs0, LP.T, gm.r_hi, 1.0);
-    r.sample_evals += std::floor(kPi * gm.r_hi * gm.r_hi / 2);
-    ProfScope ps(PPM_K_LOCAL);
-    launch_local(r, (unsigned)nb, kFinalThreads);
+static void rows_stage(const RefineRun &r, int nb, const Lane &L) {
+    hipLaunchKernelGGL(k_states_from_rows, dim3((nb + 255) / 256), dim3(256), 0, cur_stream(), L.rows_in.p, L.states2.p, nb, r.gm.a, r.ha0, r.hs0);
+    launch_local(r, r.fin, L, L.states2.p, nb);
 }
 
 // defocus offsets at the final pose (states2), then the output rows
-static int finish_chunk(RefineRun &r, int nb, const LaneV &L) {
+static int finish_chunk(const RefineRun &r, int nb, const Lane &L) {
     ppm_ref *ref = r.ref; const Geom &gm = r.gm;
     const float *d_ddef = nullptr;
     if (r.ndef > 0) {
-        launch_defocus(r.cv, gm, ref->samples.p, r.S_pad, L.Il, L.wring, L.rows_in, L.states2, nb, r.ndef, r.cfg->defocus_step,
-                       L.ddef, nullptr, r.cls_on ? (float)(gm.r_cls * gm.r_cls) : 0.f);
-        d_ddef = L.ddef;
+        launch_defocus(r.cv, gm, ref->samples.p, r.S_pad, L.Il.p, L.wring.p, L.rows_in.p, L.states2.p, nb, r.ndef, r.cfg->defocus_step,
+                       L.ddef.p, nullptr, r.cls_on ? (float)(gm.r_cls * gm.r_cls) : 0.f);
+        d_ddef = L.ddef.p;
     }
-    hipLaunchKernelGGL(k_rows_out, dim3((nb + 255) / 256), dim3(256), 0, cur_stream(), L.states2, L.rows_in, L.rows_out, nb, gm.a, gm.r_cls, gm.r_lo, d_ddef);
+    hipLaunchKernelGGL(k_rows_out, dim3((nb + 255) / 256), dim3(256), 0, cur_stream(), L.states2.p, L.rows_in.p, L.rows_out.p, nb, gm.a, gm.r_cls, gm.r_lo, d_ddef);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -760,13 +706,12 @@ static int plan_overlap(RefineRun &r, int n_img) {
     const char *e = std::getenv("PPM_REFINE_OVERLAP");
     c.forced_off = e && std::atoi(e) == 0;
     if (!overlap_on(1, c)) return 0;            // not a call the rule overlaps, whatever fits on a CU
-    const int threads = hit_stage_setup(r, lane_view(ref, 0));
-    const LocalShape ls = local_shape(r, threads);
+    const LocalShape ls = local_shape(r, r.hit);
     hipFuncAttributes ga, la;
     HIPCHK(hipFuncGetAttributes(&ga, global_kernel(r.Rwin, gm.half != 0, gm.Bs)));
     HIPCHK(hipFuncGetAttributes(&la, ls.tab ? (const void *)k_local<true> : (const void *)k_local<false>));
     const OverlapKernel host = { ga.numRegs, global_threads(r.Rwin), (long)ga.sharedSizeBytes + (long)global_lds_bytes(r.HsP, r.secs[0].nd * gm.n_psi, r.Rwin, nullptr) };
-    const OverlapKernel tenant = { la.numRegs, threads, (long)la.sharedSizeBytes + (long)ls.lds };
+    const OverlapKernel tenant = { la.numRegs, r.hit.threads, (long)la.sharedSizeBytes + (long)ls.lds };
     // gfx950 (the only device ppm_init accepts): 512 registers per lane and SIMD handed out in eights, four SIMDs, LDS in blocks of 1 280 bytes
     const OverlapDevice dev = { 512, 4, (long)g.lds_per_cu, 8, 1280 };
     r.tenants = overlap_tenants(host, tenant, dev);
@@ -775,7 +720,7 @@ static int plan_overlap(RefineRun &r, int n_img) {
         fprintf(stderr, "ppm_refine_batch: k_global %d VGPRs / %ld B LDS, hit stage %d threads, %d VGPRs / %ld B LDS: %d blocks per CU beside the search, overlap %s\n",
                 host.vgprs, host.lds_bytes, tenant.threads, tenant.vgprs, tenant.lds_bytes, r.tenants, r.overlap ? "on" : "off");
     if (!r.overlap) return 0;
-    if (int rc = ensure_alt_buffers(r)) return rc;
+    if (int rc = ensure_lane(r, 1)) return rc;
     if (!ref->local) {      // the tenants' stream yields to the search's where the dispatcher has a choice
         int lo = 0, hi = 0;
         HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
@@ -807,18 +752,19 @@ struct OverlapStreams {
 };
 
 // evaluation counts per particle, for the roofline's algorithmic bytes (ppm_refine_last_counts)
-static void refine_counts(RefineRun &r) {
+static void refine_counts(const RefineRun &r) {
     const ppm_refine_cfg *cfg = r.cfg; const Geom &gm = r.gm;
     long nl;
     if (cfg->global_search) nl = (long)r.K * r.Tb * r.per_iter + (cfg->local_refine ? (long)r.Tc * r.per_iter : 0) + 1;
     else nl = 1 + (cfg->local_refine ? (long)(r.Tb + r.Tc) * r.per_iter : 0);
-    r.ref->last_counts[0] = cfg->global_search ? gm.n_orient : 0;
     nl += 2L * r.ndef + (r.cls_on ? 1 : 0);
-    if (r.cls_on) r.sample_evals += std::floor(kPi * gm.r_cls * gm.r_cls / 2);
-    r.sample_evals += 2.0 * r.ndef * std::floor(kPi * gm.r_hi * gm.r_hi / 2);
-    r.ref->last_counts[1] = nl;
-    r.ref->last_counts[2] = (long)std::floor(kPi * gm.r_s * gm.r_s / 2);
-    r.ref->last_counts[3] = (long)r.sample_evals;      // sum over the local evaluations of their in-band sample counts
+    double evals = r.sample_evals + 2.0 * r.ndef * std::floor(kPi * gm.r_hi * gm.r_hi / 2);
+    if (r.cls_on) evals += std::floor(kPi * gm.r_cls * gm.r_cls / 2);
+    long *c = r.ref->last_counts;
+    c[0] = cfg->global_search ? gm.n_orient : 0;
+    c[1] = nl;
+    c[2] = (long)std::floor(kPi * gm.r_s * gm.r_s / 2);
+    c[3] = (long)evals;         // sum over the local evaluations of their in-band sample counts
 }
 
 extern "C" {
@@ -833,8 +779,8 @@ ppm_ref_t *ppm_reference_create_weighted(const float *vol, int n, float max_band
     int B = (int)std::ceil((double)max_band_px * pad) - 1;
     if (B > np / 2 - 1) B = np / 2 - 1;
     size_t n3 = (size_t)n * n * n, np3 = (size_t)np * np * np;
-    std::unique_ptr<ppm_ref, void (*)(ppm_ref_t *)> guard(new ppm_ref(), ppm_reference_destroy);     // freed on every error return
-    ppm_ref *r = guard.get();
+    struct Undo { ppm_ref *p; ~Undo() { ppm_reference_destroy(p); } } guard{ new ppm_ref() };        // freed on every error return
+    ppm_ref *r = guard.p;
     HIPCHKP(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
     HIPCHKP(hipStreamCreateWithFlags(&r->copy, hipStreamNonBlocking));
     StreamScope ss_(r->stream, r->copy);          // the preparation runs on the new handle's own stream: references may be made concurrently
@@ -866,26 +812,19 @@ ppm_ref_t *ppm_reference_create_weighted(const float *vol, int n, float max_band
         hipLaunchKernelGGL(k_ref_crop, dim3((unsigned)((cube_n + 255) / 256)), dim3(256), 0, cur_stream(), d_f, r->cube, np, n, B, r->CX, r->CY, r->NBX, r->NBY, r->LB, d_w, n_weight);
     }
     if (hipStreamSynchronize(cur_stream()) != hipSuccess || hipGetLastError() != hipSuccess) { fail(-5, "reference preparation failed on the device"); return nullptr; }
-    return guard.release();
+    return std::exchange(guard.p, nullptr);
 }
 
 ppm_ref_t *ppm_reference_create_padded(const float *vol, int n, float max_band_px, int pad) { return ppm_reference_create_weighted(vol, n, max_band_px, pad, nullptr, 0); }
 ppm_ref_t *ppm_reference_create(const float *vol, int n, float max_band_px) { return ppm_reference_create_weighted(vol, n, max_band_px, 1, nullptr, 0); }
 
+// The cube is freed by hand; every workspace is a DevBuf and goes with `delete`, AFTER the streams are destroyed (the frees used to come
+// first).  That order is safe: every entry point drains the handle's streams before it returns, so they are idle here; and were work
+// still queued, hipStreamDestroy returns at once and lets it complete, while each hipFree waits for the device before it releases memory.
 void ppm_reference_destroy(ppm_ref_t *r) {
     if (!r) return;
     if (r->cube) (void)hipFree(r->cube);
-    r->rows_in.release(); r->rows_out.release(); r->dir_theta.release(); r->dir_phi.release();
-    r->images.release(); r->wring.release(); r->cw.release(); r->C2.release(); r->nP.release(); r->nI.release();
-    r->s_f.release(); r->s_g.release(); r->s_F.release(); r->s_vols.release(); r->s_plan.samples.release(); r->s_plan.pos.release(); r->s_plan.bandw.release(); r->s_plan.Fw.release();
-    r->c_Il.release(); r->c_band.release(); r->c_cw.release(); r->c_img.release(); r->c_wring.release(); r->c_rows.release(); r->c_N.release(); r->c_p.release(); r->c_tl.release();
-    r->c_delta.release(); r->c_s0.release(); r->c_g0.release(); r->c_out.release(); r->c_eval.release(); r->c_rp.release(); r->c_rt.release(); r->c_slot.release(); r->c_states.release(); r->c_uoff.release(); r->c_mean.release(); r->c_active.release(); r->c_tmean.release(); r->c_acc.release(); r->c_dtrial.release(); r->c_fpm.release(); r->c_delta_t.release(); r->c_rowtab.release(); r->c_gbest.release(); r->c_cscore.release(); r->c_gshift.release(); r->c_cshift.release(); r->c_crot.release(); r->cc.release(); r->mats.release(); r->ddef.release();
-    r->band.release(); r->spill.release(); r->Il.release(); r->Wp.release(); r->bank.release(); r->twN.release(); r->rowtw.release(); r->sh.release(); r->samples.release();
-    r->hits.release(); r->states.release(); r->states2.release();
-    r->alt.rows_in.release(); r->alt.rows_out.release(); r->alt.wring.release(); r->alt.cw.release(); r->alt.ddef.release(); r->alt.Il.release();
-    r->alt.hits.release(); r->alt.states.release(); r->alt.states2.release();
     if (r->local) (void)hipStreamDestroy(r->local);
-    r->hits_t.release(); r->tile_c.release(); r->hits_s.release(); r->sec_k.release(); r->bank4.release(); r->part.release(); r->gtw.release();
     if (r->stream) (void)hipStreamDestroy(r->stream);
     if (r->copy) (void)hipStreamDestroy(r->copy);
     delete r;
@@ -959,8 +898,10 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
     }
     HIPCHK(hipStreamSynchronize(cur_stream()));
     if (int rc = local_setup(r)) return rc;
-
-    if (r.ndef > 0) if (int rc = ref->ddef.ensure(r.CH)) return rc;
+    if (cfg->global_search) { r.hit = hit_launch(r); r.fin = final_launch(r); }
+    else r.fin = rows_launch(r);
+    r.sample_evals = r.hit.evals + r.fin.evals;
+    if (int rc = ensure_lane(r, 0)) return rc;
     if (int rc = plan_overlap(r, n_img)) return rc;
     ref->last_overlap = r.overlap ? r.tenants : 0;
 
@@ -969,33 +910,33 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
     const ChunkStager stage{ (const float *)images, ref->images.p, images_on_device != 0, n_img, CH, NN };
     if (int rc = stage.prime()) return rc;
     // front of a chunk: rows upload, refinement spectra (+ search tables when the same mask serves both), grid search -> the states of the hits
-    auto front = [&](int c0, int ci, int nb, const LaneV &L) -> int {
-        HIPCHK(hipMemcpyAsync(L.rows_in, rows_in + (size_t)c0 * PPM_NCOL, (size_t)nb * PPM_NCOL * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    auto front = [&](int c0, int ci, int nb, const Lane &L, hipEvent_t ev_pre) -> int {
+        HIPCHK(hipMemcpyAsync(L.rows_in.p, rows_in + (size_t)c0 * PPM_NCOL, (size_t)nb * PPM_NCOL * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
         const float *d_img = stage.chunk_ptr(c0, ci);
-        if (int rc = launch_prep(ref->spill, d_img, L.rows_in, nb, gm, r.Rm_px, r.fall_px, cfg->normalize, cfg->invert, 1, 1, ref->band.p, L.wring,
-                                 ref->samples.p, r.S_pad, L.Il, L.cw,
+        if (int rc = launch_prep(ref->spill, d_img, L.rows_in.p, nb, gm, r.Rm_px, r.fall_px, cfg->normalize, cfg->invert, 1, 1, ref->band.p, L.wring.p,
+                                 ref->samples.p, r.S_pad, L.Il.p, L.cw.p,
                                  (cfg->global_search && !r.sep_search) ? ref->Wp.p : nullptr, ref->C2.p, ref->nI.p, nullptr, r.focus_on ? r.focus_px : nullptr)) return rc;
         if (r.sep_search)
-            if (int rc = launch_prep(ref->spill, d_img, L.rows_in, nb, gm, cfg->search_mask_radius / gm.a, r.fall_px, cfg->normalize, cfg->invert, 1, 1,
+            if (int rc = launch_prep(ref->spill, d_img, L.rows_in.p, nb, gm, cfg->search_mask_radius / gm.a, r.fall_px, cfg->normalize, cfg->invert, 1, 1,
                                      ref->band.p, nullptr, nullptr, 0, nullptr, nullptr, ref->Wp.p, ref->C2.p, ref->nI.p)) return rc;
-        if (cfg->global_search) if (int rc = search_stage(r, nb, L)) return rc;
+        if (cfg->global_search) if (int rc = search_stage(r, nb, L, ev_pre)) return rc;
         return 0;
     };
     // back of a chunk: local refinement (of the hits, or of the rows' own poses), defocus, output rows
-    auto back = [&](int nb, const LaneV &L) -> int {
-        if (cfg->global_search) { if (int rc = hits_local_stage(r, nb, L)) return rc; }
+    auto back = [&](int nb, const Lane &L) -> int {
+        if (cfg->global_search) hits_local_stage(r, nb, L);
         else rows_stage(r, nb, L);
         return finish_chunk(r, nb, L);
     };
-    auto download = [&](int c0, int nb, const LaneV &L) -> int {
-        HIPCHK(hipMemcpyAsync(rows_out + (size_t)c0 * PPM_NCOL, L.rows_out, (size_t)nb * PPM_NCOL * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
+    auto download = [&](int c0, int nb, const Lane &L) -> int {
+        HIPCHK(hipMemcpyAsync(rows_out + (size_t)c0 * PPM_NCOL, L.rows_out.p, (size_t)nb * PPM_NCOL * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
         return 0;
     };
     if (!r.overlap) {
-        const LaneV L = lane_view(ref, 0);
+        const Lane &L = ref->lane[0];
         for (int c0 = 0, ci = 0; c0 < n_img; c0 += CH, ci++) {
             const int nb = std::min(CH, n_img - c0);
-            if (int rc = front(c0, ci, nb, L)) return rc;
+            if (int rc = front(c0, ci, nb, L, nullptr)) return rc;
             if (int rc = back(nb, L)) return rc;
             if (int rc = stage.prefetch_next(c0, ci)) return rc;     // next chunk's images travel while this chunk computes
             if (int rc = download(c0, nb, L)) return rc;
@@ -1004,7 +945,7 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
         refine_counts(r);
         return 0;
     }
-    // Software pipeline over two streams and two sets of the workspaces the local stage reads (chunk parity).  This handle's stream (A)
+    // Software pipeline over two streams and the handle's two lanes (chunk parity).  This handle's stream (A)
     // runs the front of chunk i + 1 while the second stream (B) runs the back of chunk i: the hit stage's one-wave blocks move in beside
     // the resident blocks of k_global (ppm_overlap.h), the final stage follows when those have left.  Ordering is by events alone:
     //   A -> B  `ready`: the states of a chunk's hits are written;  `pre`: the next chunk's k_global is next in A's queue (B's hit stage
@@ -1013,24 +954,21 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
     // The host drains A and the copy stream at the end of every chunk as before (the image stager's double buffer) and B at the end.
     OverlapStreams os;
     if (int rc = os.open(ref)) return rc;
-    const LaneV lanes[2] = { lane_view(ref, 0), lane_view(ref, 1) };
     int prev_c0 = 0, prev_nb = 0;
     for (int c0 = 0, ci = 0; ; c0 += CH, ci++) {
         const bool more = c0 < n_img;
         const int lane = ci & 1, nb = more ? std::min(CH, n_img - c0) : 0;
         if (more) {
             if (ci >= 2) HIPCHK(hipStreamWaitEvent(cur_stream(), os.done[lane], 0));
-            r.ev_pre = os.pre[lane];
-            if (int rc = front(c0, ci, nb, lanes[lane])) return rc;
-            r.ev_pre = nullptr;
+            if (int rc = front(c0, ci, nb, ref->lane[lane], os.pre[lane])) return rc;
             HIPCHK(hipEventRecord(os.ready[lane], cur_stream()));
         }
         if (ci >= 1) {
             StreamScope sb(ref->local, ref->copy);
             HIPCHK(hipStreamWaitEvent(cur_stream(), os.ready[lane ^ 1], 0));
             if (more) HIPCHK(hipStreamWaitEvent(cur_stream(), os.pre[lane], 0));
-            if (int rc = back(prev_nb, lanes[lane ^ 1])) return rc;
-            if (int rc = download(prev_c0, prev_nb, lanes[lane ^ 1])) return rc;
+            if (int rc = back(prev_nb, ref->lane[lane ^ 1])) return rc;
+            if (int rc = download(prev_c0, prev_nb, ref->lane[lane ^ 1])) return rc;
             HIPCHK(hipEventRecord(os.done[lane ^ 1], cur_stream()));
         }
         if (!more) break;

@@ -2,7 +2,8 @@
 per-chunk workspaces, events between the streams; pyp_amd/csrc/ppm_overlap.h holds the rule for when).  It moves work in time and
 removes none, so the output rows must equal those of the serial order (PPM_REFINE_OVERLAP=0) in every bit: both parities of the
 workspace sets reused, a last chunk of one particle, fewer particle pairs than CUs and more than twice as many, calls the rule keeps
-serial, and a second call that meets used workspace sets.  Box 64, the parity suite's synthetic set-up.  Run on the GPU box: pytest -m gpu"""
+serial, and a second call that meets used workspace sets.  The evaluation counts of a call (last_counts, which the benchmark's roofline
+reads) come from its plan, so they do not depend on the order or on the chunking either.  Box 64, the parity suite's synthetic set-up.  Run on the GPU box: pytest -m gpu"""
 import numpy as np
 import pytest
 
@@ -23,9 +24,14 @@ def cfg_for(**kw):
 
 
 @pytest.fixture(scope="module")
-def data():
+def dataset():
+    return synth.make_dataset(N, M, pixel=PX, snr=0.1)
+
+
+@pytest.fixture(scope="module")
+def data(dataset):
     from pyp_amd import host
-    vol, stack, rows = synth.make_dataset(N, M, pixel=PX, snr=0.1)
+    vol, stack, rows = dataset
     return stack.numpy(), rows, host.Reference(vol, N / 2)
 
 
@@ -45,11 +51,15 @@ def test_rows_equal_the_serial_order(data, monkeypatch, n, chunk):
     imgs, rows, ref = data
     cfg = cfg_for()
     want, off = run(monkeypatch, ref, cfg, imgs[:n], rows[:n], chunk, False)
+    counts_serial = ref.last_counts()
     got, on = run(monkeypatch, ref, cfg, imgs[:n], rows[:n], chunk, True)
+    counts_overlapped = ref.last_counts()
     assert off == 0 and on >= 1                                    # the second call did overlap
     assert np.array_equal(want, got)
     one, _ = run(monkeypatch, ref, cfg, imgs[:n], rows[:n], n, True)          # one chunk: serial by the rule, and chunking changes nothing
     assert ref.last_overlap() == 0 and np.array_equal(want, one)
+    print("last_counts: serial", counts_serial, "overlapped", counts_overlapped, "one chunk", ref.last_counts())
+    assert counts_serial == counts_overlapped == ref.last_counts()             # the counts are the plan's, not the last chunk's
 
 
 def test_more_particle_pairs_than_twice_the_cus(data, monkeypatch):
@@ -77,8 +87,11 @@ def test_calls_the_rule_keeps_serial(data, monkeypatch, path, kw):
         monkeypatch.setenv("PPM_GLOBAL_PATH", path)
     cfg = cfg_for(**kw)
     want, off = run(monkeypatch, ref, cfg, imgs[:12], rows[:12], 12, False)
+    counts_one = ref.last_counts()
     got, on = run(monkeypatch, ref, cfg, imgs[:12], rows[:12], 5, True)       # three chunks, and still one stream
     assert off == 0 and on == 0 and np.array_equal(want, got)
+    print("last_counts: one chunk", counts_one, "three chunks", ref.last_counts())
+    assert counts_one == ref.last_counts()
 
 
 def test_second_call_meets_used_workspace_sets(data, monkeypatch):
@@ -90,3 +103,19 @@ def test_second_call_meets_used_workspace_sets(data, monkeypatch):
     want_b, _ = run(monkeypatch, ref, cfg, imgs[3:20], rows[3:20], 8, False)
     want_a, _ = run(monkeypatch, ref, cfg, imgs[:24], rows[:24], 8, False)
     assert np.array_equal(a, want_a) and np.array_equal(b, want_b)
+
+
+def test_handle_teardown_after_both_lanes(dataset, data, monkeypatch):
+    """A second handle that has allocated both workspace sets (an overlapped call) and run a call without a grid search is closed: its
+    buffers go with it, and the first handle computes what it computed before."""
+    from pyp_amd import host
+    imgs, rows, ref = data
+    cfg = cfg_for()
+    want, _ = run(monkeypatch, ref, cfg, imgs[:24], rows[:24], 8, False)
+    other = host.Reference(dataset[0], N / 2)
+    _, on = run(monkeypatch, other, cfg, imgs[:24], rows[:24], 8, True)
+    assert on >= 1
+    run(monkeypatch, other, cfg_for(global_search=0), imgs[:24], rows[:24], 8, True)
+    other.close()
+    again, _ = run(monkeypatch, ref, cfg, imgs[:24], rows[:24], 8, False)
+    assert np.array_equal(want, again)
