@@ -417,6 +417,24 @@ typedef struct ppm_mask_cfg { double pixel_size; int edge_width; double outside_
                               int filter; double filter_radius_A; double filter_edge_px; } ppm_mask_cfg;
 int ppm_mask_volume(const void *map, const void *mask, int on_device, int n, const ppm_mask_cfg *cfg, void *out);
 
+/* Binary mask of a map's largest body: the work of frealignx/create_mask, which PYP's masking block runs on the reference before
+ * apply_mask.exe (src/pyp/inout/image/core.py:1538-1605, answers in the order of :1548-1555).  Build-defined (the binary is absent
+ * from the reference checkout), with c = n / 2 (integer division):
+ *   sphere = voxels with integer (x - c)^2 + (y - c)^2 + (z - c)^2 <= (outer_radius_A / pixel_size)^2, the right side in double
+ *   L      = map (lowpass_A 0), or the map low-passed in Fourier space: the cosine-edge filter of ppm_mask_volume around
+ *            r_c = n pixel_size / lowpass_A Fourier pixels, lowpass_edge_px wide
+ *   B0     = sphere and {L >= threshold}, compared in float32; an empty B0 returns -22 and the message holds min / max of L over the sphere
+ *   C      = the connected body of B0 under 26-connectivity (faces, edges, corners; no wrap-around) with the most voxels; among equals
+ *            the one that holds the smallest linear index (z n + y) n + x
+ *   mask   = C (lowpass_A 0), or sphere and {low-passed indicator of C >= rebin}, compared in float32; no second labelling
+ * map, mask_out: n^3 floats, x fastest; on_device != 0: both are device pointers; mask_out may equal map; every value written is 0 or 1,
+ * and nothing is written when the call is refused.  n: 8..512; lowpass_A != 0 needs a box the transforms take (even, 32..512, prime
+ * factors 2, 3, 5, 7) and rebin strictly inside 0..1; pixel_size, outer_radius_A > 0; lowpass_A, lowpass_edge_px >= 0.  Anything else
+ * returns -22.  info (may be null): range of L over the sphere, voxels of B0, its bodies, voxels of C, voxels of the mask. */
+typedef struct ppm_create_mask_cfg { double pixel_size, outer_radius_A, threshold, lowpass_A, lowpass_edge_px, rebin; } ppm_create_mask_cfg;
+typedef struct ppm_create_mask_info { double density_min, density_max; long above, components, largest, mask_voxels; } ppm_create_mask_info;
+int ppm_create_mask(const void *map, int on_device, int n, const ppm_create_mask_cfg *cfg, void *mask_out, ppm_create_mask_info *info);
+
 /* Particle extraction straight into a (resident) stack — the step before the path:
  * crop `box` x `box` windows around the picked coordinates, fill what falls outside the micrograph with the mean
  * of the inside part, replace empty boxes by white noise, subtract the background mean and divide by the background

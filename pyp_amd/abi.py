@@ -140,3 +140,27 @@ class MaskCfg(C.Structure):
         filter: low-pass of that density (0 = none, 2 = cosine edge at filter_radius_A Angstrom, filter_edge_px Fourier pixels wide)."""
         return cls(pixel_size=float(pixel_size), edge_width=int(edge_width), outside_weight=float(outside_weight), filter=int(filter),
                    filter_radius_A=float(filter_radius_A), filter_edge_px=float(filter_edge_px))
+
+
+class CreateMaskCfg(C.Structure):
+    """ppm_create_mask_cfg (include/ppm.h)."""
+    _fields_ = [("pixel_size", C.c_double), ("outer_radius_A", C.c_double), ("threshold", C.c_double), ("lowpass_A", C.c_double),
+                ("lowpass_edge_px", C.c_double), ("rebin", C.c_double)]
+
+    @classmethod
+    def make(cls, pixel_size, outer_radius_A, threshold, lowpass_A=0.0, lowpass_edge_px=4.0, rebin=0.35):
+        """outer_radius_A: sphere outside of which nothing is kept; threshold: density at or above which a voxel counts; lowpass_A: the
+        map is low-passed to this resolution first and the largest body once more afterwards (0 = neither); lowpass_edge_px: width of
+        the filter's cosine edge in Fourier pixels; rebin: level at which the low-passed body becomes the mask (strictly inside 0..1)."""
+        return cls(pixel_size=float(pixel_size), outer_radius_A=float(outer_radius_A), threshold=float(threshold), lowpass_A=float(lowpass_A),
+                   lowpass_edge_px=float(lowpass_edge_px), rebin=float(rebin))
+
+
+class CreateMaskInfo(C.Structure):
+    """ppm_create_mask_info (include/ppm.h): range of the (low-passed) density inside the sphere, voxels at or above the threshold there,
+    their connected bodies, voxels of the largest, voxels of the mask."""
+    _fields_ = [("density_min", C.c_double), ("density_max", C.c_double), ("above", C.c_long), ("components", C.c_long),
+                ("largest", C.c_long), ("mask_voxels", C.c_long)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}

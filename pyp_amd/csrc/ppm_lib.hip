@@ -30,6 +30,7 @@
 #include "ppm_sva_kernels.h"
 #include "ppm_gfft.h"
 #include "ppm_mask_kernels.h"
+#include "ppm_label_kernels.h"
 
 using namespace ppm;
 
@@ -39,3 +40,4 @@ using namespace ppm;
 #include "host_csp.h"
 #include "host_sva.h"
 #include "host_mask.h"
+#include "host_label.h"

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import lib
-from .abi import NCOL, STATS_COLS, K_NAMES, FinalCfg, MaskCfg, ReconCfg, RefineCfg  # noqa: F401
+from .abi import NCOL, STATS_COLS, K_NAMES, CreateMaskCfg, CreateMaskInfo, FinalCfg, MaskCfg, ReconCfg, RefineCfg  # noqa: F401
 
 
 def _sync_producer(t):
@@ -340,6 +340,38 @@ def mask_volume(vol, mask, cfg, out=None, device=0):
         pv, pm, po = lib.ptr(vol), lib.ptr(mask), lib.ptr(res)
     lib.check(lib.load().ppm_mask_volume(pv, pm, 1 if on_dev else 0, n, C.byref(cfg), po))
     return res
+
+
+def create_mask(vol, cfg, out=None, device=0):
+    """Binary mask of a map's largest body (ppm_create_mask, what frealignx/create_mask does in PYP's masking block): vol = N^3
+    float32, a numpy array or a CUDA torch tensor; cfg: abi.CreateMaskCfg.  Returns (mask, info): the mask is of the kind of `vol`
+    (`out`, same kind and shape, receives it in place of a new array), info an abi.CreateMaskInfo.  A refusal - a threshold no voxel
+    reaches among them - raises lib.PpmError and leaves `out` as it was."""
+    lib.init(device)
+    on_dev = bool(getattr(vol, "is_cuda", False))
+    if out is not None and on_dev != bool(getattr(out, "is_cuda", False)):
+        raise ValueError("ERROR: create_mask: map and out must both be on the host or both on the device")
+    if not on_dev:
+        vol = np.ascontiguousarray(vol.numpy() if hasattr(vol, "numpy") else vol, dtype=np.float32)
+    shape = tuple(int(x) for x in vol.shape)
+    if len(shape) != 3 or len(set(shape)) != 1:
+        raise ValueError("ERROR: create_mask: the map must be a cubic volume")
+    n = shape[0]
+    if on_dev:
+        import torch
+        res = torch.empty_like(vol) if out is None else out
+        if tuple(res.shape) != shape:
+            raise ValueError("ERROR: create_mask: out has the wrong shape")
+        pv, _, _ = _volumes_arg(vol, 1, n)
+        po, _, _ = _volumes_arg(res, 1, n)
+    else:
+        res = np.empty_like(vol) if out is None else out
+        if not isinstance(res, np.ndarray) or res.dtype != np.float32 or res.shape != shape or not res.flags.c_contiguous:
+            raise ValueError("ERROR: create_mask: out must be a contiguous float32 array of the map's shape")
+        pv, po = lib.ptr(vol), lib.ptr(res)
+    info = CreateMaskInfo()
+    lib.check(lib.load().ppm_create_mask(pv, 1 if on_dev else 0, n, C.byref(cfg), po, C.byref(info)))
+    return res, info
 
 
 class PinnedBuffer:

@@ -10,13 +10,19 @@ from .formats.cistem import COL
 
 
 def iteration(vol, stack, rows, refine_cfg, *, pixel_size, molecular_mass_kda, symmetry="C1", keep_fraction=1.0,
-              score_weight_bfactor=0.0, outer_radius=None, split_by_pind=False, mask=None, mask_cfg=None):
+              score_weight_bfactor=0.0, outer_radius=None, split_by_pind=False, mask=None, mask_cfg=None, auto_mask=None):
     """vol: current reference (N^3 float32); stack: [M, N, N] float32 (numpy or a CUDA torch tensor); rows: [M, 32].
     mask (N^3 float32, of the same kind as vol) with mask_cfg (abi.MaskCfg; default: PYP's edge of 3 voxels, weight 0): the
     reference is shape-masked on the device first, as `shape_mask_reference` (align/core.py:783-856) does with apply_mask.exe.
+    auto_mask (abi.CreateMaskCfg) in place of mask: the mask is made from vol itself on the device (host.create_mask, the work of
+    `cistem_mask_create`, inout/image/core.py:1538-1605) and applied with mask_cfg.
     Returns dict(rows=refined table incl. OCC after selection, half1, half2, filtered, stats=[N/2-1, 7] statistics table).
     """
     n = int(refine_cfg.box)
+    if auto_mask is not None:
+        if mask is not None:
+            raise ValueError("ERROR: iteration: auto_mask and mask exclude each other")
+        mask, _ = host.create_mask(vol, auto_mask)
     if mask is not None:
         vol = host.mask_volume(vol, mask, mask_cfg if mask_cfg is not None else MaskCfg.make(pixel_size=pixel_size))
         if getattr(vol, "is_cuda", False):          # map and mask were device tensors: Reference takes a host array

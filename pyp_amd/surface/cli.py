@@ -13,7 +13,7 @@ import time
 
 import numpy as np
 
-from ..abi import FinalCfg, MaskCfg, ReconCfg, RefineCfg
+from ..abi import CreateMaskCfg, FinalCfg, MaskCfg, ReconCfg, RefineCfg
 from ..formats import cistem, mrc, parfile
 from . import prompts
 
@@ -853,4 +853,66 @@ def apply_mask_main(argv=None, stdin=None, backend=None):
     print(f"Timing: inputs {t1 - t0:.2f} s, device {t2 - t1:.2f} s, output {time.time() - t2:.2f} s")
     _release_warm()
     print("\nApplyMask: Normal termination\n", flush=True)
+    return 0
+
+
+# ------------------------------------------------------------------------------------------ create_mask
+def create_mask_main(argv=None, stdin=None, backend=None):
+    """frealignx's create_mask as PYP's masking block runs it (src/pyp/inout/image/core.py:1538-1605): the map is read in full, the mask
+    appears under its name only when complete, with the pixel size of the script in its header (the `alterheader -del` PYP runs next
+    then changes nothing).  A threshold no voxel reaches leaves no file: PYP reads that as "Threshold falls outside range" (:1602).
+    backend: what computes (vol, CreateMaskCfg) -> (mask, info); default host.create_mask on the GPU, under the per-GPU lock."""
+    t0 = time.time()
+    try:
+        d = prompts.parse_create_mask(prompts.read_answers(stdin or sys.stdin))
+    except prompts.PromptError as e:
+        _die(str(e))
+    print("\n        **   Welcome to CreateMask (MI355X / libpypmatch)   **\n")
+    for k, v in d.items():
+        print(f"{k:28s}: {v}")
+    if not os.path.exists(d["input"]):
+        _die(f"ERROR: create_mask: input file {d['input']} does not exist")
+    try:
+        vol = mrc.read(d["input"]).astype(np.float32)
+    except (IOError, ValueError) as e:
+        _die(str(e))
+    if vol.ndim != 3 or len(set(vol.shape)) != 1:
+        _die(f"ERROR: create_mask: the input map is {vol.shape}, only cubic maps are supported")
+    px, n = d["pixel_size"], vol.shape[0]
+    edge = min(prompts.CREATE_MASK_EDGE_PX, 2.0 * n * px / d["lowpass"]) if d["lowpass"] > 0 else 0.0
+    cfg = CreateMaskCfg.make(pixel_size=px, outer_radius_A=d["outer_radius"], threshold=d["threshold"], lowpass_A=d["lowpass"],
+                             lowpass_edge_px=edge, rebin=d["rebin"])
+    t1 = time.time()
+    try:
+        if backend is not None:
+            mask, info = backend(vol, cfg)
+        else:
+            from .. import host, lib
+            dev = int(os.environ.get("PPM_DEVICE", "0"))
+            try:
+                with gpu_lock(dev):
+                    mask, info = host.create_mask(vol, cfg, device=dev)
+            except lib.PpmError as e:
+                _die(str(e))
+    except ValueError as e:
+        _die(str(e))
+    t2 = time.time()
+    tmp = d["output"] + ".tmp%d" % os.getpid()
+    try:
+        mrc.write(np.asarray(mask, dtype=np.float32), tmp, pixel_size=px)
+        os.replace(tmp, d["output"])
+    except OSError as e:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        _die(f"ERROR: create_mask: could not write {d['output']}: {e}")
+    print(f"\nMask of a {n}^3 map at {px:g} A/pixel: outer radius {d['outer_radius']:g} A, threshold {d['threshold']:g}, "
+          f"low-pass {d['lowpass']:g} A (edge {edge:g} Fourier pixels), re-bin value {d['rebin']:g}")
+    print(f"Density inside the radius      : {info.density_min:g} .. {info.density_max:g}")
+    print(f"Voxels above the threshold     : {info.above}")
+    print(f"Connected components           : {info.components}")
+    print(f"Voxels of the largest          : {info.largest}")
+    print(f"Voxels of the mask             : {info.mask_voxels}")
+    print(f"Timing: input {t1 - t0:.2f} s, device {t2 - t1:.2f} s, output {time.time() - t2:.2f} s")
+    _release_warm()
+    print("\nCreateMask: Normal termination\n", flush=True)
     return 0

@@ -2,7 +2,8 @@
 
 The caller never parses prompts; it pipes a here-doc of answers, one per line, `yes`/`no` for
 booleans (src/pyp/refine/frealign/frealign.py:3918-3994 refine3d, :1780-1824 reconstruct3d,
-:1878-1888 local_merge3d, :2075-2093 merge3d; src/pyp/align/core.py:811-850 apply_mask.exe; the `.par`-surface refine3d script
+:1878-1888 local_merge3d, :2075-2093 merge3d; src/pyp/align/core.py:811-850 apply_mask.exe; src/pyp/inout/image/core.py:1583-1596
+create_mask; the `.par`-surface refine3d script
 is preserved at src/pyp/system/wrapper_functions.py:512-561).  Answer order: SURVEY.md §9.1-§9.3.
 """
 
@@ -188,6 +189,37 @@ def parse_apply_mask(answers):
         raise PromptError(f"ERROR: {prog}: cosine edge filter radius must be positive, got '{a[7]}'")
     if d["filter"] == 2 and not d["filter_edge"] >= 0:
         raise PromptError(f"ERROR: {prog}: width of the filter edge must not be negative, got '{a[8]}'")
+    return d
+
+
+CREATE_MASK = [("input", str), ("output", str), ("pixel_size", float), ("outer_radius", float), ("auto_threshold", bool),
+               ("threshold", float), ("lowpass", float), ("rebin", float)]
+# The script has no answer for the width of the low-pass edge: this many Fourier pixels, at most 2 r_c
+CREATE_MASK_EDGE_PX = 4.0
+
+
+def parse_create_mask(answers):
+    """create_mask (frealignx), the eight answers in the order of the questions at src/pyp/inout/image/core.py:1548-1555 and of the
+    script at :1583-1596: input map, output mask, pixel size, outer radius in A, auto-estimate the threshold (PYP always sends No),
+    threshold, low-pass resolution in A (0 = none), re-bin value.  Refused here: what can be told from the answers alone (the
+    automatic threshold, ranges ppm_create_mask refuses, include/ppm.h)."""
+    prog = "create_mask"
+    a = list(answers)
+    if len(a) != len(CREATE_MASK):
+        raise PromptError(f"ERROR: {prog}: expected {len(CREATE_MASK)} answers, got {len(a)}")
+    d = _take(a, CREATE_MASK, prog)
+    if d["auto_threshold"]:
+        raise PromptError(f"ERROR: {prog}: the automatic estimate of the binarization threshold is not supported by this build (answer No and give a threshold)")
+    if not d["pixel_size"] > 0:
+        raise PromptError(f"ERROR: {prog}: pixel size must be positive, got '{a[2]}'")
+    if not d["outer_radius"] > 0:
+        raise PromptError(f"ERROR: {prog}: outer radius of the mask must be positive, got '{a[3]}'")
+    if not d["threshold"] == d["threshold"] or d["threshold"] in (float("inf"), float("-inf")):
+        raise PromptError(f"ERROR: {prog}: binarization threshold must be a finite number, got '{a[5]}'")
+    if not d["lowpass"] >= 0:
+        raise PromptError(f"ERROR: {prog}: low-pass filter resolution must not be negative (0 = none), got '{a[6]}'")
+    if d["lowpass"] != 0 and not 0 < d["rebin"] < 1:
+        raise PromptError(f"ERROR: {prog}: re-bin value must lie strictly between 0 and 1, got '{a[7]}'")
     return d
 
 
