@@ -172,8 +172,7 @@ static CspSearch csp_search_plan(const ppm_csp_cfg *cc, int kind, bool any_activ
 static int csp_defocus_sweep(CspRun &c, const CspUnits &U, double *rows) {
     ppm_ref *ref = c.ref; const ppm_csp_cfg *cc = c.cc; const Geom &gm = c.gm; const int n_proj = c.n_proj;
     const double step = cc->defocus_step > 0 ? cc->defocus_step : 50.0;
-    int nt = 0;
-    if (cc->defocus_range >= step) nt = std::min((int)std::floor(cc->defocus_range / step + 1e-6), PPM_MAX_DEFOCUS_STEPS);
+    const int nt = ppm::defocus_steps(cc->defocus_range, step, PPM_MAX_DEFOCUS_STEPS);
     const int Tn = 2 * nt + 1;
     if (int rc = ref->c_states.ensure(n_proj)) return rc;
     if (int rc = ref->c_out.ensure((size_t)n_proj * Tn)) return rc;

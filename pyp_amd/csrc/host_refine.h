@@ -150,7 +150,9 @@ static void launch_defocus(const CubeView &cv, const Geom &gm, const uint32_t *s
     DP.cv = cv; DP.samples = samples; DP.Il = Il; DP.wring = wring; DP.S_pad = S_pad; DP.nrings = nrings; DP.N = gm.N; DP.B = gm.B;
     DP.rlo2 = (float)(gm.r_lo * gm.r_lo); DP.rmax2 = (float)(gm.r_hi * gm.r_hi); DP.ring_signed = (float)std::min(gm.ring_signed, 1e30); DP.a = (float)gm.a;
     DP.rows = rows; DP.states = states; DP.ddef = ddef; DP.nt = nt; DP.step = step; DP.all_scores = all_scores; DP.rcls2 = rcls2;
-    DP.tchunk = std::max(1, std::min(2 * nt + 1, (int)(60000 / (16 * (size_t)nrings))));      // per-wave ring tables of one pass stay below 64 KB
+    long knob = 0;
+    if (const char *e = std::getenv("PPM_DEFOCUS_CHUNK")) knob = std::atol(e);                  // tests: several passes at a small box
+    DP.tchunk = ppm::defocus_chunk(nt, nrings, knob);                                           // per-wave ring tables of one pass stay below 64 KB
     ProfScope ps(PPM_K_LOCAL);
     hipLaunchKernelGGL(k_defocus, dim3(n), dim3(256), ring_lds_bytes(4, DP.tchunk, nrings), cur_stream(), DP);
 }
@@ -494,9 +496,7 @@ static int local_setup(RefineRun &r) {
     r.bf = cfg->band_factor == 0 ? 3.0 : cfg->band_factor;
     r.any_ang = cfg->refine_psi || cfg->refine_theta || cfg->refine_phi; r.any_sh = cfg->refine_x || cfg->refine_y;
     r.ha0 = cfg->local_angle_step > 0 ? cfg->local_angle_step : 2.5; r.hs0 = cfg->local_shift_step > 0 ? cfg->local_shift_step : 2.0;
-    r.ndef = 0;
-    if (cfg->refine_defocus && cfg->defocus_step > 0 && cfg->defocus_range >= cfg->defocus_step)
-        r.ndef = std::min((int)std::floor(cfg->defocus_range / cfg->defocus_step + 1e-6), PPM_MAX_DEFOCUS_STEPS);
+    r.ndef = cfg->refine_defocus ? ppm::defocus_steps(cfg->defocus_range, cfg->defocus_step, PPM_MAX_DEFOCUS_STEPS) : 0;
     LP.cv = r.cv; LP.samples = ref->samples.p; LP.S_pad = r.S_pad; LP.nrings = r.nrings; LP.N = gm.N;
     LP.tabR = cube_tab_radius(gm.B, r.cv.scale);        // of the full band: decides between tables and arithmetic; a launch sizes its own (local_shape)
     r.local_tab = local_tables_wanted(LP.tabR);

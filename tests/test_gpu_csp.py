@@ -103,6 +103,33 @@ def test_defocus_mode_matches_oracle(series):
     assert np.abs(found - off[1:6]).max() <= 25.0           # the nearest 50 A grid point
 
 
+@pytest.mark.parametrize("rng_,off", [(1000.0, [-1000, -600, -250, 0, 600, 800, 1000]), (850.0, [-850, -500, -200, 0, 750, 800, 850])],
+                         ids=["1000/50", "850/50"])
+def test_defocus_mode_over_the_whole_ladder(series, rng_, off):
+    """csp mode 4 at nt = 20 (T = 41, the cap) and nt = 17 (T = 35): the tilts start at offsets that span the ladder, so the
+    winners include t = 0, T - 1 and indices >= 32, the second trip of k_defocus's final reduction (all_scores path).  Assertions
+    of test_defocus_mode_matches_oracle."""
+    from pyp_amd import host
+    import defocus_cases as D
+    O = series[-1]
+    n, px, vol, imgs, rows, parts, tilts, cfg = defocus_series()
+    g, o = host.Reference(vol, n / 2), O.Reference(vol, n / 2)
+    off = np.array(off, dtype=np.float64)
+    nt = D.csp_steps(rng_, 50.0)
+    assert D.plan(nt, O.band_dims(cfg)["B"] + 2) == (2 * nt + 1, 2 * nt + 1, 1, 2)          # one chunk, two trips of the reduction
+    rows2 = rows.copy()
+    for t in range(len(tilts)):
+        rows2[rows2[:, 27] == t, 6:8] -= off[t]
+    cc = CspCfg.make(CSP_MICROGRAPHS, refine_defocus=1, defocus_range=rng_, defocus_step=50.0)
+    wr, wp, wt, _ = O.csp_refine(o, cfg, cc, imgs, rows2, parts, tilts)
+    won = {int(round((wr[wr[:, 27] == t, 6] - rows2[rows2[:, 27] == t, 6]).mean() / 50.0)) + nt for t in range(len(tilts))}
+    assert {0, nt, 2 * nt} <= won and sum(t >= 32 for t in won) >= 3                         # the oracle's winners span the ladder
+    gr, gp, gt = g.csp_refine(cfg, cc, imgs, rows2, parts, tilts)
+    assert np.array_equal(gr[:, 6:8], wr[:, 6:8])                                            # the same offset for every tilt
+    assert np.abs(gr[:, 14] - wr[:, 14]).max() < 0.02 and np.array_equal(gr[:, 1:6], wr[:, 1:6])
+    assert np.array_equal(gp, parts) and np.array_equal(gt, tilts)
+
+
 def test_csp_errors_are_loud(series):
     from pyp_amd import lib
     n, px, vol, imgs, rows, parts, tilts, cfg, g, o, O = series
