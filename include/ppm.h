@@ -435,6 +435,47 @@ typedef struct ppm_create_mask_cfg { double pixel_size, outer_radius_A, threshol
 typedef struct ppm_create_mask_info { double density_min, density_max; long above, components, largest, mask_voxels; } ppm_create_mask_info;
 int ppm_create_mask(const void *map, int on_device, int n, const ppm_create_mask_cfg *cfg, void *mask_out, ppm_create_mask_info *info);
 
+/* Post-processing of the two half maps of the last iteration: the work of PYP's external/postprocessing/postprocessing.py, which the
+ * Post-processing block starts (src/pyp_main.py:6601-6865, command line at :6638-6737).  Build-defined (the program is absent from the
+ * reference checkout), after Rosenthal & Henderson 2003 and Chen et al. 2013:
+ *   mask     none (1 everywhere), external (as given, clamped to 0..1) or automatic: the largest body of (half1 + half2) / 2 at or above
+ *            a threshold (ppm_create_mask: outer radius n pixel_size / 2, low-pass automask_lp, re-bin 1/2) with a cosine edge of 6 voxels
+ *            (ppm_mask_volume); the threshold is the given value (0), mean + value x standard deviation of the low-passed map over the
+ *            sphere (1), or the ceil(value x voxels of the sphere)-th largest low-passed value there (2)
+ *   curves   per shell s = floor(|k| + 1/2) = 0 .. n/2: FSC of the halves (U), of the masked halves (Mk), of the masked halves whose phases
+ *            were randomised from shell s_r on (Rd), and C = Mk below s_r + 2, (Mk - Rd) / (1 - Rd) from there (0 where 1 - Rd < 1e-6)
+ *   s_r      round(n pixel_size / randomize_value) (method 0), or the first shell >= 1 with U < randomize_value (method 1); 1 .. n/2
+ *   resolution  where C first falls below 0.143, interpolated linearly in frequency; Nyquist if it never does
+ *   filter   W(s) = w(s) exp(-B f^2 / 4) L(s): w = sqrt(2C / (1 + C)) (1 with skip_fsc_weighting, max(C, 0)^2 with apply_fsc2); B none,
+ *            ad hoc, or 4 x the slope of ln(sqrt(P) w) against f^2 over 1/fit_low <= f <= 1/fit_high (fit_high 0: the resolution), P the
+ *            shell mean of |F1 + F2|^2 / 4 of the masked halves; L a cosine edge two shells wide about the low-pass cutoff (lowpass in A,
+ *            0 = none, lowpass_auto: the resolution) and a mirrored one for highpass (<= 0: none), or Gaussians with half amplitude there
+ *   outputs  unmasked = Re IFFT(W FFT((half1 + half2) / 2)), masked = mask x unmasked; flip_x/y/z reverse that axis of both
+ * half1, half2, mask (NULL unless mask_mode 1), unmasked_out, masked_out, mask_out (or NULL): n^3 floats, x fastest; on_device != 0: all
+ * of them are device pointers.  curves: 4 x (n/2 + 1) doubles on the host (U, Mk, Rd, C); shell_count (or NULL): n/2 + 1 longs on the host.
+ * n: a box the transforms take (even, 32..512, prime factors 2, 3, 5, 7).  Refused with -22: any other box, both FSC flags, fewer than
+ * three shells in the B-factor fit, values out of range; nothing is written then.  Two calls on the same data agree bit for bit. */
+typedef struct ppm_post_cfg {
+    double pixel_size;
+    int mask_mode;                  /* 0 none, 1 external, 2 automatic */
+    double automask_lp;             /* A; 0 = no low-pass */
+    int threshold_method;           /* 0 intensity, 1 sigma, 2 volume */
+    double threshold_value;
+    int randomize_method;           /* 0 resolution (A), 1 fsc */
+    double randomize_value;
+    unsigned seed;
+    int bfactor_method;             /* 0 none, 1 ad hoc, 2 automatic */
+    double adhoc_bfac, fit_low, fit_high;
+    int lowpass_auto;
+    double lowpass, highpass;
+    int gaussian, skip_fsc_weighting, apply_fsc2, flip_x, flip_y, flip_z;
+} ppm_post_cfg;
+/* s_r; the first shell with C < 0.143 (0: none); shells of the B-factor fit; complex 3-D transforms run (5 without the automatic mask);
+ * resolution in A; B in A^2; threshold of the automatic mask; voxels of the mask at or above 0.5 (automatic: of its body) */
+typedef struct ppm_post_info { int s_r, res_shell, fit_shells, transforms; double resolution, bfactor, threshold; long mask_voxels; } ppm_post_info;
+int ppm_postprocess(const void *half1, const void *half2, const void *mask, int on_device, int n, const ppm_post_cfg *cfg,
+                    void *unmasked_out, void *masked_out, void *mask_out, double *curves, long *shell_count, ppm_post_info *info);
+
 /* Particle extraction straight into a (resident) stack — the step before the path:
  * crop `box` x `box` windows around the picked coordinates, fill what falls outside the micrograph with the mean
  * of the inside part, replace empty boxes by white noise, subtract the background mean and divide by the background

@@ -164,3 +164,46 @@ class CreateMaskInfo(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PostCfg(C.Structure):
+    """ppm_post_cfg (include/ppm.h)."""
+    MASK = {"none": 0, "external": 1, "auto": 2}
+    THRESHOLD = {"intensity": 0, "sigma": 1, "volume": 2}
+    RANDOMIZE = {"resolution": 0, "fsc": 1}
+    BFACTOR = {"none": 0, "adhoc": 1, "auto": 2}
+    _fields_ = [("pixel_size", C.c_double), ("mask_mode", C.c_int), ("automask_lp", C.c_double), ("threshold_method", C.c_int),
+                ("threshold_value", C.c_double), ("randomize_method", C.c_int), ("randomize_value", C.c_double), ("seed", C.c_uint),
+                ("bfactor_method", C.c_int), ("adhoc_bfac", C.c_double), ("fit_low", C.c_double), ("fit_high", C.c_double),
+                ("lowpass_auto", C.c_int), ("lowpass", C.c_double), ("highpass", C.c_double), ("gaussian", C.c_int),
+                ("skip_fsc_weighting", C.c_int), ("apply_fsc2", C.c_int), ("flip_x", C.c_int), ("flip_y", C.c_int), ("flip_z", C.c_int)]
+
+    @classmethod
+    def make(cls, pixel_size, mask="none", automask_lp=0.0, threshold_method="intensity", threshold_value=0.0, randomize="fsc",
+             randomize_value=0.8, seed=0, bfactor="none", adhoc_bfac=0.0, fit_low=10.0, fit_high=0.0, lowpass="auto", highpass=0.0,
+             gaussian=False, skip_fsc_weighting=False, apply_fsc2=False, flip_x=False, flip_y=False, flip_z=False):
+        """mask: "none", "external" (host.postprocess is given one) or "auto" (made from the mean of the halves: low-pass automask_lp in A,
+        threshold_method "intensity" / "sigma" / "volume" with threshold_value); randomize: "fsc" (from the first shell whose unmasked FSC
+        is below randomize_value) or "resolution" (from randomize_value A); bfactor: "none", "adhoc" (adhoc_bfac, negative sharpens) or
+        "auto" (fit between fit_low and fit_high A, fit_high 0 = the resolution); lowpass: A, 0 = none, "auto" = the resolution;
+        highpass: A, <= 0 = none."""
+        auto = isinstance(lowpass, str)
+        if auto and lowpass != "auto":
+            raise ValueError(f"ERROR: PostCfg: lowpass must be a number or 'auto', got '{lowpass}'")
+        return cls(pixel_size=float(pixel_size), mask_mode=cls.MASK[mask], automask_lp=float(automask_lp),
+                   threshold_method=cls.THRESHOLD[threshold_method], threshold_value=float(threshold_value),
+                   randomize_method=cls.RANDOMIZE[randomize], randomize_value=float(randomize_value), seed=int(seed) & 0xFFFFFFFF,
+                   bfactor_method=cls.BFACTOR[bfactor], adhoc_bfac=float(adhoc_bfac), fit_low=float(fit_low), fit_high=float(fit_high),
+                   lowpass_auto=1 if auto else 0, lowpass=0.0 if auto else float(lowpass), highpass=float(highpass), gaussian=int(bool(gaussian)),
+                   skip_fsc_weighting=int(bool(skip_fsc_weighting)), apply_fsc2=int(bool(apply_fsc2)), flip_x=int(bool(flip_x)),
+                   flip_y=int(bool(flip_y)), flip_z=int(bool(flip_z)))
+
+
+class PostInfo(C.Structure):
+    """ppm_post_info (include/ppm.h): first randomised shell, first shell with a corrected FSC below 0.143 (0: none), shells of the
+    B-factor fit, complex transforms run, resolution in A, B in A^2, threshold of the automatic mask, voxels of the mask."""
+    _fields_ = [("s_r", C.c_int), ("res_shell", C.c_int), ("fit_shells", C.c_int), ("transforms", C.c_int), ("resolution", C.c_double),
+                ("bfactor", C.c_double), ("threshold", C.c_double), ("mask_voxels", C.c_long)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}

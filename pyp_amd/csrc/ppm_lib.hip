@@ -32,6 +32,7 @@
 #include "ppm_gfft.h"
 #include "ppm_mask_kernels.h"
 #include "ppm_label_kernels.h"
+#include "ppm_post_kernels.h"
 
 using namespace ppm;
 
@@ -42,3 +43,4 @@ using namespace ppm;
 #include "host_sva.h"
 #include "host_mask.h"
 #include "host_label.h"
+#include "host_post.h"

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import lib
-from .abi import NCOL, STATS_COLS, K_NAMES, CreateMaskCfg, CreateMaskInfo, FinalCfg, MaskCfg, ReconCfg, RefineCfg  # noqa: F401
+from .abi import NCOL, STATS_COLS, K_NAMES, CreateMaskCfg, CreateMaskInfo, FinalCfg, MaskCfg, PostCfg, PostInfo, ReconCfg, RefineCfg  # noqa: F401
 
 
 def _sync_producer(t):
@@ -372,6 +372,41 @@ def create_mask(vol, cfg, out=None, device=0):
     info = CreateMaskInfo()
     lib.check(lib.load().ppm_create_mask(pv, 1 if on_dev else 0, n, C.byref(cfg), po, C.byref(info)))
     return res, info
+
+
+def postprocess(half1, half2, cfg, mask=None, device=0):
+    """Post-processing of two half maps (ppm_postprocess, what PYP's external/postprocessing/postprocessing.py does): half1, half2 and
+    the optional external mask = N^3 float32, all numpy arrays or all CUDA torch tensors; cfg: abi.PostCfg (mask given: cfg.mask_mode
+    must be "external").  Returns dict(unmasked, masked, mask = maps of the kind given; curves = [4, N/2 + 1] float64 (unmasked,
+    masked, phase-randomised, corrected FSC); shell_count = [N/2 + 1] int64; info = abi.PostInfo).  A refusal raises lib.PpmError."""
+    lib.init(device)
+    maps = [half1, half2] + ([mask] if mask is not None else [])
+    on_dev = bool(getattr(half1, "is_cuda", False))
+    if any(bool(getattr(m, "is_cuda", False)) != on_dev for m in maps):
+        raise ValueError("ERROR: postprocess: the half maps and the mask must all be on the host or all on the device")
+    if not on_dev:
+        maps = [np.ascontiguousarray(m.numpy() if hasattr(m, "numpy") else m, dtype=np.float32) for m in maps]
+    shape = tuple(int(x) for x in maps[0].shape)
+    if len(shape) != 3 or len(set(shape)) != 1:
+        raise ValueError("ERROR: postprocess: the half maps must be cubic volumes")
+    if any(tuple(int(x) for x in m.shape) != shape for m in maps):
+        raise ValueError("ERROR: postprocess: the half maps and the mask have different dimensions")
+    n = shape[0]
+    if on_dev:
+        import torch
+        outs = [torch.empty_like(maps[0]) for _ in range(3)]
+        keep = [_volumes_arg(m, 1, n) for m in maps + outs]
+        ptrs = [k[0] for k in keep]
+    else:
+        outs = [np.empty_like(maps[0]) for _ in range(3)]
+        ptrs = [lib.ptr(m) for m in maps + outs]
+    pm = ptrs[2] if mask is not None else None
+    po = ptrs[-3:]
+    ns = n // 2 + 1
+    curves, counts, info = np.zeros((4, ns), dtype=np.float64), np.zeros(ns, dtype=np.int64), PostInfo()
+    lib.check(lib.load().ppm_postprocess(ptrs[0], ptrs[1], pm, 1 if on_dev else 0, n, C.byref(cfg), po[0], po[1], po[2], lib.ptr(curves),
+                                         lib.ptr(counts), C.byref(info)))
+    return dict(unmasked=outs[0], masked=outs[1], mask=outs[2], curves=curves, shell_count=counts, info=info)
 
 
 class PinnedBuffer:

@@ -10,19 +10,24 @@ from .formats.cistem import COL
 
 
 def iteration(vol, stack, rows, refine_cfg, *, pixel_size, molecular_mass_kda, symmetry="C1", keep_fraction=1.0,
-              score_weight_bfactor=0.0, outer_radius=None, split_by_pind=False, mask=None, mask_cfg=None, auto_mask=None):
+              score_weight_bfactor=0.0, outer_radius=None, split_by_pind=False, mask=None, mask_cfg=None, auto_mask=None, postprocess=None):
     """vol: current reference (N^3 float32); stack: [M, N, N] float32 (numpy or a CUDA torch tensor); rows: [M, 32].
     mask (N^3 float32, of the same kind as vol) with mask_cfg (abi.MaskCfg; default: PYP's edge of 3 voxels, weight 0): the
     reference is shape-masked on the device first, as `shape_mask_reference` (align/core.py:783-856) does with apply_mask.exe.
     auto_mask (abi.CreateMaskCfg) in place of mask: the mask is made from vol itself on the device (host.create_mask, the work of
     `cistem_mask_create`, inout/image/core.py:1538-1605) and applied with mask_cfg.
+    postprocess (abi.PostCfg): the half maps go through host.postprocess (the work of the Post-processing block, pyp_main.py:6601-6865)
+    and its result is added as "post"; a cfg with mask "external" uses `mask` (or the one auto_mask made).
     Returns dict(rows=refined table incl. OCC after selection, half1, half2, filtered, stats=[N/2-1, 7] statistics table).
     """
     n = int(refine_cfg.box)
+    if postprocess is not None and postprocess.mask_mode == 1 and mask is None and auto_mask is None:
+        raise ValueError("ERROR: iteration: postprocess asks for an external mask, but neither mask nor auto_mask was given")
     if auto_mask is not None:
         if mask is not None:
             raise ValueError("ERROR: iteration: auto_mask and mask exclude each other")
         mask, _ = host.create_mask(vol, auto_mask)
+    post_mask = mask if postprocess is not None and postprocess.mask_mode == 1 else None
     if mask is not None:
         vol = host.mask_volume(vol, mask, mask_cfg if mask_cfg is not None else MaskCfg.make(pixel_size=pixel_size))
         if getattr(vol, "is_cuda", False):          # map and mask were device tensors: Reference takes a host array
@@ -47,4 +52,9 @@ def iteration(vol, stack, rows, refine_cfg, *, pixel_size, molecular_mass_kda, s
         h1, h2, filt, stats = acc.finalize(fc)
     finally:
         acc.close()
-    return dict(rows=used, half1=h1, half2=h2, filtered=filt, stats=np.asarray(stats))
+    result = dict(rows=used, half1=h1, half2=h2, filtered=filt, stats=np.asarray(stats))
+    if postprocess is not None:
+        if getattr(post_mask, "is_cuda", False):      # the half maps are host arrays
+            post_mask = post_mask.cpu().numpy()
+        result["post"] = host.postprocess(h1, h2, postprocess, mask=post_mask)
+    return result

@@ -13,7 +13,7 @@ import time
 
 import numpy as np
 
-from ..abi import CreateMaskCfg, FinalCfg, MaskCfg, ReconCfg, RefineCfg
+from ..abi import CreateMaskCfg, FinalCfg, MaskCfg, PostCfg, ReconCfg, RefineCfg
 from ..formats import cistem, mrc, parfile
 from . import prompts
 
@@ -915,4 +915,112 @@ def create_mask_main(argv=None, stdin=None, backend=None):
     print(f"Timing: input {t1 - t0:.2f} s, device {t2 - t1:.2f} s, output {time.time() - t2:.2f} s")
     _release_warm()
     print("\nCreateMask: Normal termination\n", flush=True)
+    return 0
+
+
+# ------------------------------------------------------------------------------------------ postprocessing.py
+def post_cfg_from_options(d):
+    """abi.PostCfg of a parsed postprocessing.py command line (prompts.parse_postprocessing)."""
+    return PostCfg.make(pixel_size=d["angpix"], mask=d["mask_mode"], automask_lp=d["automask_lp"], threshold_method=d["threshold_method"],
+                        threshold_value=d["threshold_value"], randomize=d["randomize"], randomize_value=d["randomize_value"],
+                        bfactor=d["bfactor"], adhoc_bfac=d["adhoc_bfac"], fit_low=d["fit_low"], fit_high=d["fit_high"], lowpass=d["lowpass"],
+                        highpass=d["highpass"], gaussian=d["gaussian"], skip_fsc_weighting=d["skip_fsc_weighting"], apply_fsc2=d["apply_fsc2"],
+                        flip_x=d["flip_x"], flip_y=d["flip_y"], flip_z=d["flip_z"])
+
+
+def format_fsc_file(curves, n, pixel, header):
+    """<out>_data.fsc: '#' comment lines, then one row per shell 1 .. N/2: resolution in A, frequency in 1/A, unmasked, masked,
+    phase-randomised and corrected FSC.  PYP reads it with np.loadtxt(comments="#")[:, [0, 2, 3, 4, 5]] (pyp_main.py:6811)."""
+    lines = ["# " + h for h in header]
+    lines.append("# resolution_A  frequency_1/A  fsc_unmasked  fsc_masked  fsc_phase_randomized  fsc_corrected")
+    for s in range(1, n // 2 + 1):
+        f = s / (n * pixel)
+        lines.append("%12.6f %12.8f %12.8f %12.8f %12.8f %12.8f" % (1.0 / f, f, curves[0][s], curves[1][s], curves[2][s], curves[3][s]))
+    return "\n".join(lines) + "\n"
+
+
+def postprocessing_main(argv=None, backend=None):
+    """PYP's external/postprocessing/postprocessing.py as the Post-processing block runs it (src/pyp_main.py:6601-6865): the maps are read
+    in full, the four outputs appear under their names only when all are complete (the masked map, whose existence PYP tests, last).
+    backend: what computes (half1, half2, PostCfg, mask) -> the dict of host.postprocess; default host.postprocess on the GPU, under the
+    per-GPU lock."""
+    t0 = time.time()
+    try:
+        d = prompts.parse_postprocessing(sys.argv[1:] if argv is None else argv)
+    except prompts.PromptError as e:
+        _die(str(e))
+    print("\n        **   Welcome to Postprocessing (MI355X / libpypmatch)   **\n")
+    for k, v in d.items():
+        print(f"{k:28s}: {v}")
+    inputs = [d["half1"], d["half2"]] + ([d["mask"]] if d["mask"] is not None else [])
+    for p in inputs:
+        if not os.path.exists(p):
+            _die(f"ERROR: postprocessing: input file {p} does not exist")
+    try:
+        vols = [mrc.read(p).astype(np.float32) for p in inputs]
+    except (IOError, ValueError) as e:
+        _die(str(e))
+    if vols[0].ndim != 3 or len(set(vols[0].shape)) != 1:
+        _die(f"ERROR: postprocessing: the first half map is {vols[0].shape}, only cubic maps are supported")
+    for p, v in zip(inputs[1:], vols[1:]):
+        if v.shape != vols[0].shape:
+            _die(f"ERROR: postprocessing: {inputs[0]} is {vols[0].shape}, {p} is {v.shape}")
+    n, px = vols[0].shape[0], d["angpix"]
+    if not prompts.postprocessing_box_ok(n):
+        _die(f"ERROR: postprocessing: the box must be even, 32..512, with prime factors 2, 3, 5, 7, got {n}")
+    if d["xml"]:
+        print("--xml: nothing in PYP reads such a file; none is written")
+    cfg = post_cfg_from_options(d)
+    t1 = time.time()
+    try:
+        if backend is not None:
+            res = backend(vols[0], vols[1], cfg, vols[2] if len(vols) > 2 else None)
+        else:
+            from .. import host, lib
+            dev = int(os.environ.get("PPM_DEVICE", "0"))
+            try:
+                with gpu_lock(dev):
+                    res = host.postprocess(vols[0], vols[1], cfg, mask=vols[2] if len(vols) > 2 else None, device=dev)
+            except lib.PpmError as e:
+                _die(str(e))
+    except ValueError as e:
+        _die(str(e))
+    t2 = time.time()
+    info = res["info"]
+    header = [f"postprocessing: box {n}, pixel size {px:g} A, mask {d['mask_mode']}",
+              f"phases randomised from shell {info.s_r} ({n * px / info.s_r:.3f} A)",
+              f"resolution at FSC 0.143 (corrected): {info.resolution:.4f} A", f"B-factor ({d['bfactor']}): {info.bfactor:.4f} A^2"]
+    if d["refine_res_lim"] is not None:
+        header.append(f"refine_res_lim: {d['refine_res_lim']:g} A")
+    out = d["out"]
+    files = [(out + "-unmasked.mrc", res["unmasked"])]
+    if d["mask_mode"] == "auto":
+        files.append((out + "-automask.mrc", res["mask"]))
+    files += [(out + "_data.fsc", format_fsc_file(res["curves"], n, px, header)), (out + "-masked.mrc", res["masked"])]
+    tmps = []
+    try:
+        for path, what in files:
+            tmp = path + ".tmp%d" % os.getpid()
+            tmps.append(tmp)
+            if isinstance(what, str):
+                with open(tmp, "w") as f:
+                    f.write(what)
+            else:
+                mrc.write(np.asarray(what, dtype=np.float32), tmp, pixel_size=px)
+        for (path, _), tmp in zip(files, tmps):
+            os.replace(tmp, path)
+    except OSError as e:
+        for tmp in tmps:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+        _die(f"ERROR: postprocessing: could not write the outputs of {out}: {e}")
+    print(f"\nPost-processed two {n}^3 half maps at {px:g} A/pixel with {info.transforms} transforms")
+    if d["mask_mode"] == "auto":
+        print(f"Automatic mask                 : threshold {info.threshold:g} ({d['threshold_method']}), {info.mask_voxels} voxels in its body")
+    print(f"Phases randomised from shell   : {info.s_r} ({n * px / info.s_r:.2f} A)")
+    print(f"FINAL RESOLUTION (corrected FSC = 0.143) : {info.resolution:.3f} A")
+    print(f"B-factor ({d['bfactor']:5s})               : {info.bfactor:.2f} A^2")
+    print(f"Timing: inputs {t1 - t0:.2f} s, device {t2 - t1:.2f} s, outputs {time.time() - t2:.2f} s")
+    _release_warm()
+    print("\nPostprocessing: Normal termination\n", flush=True)
     return 0

@@ -5,6 +5,7 @@ booleans (src/pyp/refine/frealign/frealign.py:3918-3994 refine3d, :1780-1824 rec
 :1878-1888 local_merge3d, :2075-2093 merge3d; src/pyp/align/core.py:811-850 apply_mask.exe; src/pyp/inout/image/core.py:1583-1596
 create_mask; the `.par`-surface refine3d script
 is preserved at src/pyp/system/wrapper_functions.py:512-561).  Answer order: SURVEY.md §9.1-§9.3.
+postprocessing.py alone takes a command line (src/pyp_main.py:6638-6737): parse_postprocessing.
 """
 
 
@@ -220,6 +221,128 @@ def parse_create_mask(answers):
         raise PromptError(f"ERROR: {prog}: low-pass filter resolution must not be negative (0 = none), got '{a[6]}'")
     if d["lowpass"] != 0 and not 0 < d["rebin"] < 1:
         raise PromptError(f"ERROR: {prog}: re-bin value must lie strictly between 0 and 1, got '{a[7]}'")
+    return d
+
+
+POSTPROCESSING_FLAGS = ("flip_x", "flip_y", "flip_z", "gaussian", "skip_fsc_weighting", "apply_fsc2", "automask", "xml")
+POSTPROCESSING_VALUES = ("mask", "angpix", "out", "auto_bfac", "adhoc_bfac", "lowpass", "highpass", "automask_input", "automask_lp",
+                         "automask_threshold", "automask_fraction", "automask_sigma", "randomize_below_fsc", "randomize_beyond",
+                         "refine_res_lim", "mtf")
+POSTPROCESSING_RANDOMIZE_FSC = 0.8       # neither --randomize_below_fsc nor --randomize_beyond: from the first shell with an FSC below this
+
+
+def postprocessing_box_ok(n):
+    """A box the library's transforms take: even, 32..512, prime factors 2, 3, 5, 7."""
+    if n % 2 or not 32 <= n <= 512:
+        return False
+    for p in (2, 3, 5, 7):
+        while n % p == 0:
+            n //= p
+    return n == 1
+
+
+def parse_postprocessing(argv):
+    """postprocessing.py, the command line PYP's Post-processing block puts together at src/pyp_main.py:6638-6737 (it is a command line,
+    not a here-doc): `half1 half2 [--mask F] --angpix A --out NAME [--flip_x] [--flip_y] [--flip_z] [--refine_res_lim V] --xml
+    [--auto_bfac LOW,HIGH | --adhoc_bfac I] [--gaussian] --lowpass V|auto --highpass V [--skip_fsc_weighting] [--apply_fsc2]
+    [--automask --automask_input 0 --automask_lp V (--automask_threshold V | --automask_fraction V | --automask_sigma V)]
+    [--randomize_below_fsc V | --randomize_beyond V]`.  Options may also be written `--name=value`.  Refused here: what can be told from
+    the command line alone (--mtf, --automask_input other than 0, both FSC flags, unknown options, values out of range)."""
+    prog = "postprocessing"
+    d = {k: False for k in POSTPROCESSING_FLAGS}
+    d.update({k: None for k in POSTPROCESSING_VALUES})
+    pos = []
+    a = list(argv)
+    i = 0
+    while i < len(a):
+        tok = a[i]
+        i += 1
+        if not tok.startswith("--"):
+            pos.append(tok)
+            continue
+        name, eq, val = tok[2:].partition("=")
+        if name in POSTPROCESSING_FLAGS:
+            if eq:
+                raise PromptError(f"ERROR: {prog}: option --{name} takes no value")
+            d[name] = True
+        elif name in POSTPROCESSING_VALUES:
+            if not eq:
+                if i >= len(a):
+                    raise PromptError(f"ERROR: {prog}: option --{name} needs a value")
+                val = a[i]
+                i += 1
+            if d[name] is not None:
+                raise PromptError(f"ERROR: {prog}: option --{name} given twice")
+            d[name] = val
+        else:
+            raise PromptError(f"ERROR: {prog}: unknown option '{tok}'")
+    if len(pos) != 2:
+        raise PromptError(f"ERROR: {prog}: expected the two half maps, got {len(pos)} positional arguments")
+    d["half1"], d["half2"] = pos
+    if d["mtf"] is not None:
+        raise PromptError(f"ERROR: {prog}: the MTF correction (--mtf) is not supported by this build")
+    if d["angpix"] is None or d["out"] is None:
+        raise PromptError(f"ERROR: {prog}: --angpix and --out are required")
+    d["angpix"] = _num(d["angpix"], "angpix")
+    if not d["angpix"] > 0:
+        raise PromptError(f"ERROR: {prog}: pixel size must be positive, got '{d['angpix']:g}'")
+    if d["skip_fsc_weighting"] and d["apply_fsc2"]:
+        raise PromptError(f"ERROR: {prog}: --skip_fsc_weighting and --apply_fsc2 exclude each other")
+    # B-factor
+    if d["auto_bfac"] is not None and d["adhoc_bfac"] is not None:
+        raise PromptError(f"ERROR: {prog}: --auto_bfac and --adhoc_bfac exclude each other")
+    d["bfactor"], d["fit_low"], d["fit_high"] = "none", 10.0, 0.0
+    if d["adhoc_bfac"] is not None:
+        d["bfactor"], d["adhoc_bfac"] = "adhoc", _num(d["adhoc_bfac"], "adhoc_bfac")
+    elif d["auto_bfac"] is not None:
+        parts = d["auto_bfac"].split(",")
+        if len(parts) != 2:
+            raise PromptError(f"ERROR: {prog}: --auto_bfac takes LOW,HIGH (resolutions in A), got '{d['auto_bfac']}'")
+        d["bfactor"], d["fit_low"], d["fit_high"] = "auto", _num(parts[0], "auto_bfac low"), _num(parts[1], "auto_bfac high")
+        if not d["fit_low"] > 0 or not d["fit_high"] >= 0 or d["fit_high"] > d["fit_low"]:
+            raise PromptError(f"ERROR: {prog}: --auto_bfac needs LOW > 0 and 0 <= HIGH <= LOW (in A; HIGH 0 = the resolution), got '{d['auto_bfac']}'")
+    d["adhoc_bfac"] = d["adhoc_bfac"] if d["bfactor"] == "adhoc" else 0.0
+    # filter
+    if d["lowpass"] is None or d["lowpass"] == "auto":
+        d["lowpass"] = "auto"
+    else:
+        d["lowpass"] = _num(d["lowpass"], "lowpass")
+        if not d["lowpass"] >= 0:
+            raise PromptError(f"ERROR: {prog}: --lowpass must be a resolution in A (0 = none) or auto, got '{d['lowpass']:g}'")
+    d["highpass"] = 0.0 if d["highpass"] is None else _num(d["highpass"], "highpass")
+    # mask
+    thr = [(k, m) for k, m in (("automask_threshold", "intensity"), ("automask_fraction", "volume"), ("automask_sigma", "sigma")) if d[k] is not None]
+    d["threshold_method"], d["threshold_value"] = "intensity", 0.0
+    if d["automask"]:
+        if d["mask"] is not None:
+            raise PromptError(f"ERROR: {prog}: --mask and --automask exclude each other")
+        if d["automask_input"] is not None and _num(d["automask_input"], "automask_input") != 0:
+            raise PromptError(f"ERROR: {prog}: --automask_input {d['automask_input']} is not supported by this build (only 0, the mean of the half maps)")
+        if len(thr) != 1:
+            raise PromptError(f"ERROR: {prog}: --automask needs one of --automask_threshold, --automask_fraction, --automask_sigma, got {len(thr)}")
+        d["threshold_method"], d["threshold_value"] = thr[0][1], _num(d[thr[0][0]], thr[0][0])
+        if d["threshold_method"] == "volume" and not 0 < d["threshold_value"] <= 1:
+            raise PromptError(f"ERROR: {prog}: --automask_fraction must lie in (0, 1], got '{d['threshold_value']:g}'")
+        d["automask_lp"] = 0.0 if d["automask_lp"] is None else _num(d["automask_lp"], "automask_lp")
+        if not d["automask_lp"] >= 0:
+            raise PromptError(f"ERROR: {prog}: --automask_lp must not be negative (0 = none), got '{d['automask_lp']:g}'")
+    else:
+        if thr or d["automask_lp"] is not None or d["automask_input"] is not None:
+            raise PromptError(f"ERROR: {prog}: --automask_* options need --automask")
+        d["automask_lp"] = 0.0
+    d["mask_mode"] = "auto" if d["automask"] else "external" if d["mask"] is not None else "none"
+    # phase randomisation
+    if d["randomize_below_fsc"] is not None and d["randomize_beyond"] is not None:
+        raise PromptError(f"ERROR: {prog}: --randomize_below_fsc and --randomize_beyond exclude each other")
+    if d["randomize_beyond"] is not None:
+        d["randomize"], d["randomize_value"] = "resolution", _num(d["randomize_beyond"], "randomize_beyond")
+        if not d["randomize_value"] > 0:
+            raise PromptError(f"ERROR: {prog}: --randomize_beyond must be a positive resolution in A, got '{d['randomize_value']:g}'")
+    else:
+        d["randomize"] = "fsc"
+        d["randomize_value"] = POSTPROCESSING_RANDOMIZE_FSC if d["randomize_below_fsc"] is None else _num(d["randomize_below_fsc"], "randomize_below_fsc")
+    if d["refine_res_lim"] is not None:
+        d["refine_res_lim"] = _num(d["refine_res_lim"], "refine_res_lim")
     return d
 
 
