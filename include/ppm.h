@@ -476,6 +476,51 @@ typedef struct ppm_post_info { int s_r, res_shell, fit_shells, transforms; doubl
 int ppm_postprocess(const void *half1, const void *half2, const void *mask, int on_device, int n, const ppm_post_cfg *cfg,
                     void *unmasked_out, void *masked_out, void *mask_out, double *curves, long *shell_count, ppm_post_info *info);
 
+/* Local resolution of two half maps: the work of ResMap (--noguiSplit), which PYP's Post-processing block starts on the half maps once
+ * <out>_data.fsc is read (src/pyp_main.py:6815-6844; tabs.sharpen.resmap defaults to true).  Build-defined: the reference checkout holds
+ * neither that program nor any output of it, so nothing pins its arithmetic.  After the published idea (Kucukelbir, Sigworth & Tagare
+ * 2014): voxel by voxel and resolution by resolution, test whether the local signal at that wavelength stands out of the noise, the
+ * noise taken from the difference of the half maps, at the caller's p-value.  DESIGN.md 2e.
+ *   inside   voxels with mask > 0.5; without a mask those with |x - c| < n/2, c = (n/2, n/2, n/2); their number n_inside = 0 is refused
+ *   levels   lambda_i = lambda_min + i step for all i with lambda_i <= lambda_max, in float64; the device and the map hold them as float32.
+ *            step < 0.25 is refused.  lambda_min = min_res, raised to 2.5 pixel_size when below it (0 included; info.notes says so): the
+ *            band centre plus two widths stays inside Nyquist.  lambda_max = max_res; 0 means n pixel_size / 6 (band centre six Fourier
+ *            pixels out); above n pixel_size / 4 is refused.  No level, or more than 64, is refused.
+ *   per level, with s = n pixel_size / lambda Fourier pixels and l = lambda / pixel_size voxels:
+ *     band    b(k) = exp(-(|k| - s)^2 / (2 sb^2)), sb = max(s / 8, 1.5), b(0) = 0
+ *     window  W(k) = exp(-2 pi^2 sw^2 |k|^2 / n^2), sw = max(l, 2) / 2
+ *             k: signed indices in [-n/2, n/2) per axis; both are tables over the integer |k|^2 (3 (n/2)^2 + 1 entries), made in float64
+ *             with the transforms' 1 / n^3 folded in and rounded once to float32
+ *     A = (half1 + half2) / 2, D = (half1 - half2) / 2 in float32; A_l = IFFT(b FFT A), D_l likewise;
+ *     E_A = Re IFFT(W FFT(A_l^2)), E_D likewise from D_l^2 (cyclic convolutions)
+ *     tau     the r-th smallest E_D over the inside voxels, r = ceil((1 - p) n_inside) clipped to 1 .. n_inside: an exact order statistic
+ *             (non-negative float32 bits order like unsigned integers; a negative value counts as 0)
+ *     a voxel passes the level when it is inside and E_A > tau
+ *   map      levels run from the coarsest to the finest; a voxel is alive at first when it is inside, stays alive while it passes, and
+ *            takes the lambda of the last level at which it was alive; every other voxel keeps 100.0 (outside, or failed the coarsest
+ *            level).  No multiple-testing correction: the continuity rule keeps the chance hits of a fine level off the solvent.
+ * Both maps ride one complex array Z = A + i D (a real radial filter acts on both, squaring after the inverse transform keeps them
+ * apart): 1 + 3 L complex transforms for L levels.  Integer atomics only: two calls on the same data agree bit for bit.
+ * half1, half2, mask (or NULL), out_res: n^3 floats, x fastest; on_device != 0: device pointers, level_maps included.
+ * keep_levels (a debug output, 0 = off): the number of levels level_maps has room for, n^3 pairs (E_A, E_D) of floats each, finest level
+ * first; fewer than the grid holds is refused.  n: a box the transforms take (even, 32..512, prime factors 2, 3, 5, 7).  Refusals return
+ * -22 and write nothing. */
+#define PPM_LOCRES_MAX_LEVELS 64
+#define PPM_LOCRES_UNASSIGNED 100.0f
+typedef struct ppm_locres_cfg { double pixel_size, p_value, min_res, max_res, step; int keep_levels; } ppm_locres_cfg;
+/* levels (ascending, as float32), tau per level, voxels whose value is that level, inside voxels, those left at 100, the median of the
+ * map over the inside voxels (the ceil(n_inside / 2)-th smallest), complex 3-D transforms run, notes (what was adjusted; may be empty) */
+typedef struct ppm_locres_info {
+    int n_levels, transforms;
+    long n_inside, unassigned;
+    double median;
+    float levels[PPM_LOCRES_MAX_LEVELS], tau[PPM_LOCRES_MAX_LEVELS];
+    long counts[PPM_LOCRES_MAX_LEVELS];
+    char notes[256];
+} ppm_locres_info;
+int ppm_local_resolution(const ppm_locres_cfg *cfg, const void *half1, const void *half2, const void *mask, int on_device, int n,
+                         void *out_res, void *level_maps, ppm_locres_info *info);
+
 /* Particle extraction straight into a (resident) stack — the step before the path:
  * crop `box` x `box` windows around the picked coordinates, fill what falls outside the micrograph with the mean
  * of the inside part, replace empty boxes by white noise, subtract the background mean and divide by the background

@@ -207,3 +207,77 @@ class PostInfo(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+LOCRES_MAX_LEVELS = 64
+LOCRES_UNASSIGNED = 100.0
+LOCRES_MIN_STEP = 0.25
+LOCRES_MIN_LEVEL_PX = 2.5
+
+
+def locres_levels(n, pixel_size, min_res=0.0, max_res=0.0, step=1.0):
+    """The level grid of ppm_local_resolution as the library builds it, in float64: lambda_min + i step for all i with
+    lambda_i <= lambda_max.  min_res below 2.5 pixels (0 included) is raised to that; max_res 0 = n pixel_size / 6.  Returns
+    (levels, notes); raises ValueError for what the library refuses (step < 0.25, max_res above n pixel_size / 4, no level, more than 64)."""
+    a, lo, hi, step = float(pixel_size), float(min_res), float(max_res), float(step)
+    if not a > 0:
+        raise ValueError("ERROR: local_resolution: the pixel size must be positive")
+    if not step >= LOCRES_MIN_STEP or step == float("inf"):
+        raise ValueError("ERROR: local_resolution: the resolution step must be at least 0.25 A")
+    if not (0 <= lo < float("inf")) or not (0 <= hi < float("inf")):
+        raise ValueError("ERROR: local_resolution: the minimum and maximum resolution must not be negative (0 = the default)")
+    notes = []
+    if lo < LOCRES_MIN_LEVEL_PX * a:
+        notes.append("minimum resolution %g A raised to %g A (2.5 pixels)" % (lo, LOCRES_MIN_LEVEL_PX * a))
+        lo = LOCRES_MIN_LEVEL_PX * a
+    if hi == 0:
+        hi = n * a / 6.0
+        notes.append("maximum resolution set to %g A (box / 6)" % hi)
+    elif hi > n * a / 4.0:
+        raise ValueError("ERROR: local_resolution: the maximum resolution %g A is above a quarter of the box (%g A)" % (hi, n * a / 4.0))
+    levels = []
+    i = 0
+    while lo + i * step <= hi:
+        if i >= LOCRES_MAX_LEVELS:
+            raise ValueError("ERROR: local_resolution: more than 64 resolution levels; raise the step or narrow the range")
+        levels.append(lo + i * step)
+        i += 1
+    if not levels:
+        raise ValueError("ERROR: local_resolution: no resolution level between %g A and %g A" % (lo, hi))
+    return levels, notes
+
+
+def locres_rank(p_value, n_inside):
+    """r of ppm_local_resolution: the threshold of a level is the r-th smallest noise energy over the n_inside voxels of the mask,
+    r = ceil((1 - p) n_inside) clipped to 1 .. n_inside."""
+    import math
+    return int(min(max(math.ceil((1.0 - float(p_value)) * float(n_inside)), 1), n_inside))
+
+
+class LocresCfg(C.Structure):
+    """ppm_locres_cfg (include/ppm.h)."""
+    _fields_ = [("pixel_size", C.c_double), ("p_value", C.c_double), ("min_res", C.c_double), ("max_res", C.c_double), ("step", C.c_double),
+                ("keep_levels", C.c_int)]
+
+    @classmethod
+    def make(cls, pixel_size, p_value=0.05, min_res=0.0, max_res=0.0, step=1.0, keep_levels=False):
+        """p_value: of the test of a level's signal energy against the noise energies inside the mask; min_res, max_res, step: the level
+        grid in A (abi.locres_levels; 0 = 2.5 pixels / a sixth of the box); keep_levels: a debug output - host.local_resolution also
+        returns the energy maps (E_A, E_D) of every level."""
+        if not 0 < float(p_value) < 1:
+            raise ValueError(f"ERROR: LocresCfg: the p-value must lie strictly between 0 and 1, got {p_value}")
+        return cls(pixel_size=float(pixel_size), p_value=float(p_value), min_res=float(min_res), max_res=float(max_res), step=float(step),
+                   keep_levels=1 if keep_levels else 0)
+
+
+class LocresInfo(C.Structure):
+    """ppm_locres_info (include/ppm.h): levels (ascending), tau and voxels per level, inside voxels, those left at 100, the median of the
+    map over the inside voxels, complex transforms run, notes."""
+    _fields_ = [("n_levels", C.c_int), ("transforms", C.c_int), ("n_inside", C.c_long), ("unassigned", C.c_long), ("median", C.c_double),
+                ("levels", C.c_float * LOCRES_MAX_LEVELS), ("tau", C.c_float * LOCRES_MAX_LEVELS), ("counts", C.c_long * LOCRES_MAX_LEVELS),
+                ("notes", C.c_char * 256)]
+
+    def as_dict(self):
+        L = self.n_levels
+        return dict(n_levels=L, transforms=self.transforms, n_inside=self.n_inside, unassigned=self.unassigned, median=self.median,
+                    levels=list(self.levels[:L]), tau=list(self.tau[:L]), counts=list(self.counts[:L]), notes=self.notes.decode())

@@ -33,6 +33,7 @@
 #include "ppm_mask_kernels.h"
 #include "ppm_label_kernels.h"
 #include "ppm_post_kernels.h"
+#include "ppm_locres_kernels.h"
 
 using namespace ppm;
 
@@ -44,3 +45,4 @@ using namespace ppm;
 #include "host_mask.h"
 #include "host_label.h"
 #include "host_post.h"
+#include "host_locres.h"

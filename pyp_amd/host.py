@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import lib
-from .abi import NCOL, STATS_COLS, K_NAMES, CreateMaskCfg, CreateMaskInfo, FinalCfg, MaskCfg, PostCfg, PostInfo, ReconCfg, RefineCfg  # noqa: F401
+from .abi import NCOL, STATS_COLS, K_NAMES, CreateMaskCfg, CreateMaskInfo, FinalCfg, LocresCfg, LocresInfo, MaskCfg, PostCfg, PostInfo, ReconCfg, RefineCfg  # noqa: F401
 
 
 def _sync_producer(t):
@@ -407,6 +407,58 @@ def postprocess(half1, half2, cfg, mask=None, device=0):
     lib.check(lib.load().ppm_postprocess(ptrs[0], ptrs[1], pm, 1 if on_dev else 0, n, C.byref(cfg), po[0], po[1], po[2], lib.ptr(curves),
                                          lib.ptr(counts), C.byref(info)))
     return dict(unmasked=outs[0], masked=outs[1], mask=outs[2], curves=curves, shell_count=counts, info=info)
+
+
+def local_resolution(half1, half2, cfg, mask=None, device=0):
+    """Local resolution of two half maps (ppm_local_resolution, what ResMap --noguiSplit does in PYP's Post-processing block; DESIGN.md
+    2e): half1, half2 and the optional mask (inside where > 0.5; default: the sphere of radius N/2) = N^3 float32, all numpy arrays or all
+    CUDA torch tensors; cfg: abi.LocresCfg.  Returns dict(resolution = map of the kind given, in A, 100 where nothing was assigned;
+    levels, tau = [L] float32; counts = [L] int64, voxels per level; info = abi.LocresInfo), and with cfg.keep_levels also energies =
+    [L, N, N, N, 2] float32 of the kind given: E_A and E_D of every level.  A refusal raises lib.PpmError."""
+    from . import abi
+    lib.init(device)
+    maps = [half1, half2] + ([mask] if mask is not None else [])
+    on_dev = bool(getattr(half1, "is_cuda", False))
+    if any(bool(getattr(m, "is_cuda", False)) != on_dev for m in maps):
+        raise ValueError("ERROR: local_resolution: the half maps and the mask must all be on the host or all on the device")
+    if not on_dev:
+        maps = [np.ascontiguousarray(m.numpy() if hasattr(m, "numpy") else m, dtype=np.float32) for m in maps]
+    shape = tuple(int(x) for x in maps[0].shape)
+    if len(shape) != 3 or len(set(shape)) != 1:
+        raise ValueError("ERROR: local_resolution: the half maps must be cubic volumes")
+    if any(tuple(int(x) for x in m.shape) != shape for m in maps):
+        raise ValueError("ERROR: local_resolution: the half maps and the mask have different dimensions")
+    n = shape[0]
+    call = LocresCfg(pixel_size=cfg.pixel_size, p_value=cfg.p_value, min_res=cfg.min_res, max_res=cfg.max_res, step=cfg.step, keep_levels=0)
+    energies = None
+    if cfg.keep_levels:
+        try:
+            call.keep_levels = len(abi.locres_levels(n, cfg.pixel_size, cfg.min_res, cfg.max_res, cfg.step)[0])
+        except ValueError as e:
+            raise lib.PpmError(str(e))
+    if on_dev:
+        import torch
+        out = torch.empty_like(maps[0])
+        if call.keep_levels:
+            energies = torch.empty((call.keep_levels,) + shape + (2,), dtype=torch.float32, device=maps[0].device)
+        keep = [_volumes_arg(m, 1, n) for m in maps + [out]]
+        ptrs = [k[0] for k in keep]
+        pe = C.c_void_p(energies.data_ptr()) if energies is not None else None
+    else:
+        out = np.empty_like(maps[0])
+        if call.keep_levels:
+            energies = np.empty((call.keep_levels,) + shape + (2,), dtype=np.float32)
+        ptrs = [lib.ptr(m) for m in maps + [out]]
+        pe = lib.ptr(energies) if energies is not None else None
+    info = LocresInfo()
+    lib.check(lib.load().ppm_local_resolution(C.byref(call), ptrs[0], ptrs[1], ptrs[2] if mask is not None else None, 1 if on_dev else 0, n,
+                                              ptrs[-1], pe, C.byref(info)))
+    L = info.n_levels
+    res = dict(resolution=out, levels=np.array(info.levels[:L], dtype=np.float32), tau=np.array(info.tau[:L], dtype=np.float32),
+               counts=np.array(info.counts[:L], dtype=np.int64), info=info)
+    if energies is not None:
+        res["energies"] = energies
+    return res
 
 
 class PinnedBuffer:

@@ -17,7 +17,7 @@ EXPORTS = [
     "ppm_finalize", "ppm_profile_enable", "ppm_profile_reset", "ppm_profile_get", "ppm_device_alloc",
     "ppm_device_free", "ppm_device_upload", "ppm_device_sync", "ppm_extract_boxes", "ppm_host_alloc", "ppm_host_free", "ppm_host_read",
     "ppm_comm_unique_id", "ppm_comm_create", "ppm_comm_count", "ppm_comm_destroy", "ppm_accum_reduce", "ppm_sva_insert", "ppm_sva_align_average", "ppm_mask_volume",
-    "ppm_create_mask", "ppm_postprocess",
+    "ppm_create_mask", "ppm_postprocess", "ppm_local_resolution",
 ]
 
 
@@ -88,6 +88,7 @@ def load():
     L.ppm_mask_volume.argtypes = [vp, vp, ci, ci, vp, vp]; L.ppm_mask_volume.restype = ci
     L.ppm_create_mask.argtypes = [vp, ci, ci, vp, vp, vp]; L.ppm_create_mask.restype = ci
     L.ppm_postprocess.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]; L.ppm_postprocess.restype = ci
+    L.ppm_local_resolution.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp]; L.ppm_local_resolution.restype = ci
     _lib = L
     return L
 

@@ -10,7 +10,8 @@ from .formats.cistem import COL
 
 
 def iteration(vol, stack, rows, refine_cfg, *, pixel_size, molecular_mass_kda, symmetry="C1", keep_fraction=1.0,
-              score_weight_bfactor=0.0, outer_radius=None, split_by_pind=False, mask=None, mask_cfg=None, auto_mask=None, postprocess=None):
+              score_weight_bfactor=0.0, outer_radius=None, split_by_pind=False, mask=None, mask_cfg=None, auto_mask=None, postprocess=None,
+              local_resolution=None):
     """vol: current reference (N^3 float32); stack: [M, N, N] float32 (numpy or a CUDA torch tensor); rows: [M, 32].
     mask (N^3 float32, of the same kind as vol) with mask_cfg (abi.MaskCfg; default: PYP's edge of 3 voxels, weight 0): the
     reference is shape-masked on the device first, as `shape_mask_reference` (align/core.py:783-856) does with apply_mask.exe.
@@ -18,6 +19,9 @@ def iteration(vol, stack, rows, refine_cfg, *, pixel_size, molecular_mass_kda, s
     `cistem_mask_create`, inout/image/core.py:1538-1605) and applied with mask_cfg.
     postprocess (abi.PostCfg): the half maps go through host.postprocess (the work of the Post-processing block, pyp_main.py:6601-6865)
     and its result is added as "post"; a cfg with mask "external" uses `mask` (or the one auto_mask made).
+    local_resolution (abi.LocresCfg): the half maps go through host.local_resolution (the work of ResMap in the same block,
+    pyp_main.py:6815-6844) and its result is added as "local_resolution"; `mask` (or the one auto_mask made), where there is one, says
+    which voxels are inside.
     Returns dict(rows=refined table incl. OCC after selection, half1, half2, filtered, stats=[N/2-1, 7] statistics table).
     """
     n = int(refine_cfg.box)
@@ -28,6 +32,7 @@ def iteration(vol, stack, rows, refine_cfg, *, pixel_size, molecular_mass_kda, s
             raise ValueError("ERROR: iteration: auto_mask and mask exclude each other")
         mask, _ = host.create_mask(vol, auto_mask)
     post_mask = mask if postprocess is not None and postprocess.mask_mode == 1 else None
+    locres_mask = mask if local_resolution is not None else None
     if mask is not None:
         vol = host.mask_volume(vol, mask, mask_cfg if mask_cfg is not None else MaskCfg.make(pixel_size=pixel_size))
         if getattr(vol, "is_cuda", False):          # map and mask were device tensors: Reference takes a host array
@@ -57,4 +62,8 @@ def iteration(vol, stack, rows, refine_cfg, *, pixel_size, molecular_mass_kda, s
         if getattr(post_mask, "is_cuda", False):      # the half maps are host arrays
             post_mask = post_mask.cpu().numpy()
         result["post"] = host.postprocess(h1, h2, postprocess, mask=post_mask)
+    if local_resolution is not None:
+        if getattr(locres_mask, "is_cuda", False):
+            locres_mask = locres_mask.cpu().numpy()
+        result["local_resolution"] = host.local_resolution(h1, h2, local_resolution, mask=locres_mask)
     return result

@@ -13,7 +13,7 @@ import time
 
 import numpy as np
 
-from ..abi import CreateMaskCfg, FinalCfg, MaskCfg, PostCfg, ReconCfg, RefineCfg
+from ..abi import CreateMaskCfg, FinalCfg, LocresCfg, MaskCfg, PostCfg, ReconCfg, RefineCfg, locres_levels
 from ..formats import cistem, mrc, parfile
 from . import prompts
 
@@ -1023,4 +1023,102 @@ def postprocessing_main(argv=None, backend=None):
     print(f"Timing: inputs {t1 - t0:.2f} s, device {t2 - t1:.2f} s, outputs {time.time() - t2:.2f} s")
     _release_warm()
     print("\nPostprocessing: Normal termination\n", flush=True)
+    return 0
+
+
+# ------------------------------------------------------------------------------------------ ResMap
+def format_chimera_script(half1, half2, resmap, lo, hi):
+    """<half1 stem>_ori_resmap_chimera.cmd: the mean of the half maps coloured by the resolution map over the level range.  PYP only logs it
+    (src/pyp_main.py:6840-6843)."""
+    return "\n".join([f"open {half1}", f"open {half2}", "vop add #0,1 modelId 2", "vop scale #2 factor 0.5 modelId 3", "close #0,1,2",
+                      f"open {resmap}", "volume #0 hide", f"scolor #3 volume #0 cmap rainbow cmapRange {lo:g},{hi:g}",
+                      f"colorkey 0.2,0.14 0.8,0.1 tickMarks True rainbow {lo:g} {hi:g}"]) + "\n"
+
+
+def resmap_main(argv=None, backend=None):
+    """ResMap --noguiSplit as the Post-processing block runs it (src/pyp_main.py:6815-6844): the half maps are read in full; the
+    resolution map (float32, in A, 100 where nothing was assigned, the pixel size in its header) and the Chimera script appear under the
+    names PYP looks for only when complete, the map last.  backend: what computes (half1, half2, LocresCfg, mask) -> the dict of
+    host.local_resolution; default host.local_resolution on the GPU, under the per-GPU lock."""
+    t0 = time.time()
+    try:
+        d = prompts.parse_resmap(sys.argv[1:] if argv is None else argv)
+    except prompts.PromptError as e:
+        _die(str(e))
+    print("\n        **   Welcome to ResMap (MI355X / libpypmatch)   **\n")
+    for k, v in d.items():
+        print(f"{k:28s}: {v}")
+    inputs = [d["half1"], d["half2"]] + ([d["maskVol"]] if d["maskVol"] is not None else [])
+    for p in inputs:
+        if not os.path.exists(p):
+            _die(f"ERROR: resmap: input file {p} does not exist")
+    try:
+        vols = [mrc.read(p).astype(np.float32) for p in inputs]
+        px = d["vxSize"] if d["vxSize"] is not None else float(mrc.read_header(d["half1"])["pixel_size"])
+    except (IOError, ValueError) as e:
+        _die(str(e))
+    if vols[0].ndim != 3 or len(set(vols[0].shape)) != 1:
+        _die(f"ERROR: resmap: the first half map is {vols[0].shape}, only cubic maps are supported")
+    for p, v in zip(inputs[1:], vols[1:]):
+        if v.shape != vols[0].shape:
+            _die(f"ERROR: resmap: {inputs[0]} is {vols[0].shape}, {p} is {v.shape}")
+    n = vols[0].shape[0]
+    if not prompts.postprocessing_box_ok(n):
+        _die(f"ERROR: resmap: the box must be even, 32..512, with prime factors 2, 3, 5, 7, got {n}")
+    try:
+        locres_levels(n, px, d["minRes"], d["maxRes"], d["stepRes"])        # the refusals of the level grid, ahead of the device
+        cfg = LocresCfg.make(pixel_size=px, p_value=d["pVal"], min_res=d["minRes"], max_res=d["maxRes"], step=d["stepRes"])
+    except ValueError as e:
+        _die(str(e))
+    mask = vols[2] if len(vols) > 2 else None
+    t1 = time.time()
+    try:
+        if backend is not None:
+            res = backend(vols[0], vols[1], cfg, mask)
+        else:
+            from .. import host, lib
+            dev = int(os.environ.get("PPM_DEVICE", "0"))
+            try:
+                with gpu_lock(dev):
+                    res = host.local_resolution(vols[0], vols[1], cfg, mask=mask, device=dev)
+            except lib.PpmError as e:
+                _die(str(e))
+    except ValueError as e:
+        _die(str(e))
+    t2 = time.time()
+    info = res["info"]
+    L = info.n_levels
+    out_map, out_cmd = prompts.resmap_output_names(d["half1"])
+    files = [(out_cmd, format_chimera_script(d["half1"], d["half2"], out_map, float(info.levels[0]), float(info.levels[L - 1]))),
+             (out_map, res["resolution"])]
+    tmps = []
+    try:
+        for path, what in files:
+            tmp = path + ".tmp%d" % os.getpid()
+            tmps.append(tmp)
+            if isinstance(what, str):
+                with open(tmp, "w") as f:
+                    f.write(what)
+            else:
+                mrc.write(np.asarray(what, dtype=np.float32), tmp, pixel_size=px)
+        for (path, _), tmp in zip(files, tmps):
+            os.replace(tmp, path)
+    except OSError as e:
+        for tmp in tmps:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+        _die(f"ERROR: resmap: could not write {out_map}: {e}")
+    print(f"\nLocal resolution of two {n}^3 half maps at {px:g} A/pixel: p-value {d['pVal']:g}, {info.n_inside} voxels inside the mask, "
+          f"{L} levels, {info.transforms} transforms")
+    print("   level (A)      threshold   voxels assigned")
+    for i in range(L):
+        print("%12.3f %14.6g %17d" % (info.levels[i], info.tau[i], info.counts[i]))
+    print(f"Median level (inside the mask) : {info.median:g} A" + ("  (100 = unassigned)" if info.median >= 100 else ""))
+    print(f"Unassigned                     : {info.unassigned} voxels ({100.0 * info.unassigned / max(info.n_inside, 1):.2f} % of the inside)")
+    notes = info.notes.decode() if isinstance(info.notes, bytes) else str(info.notes)
+    if notes:
+        print(f"Notes                          : {notes}")
+    print(f"Timing: inputs {t1 - t0:.2f} s, device {t2 - t1:.2f} s, outputs {time.time() - t2:.2f} s")
+    _release_warm()
+    print("\nResMap: Normal termination\n", flush=True)
     return 0

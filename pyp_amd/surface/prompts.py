@@ -5,7 +5,7 @@ booleans (src/pyp/refine/frealign/frealign.py:3918-3994 refine3d, :1780-1824 rec
 :1878-1888 local_merge3d, :2075-2093 merge3d; src/pyp/align/core.py:811-850 apply_mask.exe; src/pyp/inout/image/core.py:1583-1596
 create_mask; the `.par`-surface refine3d script
 is preserved at src/pyp/system/wrapper_functions.py:512-561).  Answer order: SURVEY.md §9.1-§9.3.
-postprocessing.py alone takes a command line (src/pyp_main.py:6638-6737): parse_postprocessing.
+postprocessing.py and ResMap take command lines (src/pyp_main.py:6638-6737, :6826): parse_postprocessing, parse_resmap.
 """
 
 
@@ -344,6 +344,74 @@ def parse_postprocessing(argv):
     if d["refine_res_lim"] is not None:
         d["refine_res_lim"] = _num(d["refine_res_lim"], "refine_res_lim")
     return d
+
+
+RESMAP_FLAGS = ("noguiSplit", "noguiSingle", "doBenchMarking")
+RESMAP_VALUES = ("vxSize", "pVal", "minRes", "maxRes", "stepRes", "maskVol")
+RESMAP_DEFAULTS = dict(pVal=0.05, minRes=0.0, maxRes=0.0, stepRes=1.0)      # tabs.sharpen.resmap_* (config/pyp_config.toml:9222-9248)
+RESMAP_MIN_STEP = 0.25
+
+
+def parse_resmap(argv):
+    """ResMap as PYP's Post-processing block starts it (src/pyp_main.py:6826): `--noguiSplit --vxSize A --doBenchMarking --pVal P
+    --minRes=V --maxRes=V --stepRes=V [--maskVol F] half1 half2`.  A value may follow its option or be joined to it by `=` (that line
+    mixes both).  --noguiSplit is required, --noguiSingle (one map, no halves) is refused, --doBenchMarking is accepted and ignored;
+    --vxSize may be left out (the header's pixel size is used then).  Refused here: what can be told from the command line alone."""
+    prog = "resmap"
+    d = {k: False for k in RESMAP_FLAGS}
+    d.update({k: None for k in RESMAP_VALUES})
+    pos = []
+    a = list(argv)
+    i = 0
+    while i < len(a):
+        tok = a[i]
+        i += 1
+        if not tok.startswith("--"):
+            pos.append(tok)
+            continue
+        name, eq, val = tok[2:].partition("=")
+        if name in RESMAP_FLAGS:
+            if eq:
+                raise PromptError(f"ERROR: {prog}: option --{name} takes no value")
+            d[name] = True
+        elif name in RESMAP_VALUES:
+            if not eq:
+                if i >= len(a):
+                    raise PromptError(f"ERROR: {prog}: option --{name} needs a value")
+                val = a[i]
+                i += 1
+            if d[name] is not None:
+                raise PromptError(f"ERROR: {prog}: option --{name} given twice")
+            d[name] = val
+        else:
+            raise PromptError(f"ERROR: {prog}: unknown option '{tok}'")
+    if d["noguiSingle"]:
+        raise PromptError(f"ERROR: {prog}: --noguiSingle (one map) is not supported by this build; the noise is taken from two half maps (--noguiSplit)")
+    if not d["noguiSplit"]:
+        raise PromptError(f"ERROR: {prog}: --noguiSplit is required (this build has no graphical mode)")
+    if len(pos) != 2:
+        raise PromptError(f"ERROR: {prog}: expected the two half maps, got {len(pos)} positional arguments")
+    d["half1"], d["half2"] = pos
+    if d["vxSize"] is not None:
+        d["vxSize"] = _num(d["vxSize"], "vxSize")
+        if not d["vxSize"] > 0:
+            raise PromptError(f"ERROR: {prog}: --vxSize must be positive, got '{d['vxSize']:g}'")
+    for k, v in RESMAP_DEFAULTS.items():
+        d[k] = v if d[k] is None else _num(d[k], k)
+    if not 0 < d["pVal"] < 1:
+        raise PromptError(f"ERROR: {prog}: --pVal must lie strictly between 0 and 1, got '{d['pVal']:g}'")
+    if not d["minRes"] >= 0 or not d["maxRes"] >= 0:
+        raise PromptError(f"ERROR: {prog}: --minRes and --maxRes must not be negative (0 = the default)")
+    if not d["stepRes"] >= RESMAP_MIN_STEP:
+        raise PromptError(f"ERROR: {prog}: --stepRes must be at least {RESMAP_MIN_STEP:g} A, got '{d['stepRes']:g}'")
+    return d
+
+
+def resmap_output_names(half1):
+    """(<half1 without suffix>_ori_resmap<suffix>, <half1 without suffix>_ori_resmap_chimera.cmd): where src/pyp_main.py:6831-6843 looks."""
+    import os
+    stem, suffix = os.path.splitext(half1)
+    return stem + "_ori_resmap" + suffix, stem + "_ori_resmap_chimera.cmd"
 
 
 def dump_name(seed, k):
