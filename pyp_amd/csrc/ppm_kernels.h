@@ -14,6 +14,8 @@
 #include "ppm_dev.h"
 #include "ppm_geom.h"
 #include "ppm_rows.h"
+#include "ppm_window.h"
+#include <type_traits>
 
 namespace ppm {
 
@@ -889,10 +891,14 @@ __global__ void __launch_bounds__(global_threads(R)) k_global(GlobP P) {
     static_assert(!kFold || U == 4, "a step is one quad of rows");
     const int plain_rows = kFold ? 4 * P.rows.plain_steps : HsP;     // the rest of the slice's rows are quads
     float2 *Wl = (float2 *)smem;                                    // [NQ][nsampP]
+    // The register-held window of a full-wave slice is summed over kx with the columns kx and kx + 32 folded first (ppm_window.h): Ns is
+    // 128 there (bands beyond 32 pixels), and the x twiddles are those of column lane & 31.
+    constexpr bool kXFold = !TWO && HALF && NS * NS <= 64;
+    const int kxt = kXFold ? lane & 31 : kxl;
     float txc[R + 1], txs[R + 1];      // per-lane x twiddles e^{+2 pi i kx j / Ns}
 #pragma unroll
     for (int j = 0; j <= R; j++) {
-        float2 t = P.twN[(kxl * j) & (Ns - 1)];
+        float2 t = P.twN[(kxt * j) & (Ns - 1)];
         txc[j] = t.x; txs[j] = t.y;
     }
     const RowTwPtr c_rowtw = (RowTwPtr)P.rowtw;
@@ -939,18 +945,24 @@ __global__ void __launch_bounds__(global_threads(R)) k_global(GlobP P) {
         const float2 *Pp = P.bank + (size_t)msl * nsampP;         // wave-uniform base (per half when TWO), column added as a 32-bit offset
         const float2 *Pnext = P.bank + (size_t)my_slice(sl + NW < nsl ? sl + NW : sl) * nsampP;
         // accumulators (packed re/im pairs) per particle: s* = sum over rows (shift row 0); per j: even part x cos (ua, ub),
-        // odd part x sin (va, vb)
+        // odd part x sin (va, vb).  The default shape never clears them: the first pair of a slice WRITES them (a slice starts with a plain
+        // step at every band).  Wider windows keep the clears and the plain trip loop: the peeled first trip cost R = 4 31 registers and its tenants
+        // (ppm_overlap.h), and R = 6 spilled.
+        constexpr bool kSetFirst = R <= 3;
         v2f sa[NQ], sb[NQ], ua[NQ][R], ub[NQ][R], va[NQ][R], vb[NQ][R];
+        if constexpr (!kSetFirst) {
 #pragma unroll
-        for (int q = 0; q < NQ; q++) {
-            sa[q] = sb[q] = (v2f){ 0.f, 0.f };
+            for (int q = 0; q < NQ; q++) {
+                sa[q] = sb[q] = (v2f){ 0.f, 0.f };
 #pragma unroll
-            for (int j = 0; j < R; j++) { ua[q][j] = ub[q][j] = va[q][j] = vb[q][j] = (v2f){ 0.f, 0.f }; }
+                for (int j = 0; j < R; j++) { ua[q][j] = ub[q][j] = va[q][j] = vb[q][j] = (v2f){ 0.f, 0.f }; }
+            }
         }
         // U rows per step; the rows of the next step are prefetched into the other register set (ping-pong: no copies).
         // B = Im(P) (Wx, Wy) is accumulated instead of Bq = Im(P) (Wy, -Wx) (no swizzled copy of W per row): component swap
         // and sign commute with the row sums and are applied once per slice below (Bq.x = B.y, Bq.y = -B.x).
-        auto step = [&](int row0, const float2 (&cur)[U], float2 (&nxt)[U]) {
+        auto step = [&](auto first, int row0, const float2 (&cur)[U], float2 (&nxt)[U]) {
+            constexpr bool kFirst = decltype(first)::value;                              // the slice's first step: its first pair sets the accumulators
             {
                 const float2 *np = (row0 + U < HsP) ? Pp + (row0 + U) * 64 : Pnext;     // scalar base; the row offsets below fit the 12-bit immediate
 #pragma unroll
@@ -983,13 +995,18 @@ __global__ void __launch_bounds__(global_threads(R)) k_global(GlobP P) {
                     const v2f wav = { wa[q].x, wa[q].y }, wbv = { wb[q].x, wb[q].y };
                     const v2f aa = wav * pax, ab = wbv * pbx, ba = wav * pay, bb = wbv * pby;
                     const v2f as2 = aa + ab, ad2 = aa - ab, bs2 = ba + bb, bd2 = ba - bb;
-                    sa[q] += as2; sb[q] += bs2;
+                    if (kFirst && u == 0) { sa[q] = as2; sb[q] = bs2; } else { sa[q] += as2; sb[q] += bs2; }
 #pragma unroll
                     for (int j = 0; j < R; j++) {
                         const v4f t = tw[j];                                          // wave-uniform -> SGPRs {c, c, s, s}
                         const v2f tc = { t.x, t.y }, ts = { t.z, t.w };
-                        ua[q][j] += as2 * tc; ub[q][j] += bs2 * tc;
-                        va[q][j] += ad2 * ts; vb[q][j] += bd2 * ts;
+                        if (kFirst && u == 0) {
+                            ua[q][j] = as2 * tc; ub[q][j] = bs2 * tc;
+                            va[q][j] = ad2 * ts; vb[q][j] = bd2 * ts;
+                        } else {
+                            ua[q][j] += as2 * tc; ub[q][j] += bs2 * tc;
+                            va[q][j] += ad2 * ts; vb[q][j] += bd2 * ts;
+                        }
                     }
                 }
 #pragma unroll
@@ -1040,10 +1057,18 @@ __global__ void __launch_bounds__(global_threads(R)) k_global(GlobP P) {
         };
         __builtin_amdgcn_s_setprio(3);
         // plain steps, then quads; two steps per trip (the prefetch ping-pong), an odd count of plain steps shares a trip with the first quad
+        // kSetFirst: the first trip is peeled.  HsP is a multiple of 2 U and at least one step is plain, so it is (first step, plain step or quad).
+        constexpr std::true_type kSets = {}; constexpr std::false_type kAdds = {};
         int row0 = 0;
-        for (; row0 + 2 * U <= plain_rows; row0 += 2 * U) { step(row0, pv, pn); step(row0 + U, pn, pv); }
+        if constexpr (kSetFirst) {
+            step(kSets, 0, pv, pn);
+            if (!kFold || 2 * U <= plain_rows) step(kAdds, U, pn, pv);
+            else qstep(U, pn, pv);
+            row0 = 2 * U;
+        }
+        for (; row0 + 2 * U <= plain_rows; row0 += 2 * U) { step(kAdds, row0, pv, pn); step(kAdds, row0 + U, pn, pv); }
         if constexpr (kFold) {
-            if (row0 < plain_rows) { step(row0, pv, pn); qstep(row0 + U, pn, pv); row0 += 2 * U; }
+            if (row0 < plain_rows) { step(kAdds, row0, pv, pn); qstep(row0 + U, pn, pv); row0 += 2 * U; }
             for (; row0 < HsP; row0 += 2 * U) { qstep(row0, pv, pn); qstep(row0 + U, pn, pv); }      // HsP is a multiple of 2 U
         }
         __builtin_amdgcn_s_setprio(0);          // the reduction tail is a chain of dependent cross-lane steps: let it issue first
@@ -1064,37 +1089,56 @@ __global__ void __launch_bounds__(global_threads(R)) k_global(GlobP P) {
                 // both orientations of the stored slice at once, in the halves of packed registers (.x: psi, sg = +1; .y: psi + 180 deg,
                 // sg = -1): Q = A + sg Bq, U = ua + sg ub, V = va + sg vb; G(+j) = U + iV, G(-j) = U - iV;
                 // value(iy, ix) = Re(G[iy] e^{+2 pi i kx (ix-R)/Ns})
+                // The sum over kx folds the columns kx and kx + 32 first (ppm_window.h): the window rows go in pairs, a 32-lane swap per
+                // register brings the column pair (G, G') of row 2 s into lanes 0-31 and that of row 2 s + 1 into lanes 32-63; S = G + G',
+                // D = G - G', P = G + iG', Q = G - iG' take the x twiddles of column lane & 31 (shift j: i^j G' joins G), and each half
+                // reduces the (R + 1) NS values of its rows over its own 32 lanes.
                 const v2f sg2 = { 1.f, -1.f };
-                v2f val[NS * NS];
+                constexpr int NV = win_values(R);
+                v2f gxr[NS], gyr[NS], val[NV];
 #pragma unroll
                 for (int iy = 0; iy < NS; iy++) {
                     const int jy = iy - R, ja = jy < 0 ? -jy : jy;
-                    v2f gx, gy;
-                    if (jy == 0) { gx = sax + sg2 * sbx; gy = say + sg2 * sby; }
+                    if (jy == 0) { gxr[iy] = sax + sg2 * sbx; gyr[iy] = say + sg2 * sby; }
                     else {
                         const v2f ux = uax[ja - 1] + sg2 * ubx[ja - 1], uy = uay[ja - 1] + sg2 * uby[ja - 1];
                         const v2f vx = vax[ja - 1] + sg2 * vbx[ja - 1], vy = vay[ja - 1] + sg2 * vby[ja - 1];
-                        gx = jy > 0 ? ux - vy : ux + vy; gy = jy > 0 ? uy + vx : uy - vx;
-                    }
-                    val[iy * NS + R] = gx;
-#pragma unroll
-                    for (int j = 1; j <= R; j++) {
-                        const v2f pc = gx * txc[j], qs = gy * txs[j];
-                        val[iy * NS + R + j] = pc - qs;
-                        val[iy * NS + R - j] = pc + qs;
+                        gxr[iy] = jy > 0 ? ux - vy : ux + vy; gyr[iy] = jy > 0 ? uy + vx : uy - vx;
                     }
                 }
-                const v2f tot = reduce_halving2<NS * NS>(val, lane);
-                const int vi = (int)(__brev((unsigned)lane) >> 26);            // the value index this lane ended up with
-                const int iy = vi / NS, ix = vi - iy * NS;
-                const int ay = iy - R < 0 ? R - iy : iy - R, ax = ix - R < 0 ? R - ix : ix - R;
-                const bool inwin = vi < NS * NS && ax <= P.RSx && ay <= P.RSy;
+#pragma unroll
+                for (int s = 0; s < win_slots(R); s++) {
+                    const int ra = 2 * s, rb = ra + 1 < NS ? ra + 1 : ra;        // the last row has no partner: its upper half never competes
+                    float ax0 = gxr[ra].x, ax1 = gxr[ra].y, ay0 = gyr[ra].x, ay1 = gyr[ra].y;
+                    float bx0 = gxr[rb].x, bx1 = gxr[rb].y, by0 = gyr[rb].x, by1 = gyr[rb].y;
+                    lane_swap<32>(ax0, bx0); lane_swap<32>(ax1, bx1); lane_swap<32>(ay0, by0); lane_swap<32>(ay1, by1);
+                    const v2f gx = { ax0, ax1 }, gy = { ay0, ay1 }, hx = { bx0, bx1 }, hy = { by0, by1 };      // G and G' of this half's row
+                    const v2f Sx = gx + hx, Dx = gx - hx, Dy = gy - hy, Px = gx - hy, Py = gy + hx, Qx = gx + hy, Qy = gy - hx;
+                    val[s * NS + R] = Sx;
+#pragma unroll
+                    for (int j = 1; j <= R; j++) {
+                        static_assert(R <= 3, "j = 4 would take S_y");
+                        if (j == 2) {
+                            const v2f pc = Dx * txc[j], qs = Dy * txs[j];
+                            val[s * NS + R + j] = pc - qs;
+                            val[s * NS + R - j] = pc + qs;
+                        } else {
+                            const v2f &px = j == 1 ? Px : Qx, &py = j == 1 ? Py : Qy, &mx = j == 1 ? Qx : Px, &my = j == 1 ? Qy : Py;
+                            val[s * NS + R + j] = px * txc[j] - py * txs[j];
+                            val[s * NS + R - j] = mx * txc[j] + my * txs[j];
+                        }
+                    }
+                }
+                const v2f tot = reduce_halving2h<NV>(val, lane);
+                int iy = 0, ix = 0;                                             // the window position this lane ended up with
+                const bool inwin = win_valid(R, win_lane_value(lane), win_lane_half(lane), P.RSx, P.RSy, iy, ix);
+                const int vi = win_key(R, iy, ix);
 #pragma unroll
                 for (int e = 0; e < 2; e++) {
                     const float cand = inwin ? (e ? tot.y : tot.x) : -3.0e38f;
                     // arg-max over lanes; ties -> lower (sy, sx) index like the oracle's scan order
                     const float best = wave_max(cand);
-                    int ci = wave_min(cand == best ? vi : 64);
+                    int ci = wave_min(cand == best && inwin ? vi : 64);
                     if (ci > 63) ci = 0;                                         // no comparable value (NaN scores)
                     const int bsy_ = ci / NS - R, bsx_ = ci - (ci / NS) * NS - R;
                     if (lane == 0 && (q == 0 || p0 + q < P.n)) {
