@@ -290,6 +290,35 @@ int ppm_csp_search_plan(const ppm_refine_cfg *cfg, const ppm_csp_cfg *csp, ppm_c
  * 0 for a particle that was not searched, negative on error. */
 int ppm_csp_search_candidates(ppm_ref_t *ref, long unit, int max_k, long *rot_index, long *shift_index, double *score);
 
+/* Movie-frame refinement (the `csp` program with its refine-frames flag, src/pyp/system/local_run.py:330-376; csp_frame_refinement,
+ * config/pyp_config.toml:6473-6478): one shift per frame row from score maps pooled over the neighbouring frames.  Build-defined
+ * (DESIGN.md section 8).  A GROUP is the set of rows with equal (PIND, TIND), ordered by FIND; a = pixel size, N = box.
+ *   own map   S_r(d) = the local score of ppm_refine_batch at row r's pose and defocus with its shift moved by d, ALL RINGS SIGNED
+ *             (cfg->res_signed_cc is ignored), over res_low .. res_high, for d = (jx, jy) h, |jx|, |jy| <= W, stored row-major (jy, jx)
+ *   grid      h = step_px (0 = 0.5 pixel), W = min(ceil(range_px / h - 1e-6), PPM_FRAME_MAX_STEPS); a range that is cut sets
+ *             info->clipped and ppm_refine_note() says so
+ *   pooled    P_r(d) = sum g(FIND_r' - FIND_r) S_r'(d) / sum g over the rows r' of r's group with OCCUPANCY > 0 and |FIND_r' - FIND_r| <=
+ *             half_width, g(D) = exp(-D^2 / (2 (half_width / 2)^2)), added in ascending FIND; half_width 0: P_r = S_r
+ *   peak      the arg-max of P_r in row-major order, ties to the lower index; per axis, where the arg-max is not on the window's edge and
+ *             l - 2c + r < 0 for its two neighbours l, r, plus (l - r) / (2 (l - 2c + r)) h.  The result is delta_r, pixels
+ *   groups with TIND in first..last (last < 0: to the end) AND in tind_min..tind_max (tind_max < 0: no limit): X_SHIFT, Y_SHIFT, FSHIFT_X and
+ *             FSHIFT_Y all move by delta_r a; SCORE = 100 S_r at the arg-max grid point; LOGP and SIGMA stay
+ *   groups in first..last outside tind_min..tind_max are scored only: SCORE = 100 S_r(0), nothing else changes
+ *   rows with OCCUPANCY <= 0, and rows of other groups, are returned unchanged and enter no pool
+ * rows / rows_out: n_rows x PPM_NCOL doubles (host), image i belongs to row i; the rows may come in any order and a call may hold any
+ * subset of the groups: a group's result depends on its own rows alone.  own_maps / pooled_maps (NULL: not wanted): n_rows x (2W + 1)^2
+ * floats on the host, zeros for rows without a map.  Refused with -22: a FIND that occurs twice in a group, step_px < 0, range_px <= 0,
+ * half_width < 0. */
+#define PPM_FRAME_MAX_STEPS 8
+typedef struct ppm_frame_cfg { float range_px, step_px; int half_width, tind_min, tind_max, first, last; } ppm_frame_cfg;
+/* groups with a usable row; slices gathered (one per set of frames of a group with bit-identical PSI, THETA, PHI, DEFOCUS_1, DEFOCUS_2,
+ * DEFOCUS_ANGLE, PHASE_SHIFT); rows whose shifts moved; rows scored only; rows returned unchanged; W; h; W h; whether the range was cut */
+typedef struct ppm_frame_info { long groups, models, rows_refined, rows_scored, rows_skipped; int n_steps; float step_px, range_px; int clipped; } ppm_frame_info;
+int ppm_frame_refine(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const ppm_frame_cfg *fcfg, const void *images, int images_on_device,
+                     const double *rows, int n_rows, double *rows_out, float *own_maps, float *pooled_maps, ppm_frame_info *info);
+/* The grid ppm_frame_refine would use (pure host; any output may be NULL); the same refusals. */
+int ppm_frame_plan(const ppm_frame_cfg *fcfg, float *step_px, int *n_steps, int *clipped);
+
 /* Sub-tomogram alignment (3DAVG, `external/TOMO/MPI_Classification`, driven by src/pyp/refine/tomo_avg/sub_tomo_avg.py:318-555
  * with the XML protocols of src/pyp/refine/3DAVG/): every sub-volume is aligned to the reference by a rotation + 3-D shift that
  * maximise the band-passed, missing-wedge-weighted normalised cross-correlation of its 3-D transform with the rotated

@@ -101,6 +101,33 @@ class CspSearchInfo(C.Structure):
                 ("n_rot", C.c_long), ("n_shift", C.c_long), ("n_candidates", C.c_int)]
 
 
+FRAME_MAX_STEPS = 8
+
+
+class FrameCfg(C.Structure):
+    """ppm_frame_cfg (include/ppm.h)."""
+    _fields_ = [("range_px", C.c_float), ("step_px", C.c_float), ("half_width", C.c_int), ("tind_min", C.c_int), ("tind_max", C.c_int),
+                ("first", C.c_int), ("last", C.c_int)]
+
+    @classmethod
+    def make(cls, range_px, step_px=0.0, half_width=2, tind_min=0, tind_max=-1, first=0, last=-1):
+        """range_px: shifts searched either side of a row's own, pixels; step_px: grid step (0 = half a pixel); half_width: frames pooled
+        either side (csp_running_average_frames); tind_min / tind_max: tilts whose shifts are written back, the others are scored only
+        (csp_UseImagesForRefinementMin / Max; max < 0 = no limit); first / last: tilts the call works on (last < 0 = to the end)."""
+        return cls(range_px=float(range_px), step_px=float(step_px), half_width=int(half_width), tind_min=int(tind_min), tind_max=int(tind_max),
+                   first=int(first), last=int(last))
+
+
+class FrameInfo(C.Structure):
+    """ppm_frame_info (include/ppm.h): groups with a usable row, slices gathered, rows whose shifts moved, rows scored only, rows returned
+    unchanged, grid steps either side, grid step and reach in pixels, whether the range was cut."""
+    _fields_ = [("groups", C.c_long), ("models", C.c_long), ("rows_refined", C.c_long), ("rows_scored", C.c_long), ("rows_skipped", C.c_long),
+                ("n_steps", C.c_int), ("step_px", C.c_float), ("range_px", C.c_float), ("clipped", C.c_int)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class SvaCfg(C.Structure):
     """ppm_sva_cfg (include/ppm.h)."""
     _fields_ = [("box", C.c_int), ("pixel_size", C.c_float), ("window", C.c_float * 3), ("window_sigma", C.c_float),

@@ -206,6 +206,8 @@ struct ppm_ref {
     // ppm_csp_search_candidates answers from (the last call's candidates: PIND of every searched particle, K entries each)
     DevBuf<double> c_rowtab; DevBuf<float> c_gbest, c_cscore; DevBuf<int> c_gshift, c_cshift; DevBuf<long> c_crot;
     std::vector<long> cand_unit, cand_rot; std::vector<int> cand_shift; std::vector<float> cand_score; int cand_K = 0;
+    // movie-frame refinement (ppm_frame_refine): the frame tables, the own and pooled maps, the slice store of a band too wide for LDS
+    DevBuf<int> f_int; DevBuf<float> f_flt, f_own, f_pool; DevBuf<double> f_dbl; DevBuf<float2> f_store;
     // sub-tomogram alignment (ppm_sva_align): the transforms' work array, the band-limited transforms of a chunk, staged host volumes
     // (GBs: allocating and freeing them on every call cost ~20 ms of a 120 ms call)
     DevBuf<float2> s_f, s_g, s_F; DevBuf<float> s_vols;

@@ -28,6 +28,7 @@
 #include "ppm_defocus_plan.h"
 #include "ppm_kernels2.h"
 #include "ppm_csp_kernels.h"
+#include "ppm_frame_kernels.h"
 #include "ppm_sva_kernels.h"
 #include "ppm_gfft.h"
 #include "ppm_mask_kernels.h"
@@ -41,6 +42,7 @@ using namespace ppm;
 #include "host_refine.h"
 #include "host_recon.h"
 #include "host_csp.h"
+#include "host_frames.h"
 #include "host_sva.h"
 #include "host_mask.h"
 #include "host_label.h"

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import lib
-from .abi import NCOL, STATS_COLS, K_NAMES, CreateMaskCfg, CreateMaskInfo, FinalCfg, LocresCfg, LocresInfo, MaskCfg, PostCfg, PostInfo, ReconCfg, RefineCfg  # noqa: F401
+from .abi import NCOL, STATS_COLS, K_NAMES, CreateMaskCfg, CreateMaskInfo, FinalCfg, FrameCfg, FrameInfo, LocresCfg, LocresInfo, MaskCfg, PostCfg, PostInfo, ReconCfg, RefineCfg  # noqa: F401
 
 
 def _sync_producer(t):
@@ -96,6 +96,27 @@ class Reference:
                                             len(particles), lib.ptr(tilts), len(tilts)))
         del keep
         return rows, particles, tilts
+
+    def frame_refine(self, cfg, fcfg, images, rows, maps=False):
+        """Movie-frame refinement (ppm_frame_refine): one shift per frame row from score maps pooled over the neighbouring frames of its
+        (PIND, TIND) group.  Returns (rows_out, info dict), with maps=True (rows_out, info, own_maps, pooled_maps), both (M, 2W + 1, 2W + 1)
+        float32, row-major (jy, jx), zeros for rows without a map."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[1] != NCOL:
+            raise ValueError("ERROR: rows must be (M, 32)")
+        L = lib.load()
+        nst = C.c_int()
+        lib.check(L.ppm_frame_plan(C.byref(fcfg), None, C.byref(nst), None))
+        side = 2 * nst.value + 1
+        out = np.empty_like(rows)
+        info = FrameInfo()
+        own = np.zeros((len(rows), side, side), dtype=np.float32) if maps else None
+        pooled = np.zeros((len(rows), side, side), dtype=np.float32) if maps else None
+        p, on_dev, keep = _images_arg(images, len(rows), cfg.box)
+        lib.check(L.ppm_frame_refine(self.h, C.byref(cfg), C.byref(fcfg), p, on_dev, lib.ptr(rows), len(rows), lib.ptr(out),
+                                     lib.ptr(own) if maps else None, lib.ptr(pooled) if maps else None, C.byref(info)))
+        del keep
+        return (out, info.as_dict(), own, pooled) if maps else (out, info.as_dict())
 
     def sva_align(self, cfg, volumes, wedges, poses, accumulator=None, index=None):
         """Sub-tomogram alignment (ppm_sva_align): volumes (V, N, N, N) float32 (numpy or CUDA tensor), wedges (V, 2) tilt limits in

@@ -14,6 +14,8 @@ Modes (src/pyp/align/core.py:1015-1023 and the 2 -> 5, 3 -> 6 remaps of local_ru
        (csp_produce_running_average, align/core.py:1000-1001; merged by the caller into <name>_stack_weighted_average.mrc)
     1 / 2 / 5  particle rotations / 3-D shifts / both, particles first..last (PIND); 8 / 7 = 1 / 2 (the caller's region codes)
     0 / 3 / 6  tilt angle + axis / image shifts / both, tilts first..last (TIND; last = -1: up to the end)
+    3 with <flag> = 1, <images> = a frame list and csp_frame_refinement = true: movie-frame refinement, one shift per FRAME row of the
+       tilts first..last (align/core.py:994-1003; frames.is_frame_refinement, _refine_frames)
     4  one defocus offset per tilt (csp_ToleranceMicrographDefocus1 either side, 50 A steps), tilts first..last
 Region-based ("patch") refinement (align/core.py:1106-1151, local_run.py:327-404): <param> is one of the
 `<name>_regionNNNN.cistem` files of particle_cspt.split_parameter_file — the rows of the region's particles with RIND = the
@@ -31,7 +33,8 @@ import time
 
 import numpy as np
 
-from ..abi import CSP_MICROGRAPHS, CSP_PARTICLES, CspCfg, RefineCfg
+from ..abi import CSP_MICROGRAPHS, CSP_PARTICLES, CspCfg, FrameCfg, RefineCfg
+from ..frames import is_frame_refinement
 from ..formats import cistem, mrc
 from .cli import _die, gpu_lock
 
@@ -160,7 +163,8 @@ def csp_main(argv=None):
             _die(f"ERROR: csp: input file {pth} does not exist")
     if not param_file.endswith(".cistem"):
         _die("ERROR: csp: the parameter file must be a .cistem file")
-    s = _settings(read_flat_toml(".pyp_config.toml"))
+    project = read_flat_toml(".pyp_config.toml")
+    s = _settings(project)
     rows = cistem.read_parameters(param_file)
     ext = cistem.read_extended(ext_file)
     particles, tilts = ext["particles"], ext["tilts"]
@@ -171,6 +175,8 @@ def csp_main(argv=None):
     mode = {7: 2, 8: 1}.get(mode, mode)
     if mode not in (0, 1, 2, 3, 4, 5, 6):
         _die(f"ERROR: csp: unknown mode {mode}")
+    if is_frame_refinement(mode, flag, images, project):
+        return _refine_frames(s, rows, particles, tilts, param_file, first, last, stack, t0)
     unit = CSP_PARTICLES if mode in (1, 2, 5) else CSP_MICROGRAPHS
     key = C["PIND"] if unit == CSP_PARTICLES else C["TIND"]
     hi = last if last >= 0 else np.inf
@@ -224,6 +230,67 @@ def csp_main(argv=None):
         print("%7d%8d%6d%8.2f%8.2f%8.2f%10.2f%10.2f%10.4f" % (r[0], r[C["PIND"]], r[C["TIND"]], r[1], r[2], r[3], r[4], r[5], r[C["SCORE"]]))
     print(f"\nRefined {int(keep.sum())} {'particles' if unit == CSP_PARTICLES else 'tilts'} over {len(rout)} projections in {time.time() - t0:.1f} s; "
           f"mean score {rout[:, C['SCORE']].mean():.4f} (was {rin[:, C['SCORE']].mean():.4f})")
+    print("\nCSP: Normal termination\n", flush=True)
+    return 0
+
+
+def _refine_frames(s, rows, particles, tilts, param_file, first, last, stack, t0):
+    """Movie-frame refinement (mode 3 with the refine-frames flag, a frame list and csp_frame_refinement; frames.is_frame_refinement): one
+    shift per frame row of the tilts first..last from score maps pooled over csp_running_average_frames frames either side, searched
+    within csp_ToleranceMicrographShifts (ppm_frame_refine, DESIGN.md section 8).  X_SHIFT / Y_SHIFT and FSHIFT_X / FSHIFT_Y move together;
+    tilts outside csp_UseImagesForRefinementMin .. Max are scored only (the caller's evaluation pass).  The frame boxes come from <stack>,
+    as mode -2 cut them from the frame list."""
+    hi = last if last >= 0 else np.inf
+    sel = np.where((rows[:, C["TIND"]] >= first) & (rows[:, C["TIND"]] <= hi))[0]
+    if len(sel) == 0:
+        _die(f"ERROR: csp: no rows with TIND in {first}..{last}")
+    rin = rows[sel].copy()
+    if not os.path.exists(stack):
+        _die(f"ERROR: csp: particle stack {stack} does not exist (run mode -2 first)")
+    mm = mrc.mmap(stack)
+    pos = rin[:, C["POSITION_IN_STACK"]].astype(np.int64)
+    if pos.min() < 1 or pos.max() > mm.shape[0]:
+        _die(f"ERROR: csp: {stack} has {mm.shape[0]} images, rows ask for {int(pos.max())}")
+    imgs = np.ascontiguousarray(mm[pos - 1], dtype=np.float32)
+    box = imgs.shape[1]
+    refp = os.path.join(os.environ.get("PYP_SCRATCH", "."), f"{s['data_set']}_frames_CSP_01.mrc")
+    if not os.path.exists(refp):
+        _die(f"ERROR: csp: reference {refp} does not exist")
+    vol = mrc.read(refp).astype(np.float32)
+    if vol.shape != (box, box, box):
+        _die(f"ERROR: csp: reference is {vol.shape}, particles are {box}^2")
+    px = float(rin[0, C["PIXEL_SIZE"]]) if rin[0, C["PIXEL_SIZE"]] > 0 else s["pixel"]
+    cfg = RefineCfg.make(box=box, pixel_size=px, molecular_mass_kda=s["mw"], mask_radius=s["radius"], res_low=s["res_low"], res_high=s["res_high"],
+                         res_signed_cc=0.0, global_search=0, local_refine=1, normalize=s["normalize"], invert=s["invert"])
+    if s["running_frames"] < 0:
+        _die(f"ERROR: csp: csp_running_average_frames = {s['running_frames']} must not be negative")
+    fc = FrameCfg.make(range_px=s["tol_m_shift"] / px, step_px=0.0, half_width=s["running_frames"], tind_min=s["tind_min"], tind_max=s["tind_max"],
+                       first=first, last=last)
+    from .. import host, lib
+    dev = int(os.environ.get("PPM_DEVICE", "0"))
+    try:
+        with gpu_lock(dev):
+            ref = host.Reference(vol, box / 2, device=dev)
+            rout, info = ref.frame_refine(cfg, fc, imgs, rin)
+            note = ref.note()
+            ref.close()
+    except (lib.PpmError, ValueError) as e:
+        _die(str(e))
+    side = 2 * info["n_steps"] + 1
+    print(f"\nFrame refinement: shifts within +-{info['range_px']:g} pixels on a grid of {side} x {side} points, {info['step_px']:g} pixels apart; "
+          f"maps pooled over +-{fc.half_width} frames; tilts {fc.tind_min}..{fc.tind_max} are refined, the others scored")
+    if note:
+        print(note)
+    out_main, out_ext = _out_names(param_file, first, last)
+    keep = (tilts[:, 0] >= first) & (tilts[:, 0] <= hi)
+    cistem.write_parameters(out_main, rout)
+    cistem.write_extended(out_ext, particles, tilts[keep])
+    print("\n   ROW    PIND  TIND  FIND       SHX       SHY   FSHIFTX   FSHIFTY     SCORE")
+    for r in rout[:40]:
+        print("%7d%8d%6d%6d%10.2f%10.2f%10.2f%10.2f%10.4f" % (r[0], r[C["PIND"]], r[C["TIND"]], r[C["FIND"]], r[4], r[5], r[C["FSHIFT_X"]], r[C["FSHIFT_Y"]],
+                                                          r[C["SCORE"]]))
+    print(f"\n{info['groups']} groups, {info['models']} models; {info['rows_refined']} rows refined, {info['rows_scored']} scored, {info['rows_skipped']} skipped "
+          f"in {time.time() - t0:.1f} s; mean score {rout[:, C['SCORE']].mean():.4f} (was {rin[:, C['SCORE']].mean():.4f})")
     print("\nCSP: Normal termination\n", flush=True)
     return 0
 

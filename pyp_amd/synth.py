@@ -332,6 +332,34 @@ def make_tilt_series(n, n_part, tilt_angles, pixel=1.0, snr=0.1, vol=None, seed=
     return vol, stack, rows, particles, tilts
 
 
+def make_frame_series(n, n_part, tilt_angles, n_frames, pixel=1.0, snr=0.2, vol=None, seed=20240601, device="cpu", drift_lin=0.9, drift_quad=0.5,
+                      **kw):
+    """Movie frames of a synthetic tilt series: every row of make_tilt_series(n, n_part, tilt_angles, ...) tiled over `n_frames` frames
+    (FIND = 0 .. n_frames - 1, POSITION_IN_STACK = 1 .. M in row order, the frames of a (particle, tilt) consecutive) with a planted
+    trajectory per (particle, tilt): frame f sits at the row's shift plus a t + b (t^2 - 1/2) pixels, t = -1 .. 1 over the frames, the
+    components of a uniform in +-drift_lin and those of b in +-drift_quad.  Returns (vol, stack (M, n, n) rendered at the TRUE shifts with
+    white noise at `snr` per frame, rows (M, 32) that carry the tilt-series shift for every frame - the start of a frame refinement -,
+    true rows, particles, tilts)."""
+    vol, _, rows0, particles, tilts = make_tilt_series(n, n_part, tilt_angles, pixel=pixel, snr=snr, vol=vol, seed=seed, device=device, **kw)
+    C = cistem.COL
+    rng = np.random.default_rng(seed + 7)
+    m0, F = len(rows0), int(n_frames)
+    rows = np.repeat(rows0, F, axis=0)
+    rows[:, C["FIND"]] = np.tile(np.arange(F), m0)
+    rows[:, C["POSITION_IN_STACK"]] = np.arange(1, m0 * F + 1)
+    t = np.linspace(-1.0, 1.0, F) if F > 1 else np.zeros(1)
+    a = rng.uniform(-drift_lin, drift_lin, (m0, 2))
+    b = rng.uniform(-drift_quad, drift_quad, (m0, 2))
+    drift = a[:, None, :] * t[None, :, None] + b[:, None, :] * (t * t - 0.5)[None, :, None]          # (m0, F, 2) pixels
+    true = rows.copy()
+    true[:, C["X_SHIFT"]] += drift[..., 0].ravel() * pixel
+    true[:, C["Y_SHIFT"]] += drift[..., 1].ravel() * pixel
+    true[:, C["FSHIFT_X"]] += drift[..., 0].ravel() * pixel
+    true[:, C["FSHIFT_Y"]] += drift[..., 1].ravel() * pixel
+    stack = render_rows(vol, true, pixel, snr, seed + 2, device, 64, kw.get("particle_rad_frac", 0.32))
+    return vol, stack, rows, true, particles, tilts
+
+
 def make_subtomograms(n, n_vol, pixel=1.0, snr=0.5, vol=None, seed=20240701, wedge=(-60.0, 60.0), shift_sigma=1.5, device="cpu"):
     """Synthetic sub-tomograms of `vol`: sub-volume v has the transform ref(N_v k) e^{+2 pi i k.p_v / n} inside the measured
     wedge (tilt axis y, tilt range `wedge` degrees), zero in the missing wedge, plus white noise.  Returns (vol, volumes
