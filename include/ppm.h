@@ -268,6 +268,11 @@ int ppm_refine_last_sections(ppm_ref_t *ref);
  * order (one chunk, a search by transform, tiles or sections, no grid search, no room on a compute unit, or PPM_REFINE_OVERLAP=0).
  * The result does not depend on it. */
 int ppm_refine_last_overlap(ppm_ref_t *ref);
+/* Tap reuse in the full-band local refinement of the last ppm_refine_batch on this reference, counted only while the environment has
+ * PPM_LOCAL_REUSE_COUNT=1 (both 0 otherwise): the cube gathers its compass sweeps made for the angular neighbours of a pose, one per
+ * lane and in-list sample, and how many of them took the centre pose's taps instead of addressing the cube (0 with
+ * PPM_LOCAL_REUSE=0).  The result does not depend on either. */
+int ppm_refine_last_reuse(ppm_ref_t *ref, long *gathers, long *reused);
 
 /* refine3d answers 8 / 43 "matching projections" (frealign.py:3929-3931, refine_fmatch): out[i] (box * box floats, host) = the
  * reference projected at row i's pose, times the row's CTF, moved to the row's X / Y shift and band-limited at cfg->res_high — the

@@ -227,6 +227,7 @@ struct ppm_ref {
     long last_counts[4] = { 0, 0, 0, 0 };
     int last_sections = 0;           // sections of the last call's grid search (0: it had none)
     int last_overlap = 0;            // hit-stage blocks per CU beside k_global in the last call (0: serial order)
+    DevBuf<unsigned long long> reuse; long last_reuse[2] = { 0, 0 };    // tap reuse of the last call's full-band k_local launches (PPM_LOCAL_REUSE_COUNT=1): neighbour lane-gathers, reused ones
     std::string note;
 };
 
@@ -252,6 +253,8 @@ static CubeView cube_view(const ppm_ref *ref) {
 }
 
 // tap addresses from LDS tables (ppm_dev.h) unless the tables would crowd the ring sums out of a CU (PPM_LOCAL_TABLES=0: arithmetic)
+// the compass neighbours of the full-band k_local launch take the centre pose's taps where they can (PPM_LOCAL_REUSE=0: every lane gathers)
+static bool local_reuse_wanted() { return !(getenv("PPM_LOCAL_REUSE") && atoi(getenv("PPM_LOCAL_REUSE")) == 0); }
 static bool local_tables_wanted(int tabR) {
     return !(getenv("PPM_LOCAL_TABLES") && atoi(getenv("PPM_LOCAL_TABLES")) == 0) && cube_tab_bytes(tabR) <= 16 * 1024;
 }

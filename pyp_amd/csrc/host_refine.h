@@ -161,7 +161,8 @@ namespace {
 // One k_local launch of a call, the same for every chunk: LocalP but for the chunk's pointers (Il, cw, states: launch_local takes them from
 // the chunk's Lane), the threads of a block, the poses per particle (blocks = particles x per_particle) and the in-band samples summed
 // over the launch's score evaluations of one particle
-struct LocalLaunch { LocalP P = {}; int threads = 0, per_particle = 1; double evals = 0; };
+// near: the launch runs k_local's tap-reusing instance (the full-band launch; P.near_it says in which iterations it reuses)
+struct LocalLaunch { LocalP P = {}; int threads = 0, per_particle = 1; double evals = 0; bool near = false; };
 // what a ppm_refine_batch call works out before its chunk loop; the loop's stages read it and write none of it
 struct RefineRun {
     ppm_ref *ref = nullptr; const ppm_refine_cfg *cfg = nullptr;
@@ -186,6 +187,7 @@ struct RefineRun {
     double sample_evals = 0;            // in-band samples summed over all k_local score evaluations of one particle
     // the local stage of chunk i on a second stream beside the search of chunk i + 1 (ppm_overlap.h)
     bool overlap = false; int tenants = 0;
+    unsigned long long *reuse = nullptr;    // PPM_LOCAL_REUSE_COUNT=1: the handle's two tap-reuse counters (device), zeroed for this call
 
     int ntiles() const { return (int)(cxs.size() * cys.size()); }
     int nsec() const { return (int)secs.size(); }
@@ -530,6 +532,7 @@ static LocalLaunch with_schedule(const RefineRun &r, LocalLaunch L, double ha, d
         double rb = march_band(r.bf, r.gm.N, r.Rm_px, ha, hs, r.any_ang, r.any_sh, rcap);
         L.P.rmax2_it[t] = (float)(rb * rb); L.P.S_it[t] = r.prefix_of(rb);
         L.evals += (double)L.per_particle * r.per_iter * std::floor(kPi * rb * rb / 2);
+        if (L.near && near_reuse_pays(r.any_ang, ha, r.cv.scale, rb)) L.P.near_it |= 1u << t;
         ha *= 0.5; hs *= 0.5;
     }
     return L;
@@ -547,7 +550,7 @@ static LocalLaunch hit_launch(const RefineRun &r) {
 }
 // one pose per particle for T iterations from the steps (ha, hs), then scored at the full band
 static LocalLaunch full_band_launch(const RefineRun &r, int T, double ha, double hs) {
-    LocalLaunch L; L.P = r.base; L.threads = kFinalThreads;
+    LocalLaunch L; L.P = r.base; L.threads = kFinalThreads; L.near = local_reuse_wanted();
     L.P.T = r.cfg->local_refine ? T : 0; L.P.final_rescore = 1; L.P.nr = r.nrings;
     L = with_schedule(r, L, ha, hs, r.gm.r_hi);
     L.evals += std::floor(kPi * r.gm.r_hi * r.gm.r_hi / 2);
@@ -563,6 +566,12 @@ static LocalLaunch rows_launch(const RefineRun &r) { return full_band_launch(r, 
 // themselves cover the largest marching band of THIS launch — the coordinates its sample-list prefixes reach — so that the one-wave
 // blocks of the hit stage stay small (ppm_overlap.h).  Same entries, fewer of them.
 struct LocalShape { size_t lds; bool tab; int tabR; };
+// the instance of k_local a launch runs: plan_overlap asks the runtime about the one the hit stage really launches
+typedef void (*LocalKernel)(LocalP);
+static LocalKernel local_kernel(bool tab, bool near) {
+    if (near) return tab ? k_local<true, true> : k_local<false, true>;
+    return tab ? k_local<true, false> : k_local<false, false>;
+}
 static LocalShape local_shape(const RefineRun &r, const LocalLaunch &L) {
     const LocalP &LP = L.P;
     const size_t ring = ring_lds_bytes8(L.threads / 64, kMaxCand, LP.nr);
@@ -578,13 +587,12 @@ static LocalShape local_shape(const RefineRun &r, const LocalLaunch &L) {
 // `L` for the nb particles of the chunk in `ln`, their poses in `states`
 static void launch_local(const RefineRun &r, const LocalLaunch &L, const Lane &ln, LState *states, int nb) {
     LocalP LP = L.P;
-    LP.Il = ln.Il.p; LP.cw = ln.cw.p; LP.states = states;
+    LP.Il = ln.Il.p; LP.cw = ln.cw.p; LP.states = states; LP.reuse = L.near ? r.reuse : nullptr;
     const LocalShape s = local_shape(r, L);
     LP.tabR = s.tabR;
     const dim3 grid((unsigned)(nb * L.per_particle)), block(L.threads);
     ProfScope ps(PPM_K_LOCAL);
-    if (s.tab) hipLaunchKernelGGL(k_local<true>, grid, block, s.lds, cur_stream(), LP);
-    else hipLaunchKernelGGL(k_local<false>, grid, block, s.lds, cur_stream(), LP);
+    hipLaunchKernelGGL(local_kernel(s.tab, L.near), grid, block, s.lds, cur_stream(), LP);
 }
 
 // one section of the grid for one chunk: the section's banks (built unless they are the ones in place), slice norms -> k_gfft | one
@@ -709,7 +717,7 @@ static int plan_overlap(RefineRun &r, int n_img) {
     const LocalShape ls = local_shape(r, r.hit);
     hipFuncAttributes ga, la;
     HIPCHK(hipFuncGetAttributes(&ga, global_kernel(r.Rwin, gm.half != 0, gm.Bs)));
-    HIPCHK(hipFuncGetAttributes(&la, ls.tab ? (const void *)k_local<true> : (const void *)k_local<false>));
+    HIPCHK(hipFuncGetAttributes(&la, (const void *)local_kernel(ls.tab, r.hit.near)));
     const OverlapKernel host = { ga.numRegs, global_threads(r.Rwin), (long)ga.sharedSizeBytes + (long)global_lds_bytes(r.HsP, r.secs[0].nd * gm.n_psi, r.Rwin, nullptr) };
     const OverlapKernel tenant = { la.numRegs, r.hit.threads, (long)la.sharedSizeBytes + (long)ls.lds };
     // gfx950 (the only device ppm_init accepts): 512 registers per lane and SIMD handed out in eights, four SIMDs, LDS in blocks of 1 280 bytes
@@ -765,6 +773,18 @@ static void refine_counts(const RefineRun &r) {
     c[1] = nl;
     c[2] = (long)std::floor(kPi * gm.r_s * gm.r_s / 2);
     c[3] = (long)evals;         // sum over the local evaluations of their in-band sample counts
+}
+
+// the call's tap-reuse counts, once its streams are drained (ppm_refine_last_reuse)
+static int read_reuse(const RefineRun &r) {
+    if (!r.reuse) return 0;
+    unsigned long long h[2] = { 0, 0 };
+    HIPCHK(hipMemcpyAsync(h, r.reuse, sizeof(h), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipStreamSynchronize(cur_stream()));
+    r.ref->last_reuse[0] = (long)h[0]; r.ref->last_reuse[1] = (long)h[1];
+    if (std::getenv("PPM_TRACE"))
+        fprintf(stderr, "ppm_refine_batch: tap reuse in the full-band stage: %llu of %llu neighbour lane-gathers (iterations 0x%x)\n", h[1], h[0], r.fin.P.near_it);
+    return 0;
 }
 
 extern "C" {
@@ -898,6 +918,13 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
     }
     HIPCHK(hipStreamSynchronize(cur_stream()));
     if (int rc = local_setup(r)) return rc;
+    ref->last_reuse[0] = ref->last_reuse[1] = 0;
+    if (const char *e = std::getenv("PPM_LOCAL_REUSE_COUNT")) if (std::atoi(e) != 0) {
+        if (int rc = ref->reuse.ensure(2)) return rc;
+        HIPCHK(hipMemsetAsync(ref->reuse.p, 0, 2 * sizeof(unsigned long long), cur_stream()));
+        HIPCHK(hipStreamSynchronize(cur_stream()));         // the second stream's launches add to it as well
+        r.reuse = ref->reuse.p;
+    }
     if (cfg->global_search) { r.hit = hit_launch(r); r.fin = final_launch(r); }
     else r.fin = rows_launch(r);
     r.sample_evals = r.hit.evals + r.fin.evals;
@@ -943,7 +970,7 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
             if (int rc = stage.sync()) return rc;
         }
         refine_counts(r);
-        return 0;
+        return read_reuse(r);
     }
     // Software pipeline over two streams and the handle's two lanes (chunk parity).  This handle's stream (A)
     // runs the front of chunk i + 1 while the second stream (B) runs the back of chunk i: the hit stage's one-wave blocks move in beside
@@ -978,7 +1005,7 @@ int ppm_refine_batch(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const void *imag
     }
     if (int rc = os.drain()) return rc;
     refine_counts(r);
-    return 0;
+    return read_reuse(r);
 }
 
 
@@ -986,6 +1013,12 @@ const char *ppm_refine_note(ppm_ref_t *ref) { return ref ? ref->note.c_str() : "
 
 int ppm_refine_last_sections(ppm_ref_t *ref) { return ref ? ref->last_sections : 0; }
 int ppm_refine_last_overlap(ppm_ref_t *ref) { return ref ? ref->last_overlap : 0; }
+int ppm_refine_last_reuse(ppm_ref_t *ref, long *gathers, long *reused) {
+    if (!ref) return fail(-22, "null reference");
+    if (gathers) *gathers = ref->last_reuse[0];
+    if (reused) *reused = ref->last_reuse[1];
+    return 0;
+}
 
 int ppm_refine_last_counts(ppm_ref_t *ref, long *n_global, long *n_local, long *samples_global, long *samples_local) {
     if (!ref) return fail(-22, "null reference");

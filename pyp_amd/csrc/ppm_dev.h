@@ -275,9 +275,41 @@ struct CubeTaps { float4 a, b, c, d; float fx, fy, fz; bool cj; };
 
 typedef float cube_v4f __attribute__((ext_vector_type(4)));
 
+// Where the taps of one sample lie: the byte offsets of its four x-pairs and its 2 x 2 x 2 cell (x0, y0, z0 after the Friedel flip;
+// y0 and z0 as the fetch that filled it counts them).  Two samples with the same cell read the same 64 bytes.
+struct CubeAddr { unsigned oa, ob, oc, od; int x0, y0, z0; };
+
 // The four 16-byte x-pairs come through BUFFER loads: one 32-bit byte offset per load against a wave-uniform resource descriptor
 // (the cube's base and size in SGPRs) instead of a 64-bit address per lane and load - the address arithmetic of a gather drops from
 // ~20 vector instructions to ~8, and an offset beyond the cube reads zeros instead of faulting.
+__device__ __forceinline__ void cube_load(const CubeView &cv, const CubeAddr &o, CubeTaps &t) {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)cv.cube, 0, (int)(2u * cv.LB * 8u), 0x00020000);
+    const cube_v4f a = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)o.oa, 0, 0), b = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)o.ob, 0, 0);
+    const cube_v4f c = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)o.oc, 0, 0), d = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)o.od, 0, 0);
+    t.a = make_float4(a.x, a.y, a.z, a.w); t.b = make_float4(b.x, b.y, b.z, b.w);
+    t.c = make_float4(c.x, c.y, c.z, c.w); t.d = make_float4(d.x, d.y, d.z, d.w);
+}
+// cube_fetch in two halves (k_local's reusing loop compares cells between them): fractions and Friedel flag of the sample into `t`, its
+// addresses returned; then the loads.  cube_fetch itself stays one piece, so that the kernels that call it compile as they did.
+__device__ __forceinline__ CubeAddr cube_addr(const CubeView &cv, CubeTaps &t, float X, float Y, float Z) {
+    X *= cv.scale; Y *= cv.scale; Z *= cv.scale;
+    t.cj = X < 0.f;                                  // Friedel symmetry supplies x < 0
+    if (t.cj) { X = -X; Y = -Y; Z = -Z; }
+    const float xf = floorf(X), yf = floorf(Y), zf = floorf(Z);
+    t.fx = X - xf; t.fy = Y - yf; t.fz = Z - zf;
+    const int x0 = (int)xf, y0 = (int)yf + cv.off, z0 = (int)zf + cv.off;
+    const bool second = (x0 & 3) == 3;
+    const int xs = second ? x0 - 2 : x0;
+    // byte offsets; brick counts and offsets stay below 2^24 elements: 24-bit multiplies (full rate; v_mul_lo_u32 issues at a quarter of it)
+    const unsigned rowb = (unsigned)cv.NBX * 128u, planeb = __umul24(rowb, (unsigned)cv.NBY);
+    const unsigned xl = (unsigned)(xs >> 2) * 128u + (unsigned)(xs & 3) * 8u + (second ? cv.LB * 8u : 0u);
+    const unsigned yl0 = __umul24((unsigned)(y0 >> 1), rowb) + (unsigned)(y0 & 1) * 32u, dy = (y0 & 1) ? rowb - 32u : 32u;
+    const unsigned zl0 = __umul24((unsigned)(z0 >> 1), planeb) + (unsigned)(z0 & 1) * 64u, dz = (z0 & 1) ? planeb - 64u : 64u;
+    CubeAddr o;
+    o.oa = xl + yl0 + zl0; o.ob = o.oa + dy; o.oc = o.oa + dz; o.od = o.ob + dz;
+    o.x0 = x0; o.y0 = y0; o.z0 = z0;
+    return o;
+}
 __device__ __forceinline__ CubeTaps cube_fetch(const CubeView &cv, float X, float Y, float Z) {
     CubeTaps t;
     X *= cv.scale; Y *= cv.scale; Z *= cv.scale;
@@ -329,7 +361,18 @@ __device__ inline CubeTab cube_tab_fill(const CubeView &cv, void *mem, int R, in
 
 __device__ __forceinline__ int floor_to_int(float x) { int i; asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(i) : "v"(x)); return i; }
 
-// cube_fetch for coordinates that already carry the padding factor, through the address tables
+// cube_addr and cube_fetch for coordinates that already carry the padding factor, through the address tables
+__device__ __forceinline__ CubeAddr cube_addr_tab(const CubeTab &tb, CubeTaps &t, float X, float Y, float Z) {
+    t.cj = X < 0.f;
+    if (t.cj) { X = -X; Y = -Y; Z = -Z; }
+    t.fx = __builtin_amdgcn_fractf(X); t.fy = __builtin_amdgcn_fractf(Y); t.fz = __builtin_amdgcn_fractf(Z);
+    CubeAddr o;
+    o.x0 = floor_to_int(X); o.y0 = floor_to_int(Y); o.z0 = floor_to_int(Z);
+    const unsigned xl = tb.tx0[o.x0];
+    const uint2 ey = tb.ty0[o.y0], ez = tb.tz0[o.z0];
+    o.oa = xl + ey.x + ez.x; o.ob = o.oa + ey.y; o.oc = o.oa + ez.y; o.od = o.ob + ez.y;
+    return o;
+}
 __device__ __forceinline__ CubeTaps cube_fetch_tab(const CubeView &cv, const CubeTab &tb, float X, float Y, float Z) {
     CubeTaps t;
     t.cj = X < 0.f;
@@ -344,6 +387,25 @@ __device__ __forceinline__ CubeTaps cube_fetch_tab(const CubeView &cv, const Cub
     t.a = make_float4(a.x, a.y, a.z, a.w); t.b = make_float4(b.x, b.y, b.z, b.w);
     t.c = make_float4(c.x, c.y, c.z, c.w); t.d = make_float4(d.x, d.y, d.z, d.w);
     return t;
+}
+
+// ---- tap reuse (k_local's compass sweep): a neighbour pose h away turns the sample at k by h |k| voxels, and once that is well
+// below a voxel most of its samples fall into the cell the centre pose's sample fell into: the same four x-pairs.  Such a lane takes
+// the centre's taps (its own fractions and Friedel flag stay) and must not address the cube.  The test is on the cell itself: equal
+// first offsets do not prove equal cells, the table entries of coordinates outside the band wrap and could collide.
+__device__ __forceinline__ bool cube_same_cell(const CubeAddr &o, const CubeAddr &c) { return o.x0 == c.x0 && o.y0 == c.y0 && o.z0 == c.z0; }
+// The loads of a reusing lane stay in the instruction stream (every group keeps its own static vmcnt wait, sweep_plan) but carry an
+// offset past the end of any cube, for which the descriptor answers zeros without a look-up.
+__device__ __forceinline__ void cube_load_unless(const CubeView &cv, CubeAddr o, bool same, CubeTaps &t) {
+    constexpr unsigned kNoTap = 0xFFFFFFF0u;        // + 16 bytes > every num_records (a cube stays below 2^32 - 16 bytes)
+    if (same) { o.oa = kNoTap; o.ob = kNoTap; o.oc = kNoTap; o.od = kNoTap; }
+    cube_load(cv, o, t);
+}
+__device__ __forceinline__ float4 cube_pick(bool same, const float4 &c, const float4 &own) {
+    return make_float4(same ? c.x : own.x, same ? c.y : own.y, same ? c.z : own.z, same ? c.w : own.w);
+}
+__device__ __forceinline__ void cube_take(CubeTaps &t, bool same, const CubeTaps &c) {
+    t.a = cube_pick(same, c.a, t.a); t.b = cube_pick(same, c.b, t.b); t.c = cube_pick(same, c.c, t.c); t.d = cube_pick(same, c.d, t.d);
 }
 
 __device__ __forceinline__ float2 cube_interp(const CubeTaps &t) {

@@ -360,6 +360,15 @@ inline int compass_iterations(double ha, double hs, double steptol, int min_iter
     const int T = m > steptol ? (int)std::ceil(std::log(m / steptol) / std::log(2.0)) : min_iters;
     return std::min(12, std::max(min_iters, T));
 }
+// ---- tap reuse in the compass sweep of k_local's full-band launch (ppm_dev.h, "tap reuse"): the neighbour poses of an iteration lie
+// `ha` degrees from the centre pose, so their sample at |k| lies ha |k| pad voxels of the padded cube from the centre's, at the edge
+// of the iteration's band `rband` (Fourier pixels) near_move() voxels.  The reusing loop pays ~24 more vector instructions per
+// neighbour gather and saves the line look-ups of the lanes that stay in the centre's cell; it is taken while the move at the band's
+// edge is at most kNearMove voxels (CHANGELOG.md, "k_local: compass neighbours reuse the centre's taps", has the measurement).
+constexpr double kNearMove = 1.6;
+inline double near_move(double ha, double pad, double rband) { return ha * kPi / 180.0 * pad * rband; }
+inline bool near_reuse_pays(bool any_ang, double ha, double pad, double rband) { return any_ang && near_move(ha, pad, rband) <= kNearMove; }
+
 // ---- launch plan of the pre-processing kernel (k_prep, ppm_kernels.h): block shape, row pairs per row pass, column chunks and the
 // carve-up of the block's dynamic LDS.  launch_prep (host_refine.h) launches from it and the kernel takes its pointers from the same
 // prep_lds, so the two cannot disagree; tests/test_prep_plan_cpu.py pins the Python restatement of the box sweep to it.

@@ -22,6 +22,9 @@ struct LocalP {
     float rmax2_class; int S_class;     // answer 22: band of LOGP / SIGMA (S_class = 0: the full band, no extra sweep)
     // answer 7 "use priors" (include/ppm.h): Gaussian restraint on the refined parameters; w = 1 / (2 var n_s), shifts in pixels
     int use_priors; double pmean[5], pw[5];
+    // tap reuse (k_local<TAB, true>): bit t set = the compass sweep of iteration t takes the neighbours' taps from the centre pose where
+    // the cell is the same (with_schedule, near_reuse_pays); reuse = null, or two counters: neighbour lane-gathers, reused ones
+    unsigned near_it; unsigned long long *reuse;
 };
 
 // restraint of one pose (k_local's compass; same expression as the oracle's prior_pen)
@@ -88,8 +91,14 @@ struct SweepCtx {
 //  * slot numbers and the LDS cells of a group are wave-uniform and kept in scalar registers;
 //  * tap addresses come from the LDS tables of ppm_dev.h (TAB), coordinates are pre-multiplied by the padding factor;
 //  * the model power |c v|^2 goes to ONE LDS cell per group (bsl), not to one per slot.
-template <bool TAB>
-__device__ __forceinline__ void sweep_plan(SweepPlan &plan, const SweepCtx &C, const int tid, const int nthr) {
+//
+// NEAR (k_local's final / rows launch) with `near` set, wave-uniform: the LAST group is the centre pose of a compass sweep and is
+// fetched first; a lane of a neighbour group whose sample falls into the centre's cell takes the centre's taps instead of addressing
+// the cube (ppm_dev.h, "tap reuse").  Only the order of the groups within a sample changes, and every slot has LDS cells of its own:
+// the scores are bit for bit those of the plain loop.  cnt (NEAR): this wave's neighbour lane-gathers and the reused ones.
+struct ReuseCount { unsigned all, same; };
+template <bool TAB, bool NEAR = false>
+__device__ __forceinline__ void sweep_plan(SweepPlan &plan, const SweepCtx &C, const int tid, const int nthr, const bool near = false, ReuseCount *cnt = nullptr) {
     const int lane = tid & 63, wave = tid >> 6, nw = C.nw, nr = C.nr;
     float *const ringA = C.ringA, *const sumB = C.sumB, *const sumC = C.sumC; double *const score = C.score;
     const float2 *const Il = C.Il; const float *const cw = C.cw; const float invN = C.invN;
@@ -125,11 +134,21 @@ __device__ __forceinline__ void sweep_plan(SweepPlan &plan, const SweepCtx &C, c
         };
         float b0x, b0y;
         turned(0, b0x, b0y);           // the angular neighbours and the centre share one shift (slots 0 .. q_same)
+        // a slice coordinate m0 kx + m1 ky: the second product rounded, the first fused into the sum.  Written out, because left to the
+        // compiler's contraction the rounding changed from one fetch site to the next (the arithmetic instance mixed fused and unfused
+        // sums), and a group's coordinates must not depend on the site that fetches it: the reusing loop takes the groups in another order
+        auto coord = [&](float m0, float m1) { return __fmaf_rn(fkx, m0, __fmul_rn(fky, m1)); };
         auto fetch = [&](int g) {
             const float *m = plan.ms[g];
-            const float X = m[0] * fkx + m[1] * fky, Y = m[2] * fkx + m[3] * fky, Z = m[4] * fkx + m[5] * fky;
+            const float X = coord(m[0], m[1]), Y = coord(m[2], m[3]), Z = coord(m[4], m[5]);
             if constexpr (TAB) return cube_fetch_tab(C.cv, C.tab, X, Y, Z);
             else { CubeView one = C.cv; one.scale = 1.f; return cube_fetch(one, X, Y, Z); }
+        };
+        auto where = [&](int g, CubeTaps &t) {                       // fetch, the address half
+            const float *m = plan.ms[g];
+            const float X = coord(m[0], m[1]), Y = coord(m[2], m[3]), Z = coord(m[4], m[5]);
+            if constexpr (TAB) return cube_addr_tab(C.tab, t, X, Y, Z);
+            else { CubeView one = C.cv; one.scale = 1.f; return cube_addr(one, t, X, Y, Z); }
         };
         const bool mine = head && ring < nr;
         float *const cellA = myA + ring;
@@ -163,6 +182,38 @@ __device__ __forceinline__ void sweep_plan(SweepPlan &plan, const SweepCtx &C, c
         // the next group's gathers fly while this group is scored; A and B alternate.  Inside the loop both fetches are unconditional,
         // so the wait before a group's interpolation is for ITS four loads only (a fetch under a condition forces the wait for the
         // oldest loads of either path, i.e. for the prefetch as well)
+        if constexpr (NEAR) {
+            const unsigned long long act = __ballot(s < S_used);
+            cnt->all += (unsigned)__builtin_popcountll(act) * (unsigned)(ng - 1);
+            if (near && ng > 1) {
+                // the centre's taps and cell stay in registers for the sample; its group (the shift probes: the longest to score) is
+                // scored while the first neighbour's loads fly, then the neighbours ping-pong as the plain loop's groups do
+                struct Near { CubeTaps t; bool same; };
+                CubeTaps C0;
+                const CubeAddr c0 = where(ng - 1, C0);
+                cube_load(C.cv, c0, C0);
+                auto fetch_near = [&](int g) {
+                    Near n;
+                    const CubeAddr o = where(g, n.t);
+                    n.same = cube_same_cell(o, c0);
+                    cnt->same += (unsigned)__builtin_popcountll(__ballot(n.same) & act);
+                    cube_load_unless(C.cv, o, n.same, n.t);
+                    return n;
+                };
+                auto score_near = [&](int g, Near &n) { cube_take(n.t, n.same, C0); score_group(g, n.t); };
+                const int nn = ng - 1;
+                Near A = fetch_near(0), B;
+                __builtin_amdgcn_sched_barrier(0); score_group(nn, C0);
+                int g = 0;
+                for (; g + 2 < nn; g += 2) {
+                    B = fetch_near(g + 1); __builtin_amdgcn_sched_barrier(0); score_near(g, A);
+                    A = fetch_near(g + 2); __builtin_amdgcn_sched_barrier(0); score_near(g + 1, B);
+                }
+                if (g + 1 < nn) { B = fetch_near(g + 1); __builtin_amdgcn_sched_barrier(0); score_near(g, A); score_near(g + 1, B); }
+                else score_near(g, A);
+                continue;
+            }
+        }
         CubeTaps A = fetch(0), B;
         int g = 0;
         for (; g + 2 < ng; g += 2) {          // sched_barrier: the loads are issued BEFORE the scheduler may start on the other set's interpolation
@@ -211,7 +262,7 @@ __device__ __forceinline__ void sweep_plan(SweepPlan &plan, const SweepCtx &C, c
 #ifndef PPM_LOCAL_MINW
 #define PPM_LOCAL_MINW 4
 #endif
-template <bool TAB>
+template <bool TAB, bool NEAR>
 __global__ void __launch_bounds__(256, PPM_LOCAL_MINW) k_local(LocalP P) {
     __shared__ SweepPlan plan;
     extern __shared__ float lsm[];                    // ringA[slot][wave][nr], sumB[slot][wave], sumC[wave]; then the address tables (TAB)
@@ -219,6 +270,7 @@ __global__ void __launch_bounds__(256, PPM_LOCAL_MINW) k_local(LocalP P) {
     __shared__ LState st;
     __shared__ double sfp[5], sfm[5], sd[5], sMt[9], sshq[2], sf0;
     __shared__ double spen[kMaxCand];                 // restraint of every slot's pose (use_priors)
+    ReuseCount cnt = { 0u, 0u };                      // tap reuse of this wave's sweeps (NEAR)
     const int tid = threadIdx.x, nthr = blockDim.x;      // 128 or 256 threads (few samples per sweep: smaller blocks)
     const int nw = nthr >> 6, nr = P.nr;
     float *const ringA = lsm, *const sumB = lsm + kMaxCand * nw * nr, *const sumC = sumB + kMaxCand * nw;
@@ -298,7 +350,8 @@ __global__ void __launch_bounds__(256, PPM_LOCAL_MINW) k_local(LocalP P) {
             if (tid == 0) { plan.S_used = P.S_class; plan.rmax2 = P.rmax2_class; }
         }                                                // PH_TRIAL: the plan was written when the compass scores were read
         __syncthreads();
-        sweep_plan<TAB>(plan, SC, tid, nthr);
+        if constexpr (NEAR) sweep_plan<TAB, true>(plan, SC, tid, nthr, phase == PH_COMPASS && ((P.near_it >> it) & 1u), &cnt);
+        else sweep_plan<TAB>(plan, SC, tid, nthr);
         if (tid == 0) {
             if (phase == PH_COMPASS) {
                 int qc = 0;                              // slot of the centre: the angles' probes lie before it, the shifts' after it
@@ -336,6 +389,16 @@ __global__ void __launch_bounds__(256, PPM_LOCAL_MINW) k_local(LocalP P) {
         __syncthreads();
     }
     if (tid == 0) P.states[blockIdx.x] = st;
+    if constexpr (NEAR) {
+        if (P.reuse) {                                // per wave the counts are uniform: one LDS add per wave, one global add per block and counter
+            __shared__ unsigned sreuse[2];
+            if (tid == 0) sreuse[0] = sreuse[1] = 0u;
+            __syncthreads();
+            if ((tid & 63) == 0) { atomicAdd(&sreuse[0], cnt.all); atomicAdd(&sreuse[1], cnt.same); }
+            __syncthreads();
+            if (tid == 0) { atomicAdd(P.reuse, (unsigned long long)sreuse[0]); atomicAdd(P.reuse + 1, (unsigned long long)sreuse[1]); }
+        }
+    }
 }
 
 // states from global-search hits: one thread per (particle, hit)

@@ -159,6 +159,13 @@ class Reference:
         """Hit-stage blocks per compute unit beside the grid search in the last refine() (ppm_refine_last_overlap); 0: serial order."""
         return int(lib.load().ppm_refine_last_overlap(self.h))
 
+    def last_reuse(self):
+        """(neighbour lane-gathers, reused ones) of the full-band compass sweeps of the last refine() (ppm_refine_last_reuse);
+        counted only under PPM_LOCAL_REUSE_COUNT=1, (0, 0) otherwise."""
+        v = [C.c_long(), C.c_long()]
+        lib.check(lib.load().ppm_refine_last_reuse(self.h, C.byref(v[0]), C.byref(v[1])))
+        return v[0].value, v[1].value
+
     def close(self):
         if getattr(self, "h", None):
             lib.load().ppm_reference_destroy(self.h)
