@@ -555,6 +555,36 @@ typedef struct ppm_locres_info {
 int ppm_local_resolution(const ppm_locres_cfg *cfg, const void *half1, const void *half2, const void *mask, int on_device, int n,
                          void *out_res, void *level_maps, ppm_locres_info *info);
 
+/* Fourier resampling and real-space resizing of maps and image stacks: the work of cistem2's `resample` and `resize`, which PYP runs on the
+ * initial model (src/pyp/preprocess/core.py:762-793 through src/pyp/system/wrapper_functions.py:14-122), and of frealign_v9.11's
+ * resample_mp.exe, which Fourier-bins particle stacks (src/pyp/analysis/image.py:71-147, :209-248).  DESIGN.md section 2f defines both:
+ *   resample  per axis, with X the unnormalised DFT of a line of n_in samples, K = min(n_in, n_out), h = K / 2: Y[k mod n_out] = X[k mod n_in]
+ *             for |k| < h; the Nyquist term of the smaller grid Y[h] = X[h] + X[n_in - h] (n_out < n_in) or Y[h] = Y[n_out - h] = X[h] / 2
+ *             (n_out > n_in); all else 0; y = (1 / n_in) IDFT(Y).  Sample 0 stays sample 0, the mean is kept.  Both sizes must be ones the
+ *             transforms take (even, 32..512, prime factors 2, 3, 5, 7); the refusal names the nearest such sizes.
+ *   resize    out[i] = in[i - n_out / 2 + n_in / 2] per axis where that lies inside the input, elsewhere the pad value: the mean of the voxels
+ *             on the six faces of a volume (the four edges of an image, per image), every voxel once, summed in double in a fixed order
+ *             (no floating-point atomics: two calls agree bit for bit).  normalize != 0: the mean of the item is subtracted and the result
+ *             divided by its standard deviation first (both in double, over all voxels); a deviation of 0 is refused.  Sizes 8..512.
+ *             pad_values (host memory, may be NULL): the pad value of every item as written.
+ * dims: 2 = n_items square images, 3 = n_items cubic volumes, x fastest, items one after the other.  on_device != 0: src and dst are
+ * device pointers.  Host stacks of any length pass through the device in chunks sized from its total memory.  Refusals return -22 and
+ * write nothing to dst. */
+int ppm_resample(const void *src, int on_device, int dims, long n_items, int n_in, int n_out, void *dst);
+int ppm_resize(const void *src, int on_device, int dims, long n_items, int n_in, int n_out, int normalize, void *dst, float *pad_values);
+/* Fitting a reference of n_in voxels at pixel_in to a box of box_out voxels at pixel_out: s = pixel_in / pixel_out,
+ * n_c = min(n_in, 2 ceil(box_out / (2 s)) + 2) is what the output box can show; among the sizes P >= n_c and M the transforms take the
+ * pair with the smallest rel_error = |M / (P s) - 1| is chosen (ties: the smaller P M, then the smaller P); the map is resized n_in -> P,
+ * resampled P -> M and resized M -> box_out.  pixel_achieved = pixel_in P / M is what the output header should carry.  A rel_error above
+ * 0.01 (the caller's own tolerance, preprocess/core.py:810-812) is refused with the best pair in the message; `out` of the plan is filled
+ * in either case.  The plan needs no device and no initialised library; the volume call fills pad_value_1 / pad_value_2 (the pad values of the two resizes) too. */
+typedef struct ppm_fit_info {
+    int n_in, box_out, n_c, P, M;
+    double scale, pixel_achieved, rel_error, pad_value_1, pad_value_2;
+} ppm_fit_info;
+int ppm_fit_plan(int n_in, double pixel_in, double pixel_out, int box_out, ppm_fit_info *out);
+int ppm_fit_volume(const void *vol, int on_device, int n_in, double pixel_in, double pixel_out, int box_out, void *out, ppm_fit_info *info);
+
 /* Particle extraction straight into a (resident) stack — the step before the path:
  * crop `box` x `box` windows around the picked coordinates, fill what falls outside the micrograph with the mean
  * of the inside part, replace empty boxes by white noise, subtract the background mean and divide by the background

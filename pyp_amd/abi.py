@@ -193,6 +193,17 @@ class CreateMaskInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FitInfo(C.Structure):
+    """ppm_fit_info (include/ppm.h): the plan that fits a reference of n_in voxels to box_out - what the output box can show (n_c), the
+    padded / cropped input P, its resampled size M, scale = pixel_in / pixel_out, the pixel size the pair achieves and how far M / (P scale)
+    is from 1 - and the pad values of the two resizes (ppm_fit_volume only)."""
+    _fields_ = [("n_in", C.c_int), ("box_out", C.c_int), ("n_c", C.c_int), ("P", C.c_int), ("M", C.c_int), ("scale", C.c_double),
+                ("pixel_achieved", C.c_double), ("rel_error", C.c_double), ("pad_value_1", C.c_double), ("pad_value_2", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class PostCfg(C.Structure):
     """ppm_post_cfg (include/ppm.h)."""
     MASK = {"none": 0, "external": 1, "auto": 2}

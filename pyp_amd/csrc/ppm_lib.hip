@@ -35,6 +35,8 @@
 #include "ppm_label_kernels.h"
 #include "ppm_post_kernels.h"
 #include "ppm_locres_kernels.h"
+#include "ppm_resample_plan.h"
+#include "ppm_resample_kernels.h"
 
 using namespace ppm;
 
@@ -48,3 +50,4 @@ using namespace ppm;
 #include "host_label.h"
 #include "host_post.h"
 #include "host_locres.h"
+#include "host_resample.h"

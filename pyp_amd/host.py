@@ -489,6 +489,110 @@ def local_resolution(half1, half2, cfg, mask=None, device=0):
     return res
 
 
+def _items_in_out(x, n_out, volume, out, who):
+    """Shared front of resample() / resize(): x = one image [N, N], a stack [n, N, N] or, with volume=True, a volume [N, N, N]; numpy array
+    or CUDA torch tensor.  Returns (x, result, dims, n_items, n_in, pointer in, pointer out, on_device)."""
+    on_dev = bool(getattr(x, "is_cuda", False))
+    if out is not None and on_dev != bool(getattr(out, "is_cuda", False)):
+        raise ValueError(f"ERROR: {who}: input and out must both be on the host or both on the device")
+    if not on_dev:
+        x = np.ascontiguousarray(x.numpy() if hasattr(x, "numpy") else x, dtype=np.float32)
+    shape = tuple(int(s) for s in x.shape)
+    if len(shape) == 2 and not volume:
+        dims, n_items = 2, 1
+    elif len(shape) == 3:
+        dims, n_items = (3, 1) if volume else (2, shape[0])
+    else:
+        raise ValueError(f"ERROR: {who}: expected an image, a stack of images or (volume=True) a volume, got shape {shape}")
+    n_in, n_out = shape[-1], int(n_out)
+    if len(set(shape[-dims:])) != 1:
+        raise ValueError(f"ERROR: {who}: only square images and cubic volumes are supported, got shape {shape}")
+    if n_items < 1:
+        raise ValueError(f"ERROR: {who}: the stack is empty")
+    oshape = shape[:len(shape) - dims] + (n_out,) * dims
+    if on_dev:
+        import torch
+        if str(x.dtype) != "torch.float32" or not x.is_contiguous():
+            raise ValueError(f"ERROR: {who}: a device array must be contiguous float32")
+        res = torch.empty(oshape, dtype=torch.float32, device=x.device) if out is None else out
+        if tuple(res.shape) != oshape or str(res.dtype) != "torch.float32" or not res.is_contiguous():
+            raise ValueError(f"ERROR: {who}: out must be a contiguous float32 tensor of shape {oshape}")
+        for t in (x, res):
+            if not getattr(t, "ready", False):
+                _sync_producer(t)
+        pi, po = C.c_void_p(x.data_ptr()), C.c_void_p(res.data_ptr())
+    else:
+        res = np.empty(oshape, dtype=np.float32) if out is None else out
+        if not isinstance(res, np.ndarray) or res.dtype != np.float32 or res.shape != oshape or not res.flags.c_contiguous:
+            raise ValueError(f"ERROR: {who}: out must be a contiguous float32 array of shape {oshape}")
+        pi, po = lib.ptr(x), lib.ptr(res)
+    return x, res, dims, n_items, n_in, pi, po, on_dev
+
+
+def resample(x, n_out, volume=False, out=None, device=0):
+    """Fourier resampling (ppm_resample; what cistem2's resample and frealign_v9.11's resample_mp.exe do): every image of a
+    stack [n, N, N] (or one image [N, N]) to n_out x n_out, or with volume=True a volume [N, N, N] to n_out^3.  numpy array or CUDA torch
+    tensor in, the same kind out (`out`, same kind, receives it in place of a new array).  Both sizes must be ones the transforms take; a
+    refusal raises lib.PpmError and leaves `out` as it was."""
+    lib.init(device)
+    x, res, dims, n_items, n_in, pi, po, on_dev = _items_in_out(x, n_out, volume, out, "resample")
+    lib.check(lib.load().ppm_resample(pi, 1 if on_dev else 0, dims, n_items, n_in, int(n_out), po))
+    return res
+
+
+def resize(x, n_out, normalize=False, volume=False, out=None, device=0, pad_values=False):
+    """Crop or pad about the centre (ppm_resize; what cistem2's resize does): the pad value is the mean of the faces of a
+    volume / of the four edges of every image; normalize: mean 0, standard deviation 1 first.  Arguments as for resample(); sizes 8..512.
+    pad_values=True: returns (result, float32 array of the pad value of every item)."""
+    lib.init(device)
+    x, res, dims, n_items, n_in, pi, po, on_dev = _items_in_out(x, n_out, volume, out, "resize")
+    pads = np.zeros(n_items, dtype=np.float32)
+    lib.check(lib.load().ppm_resize(pi, 1 if on_dev else 0, dims, n_items, n_in, int(n_out), 1 if normalize else 0, po, lib.ptr(pads)))
+    return (res, pads) if pad_values else res
+
+
+def fit_plan(n_in, pixel_in, pixel_out, box):
+    """The plan of fit_reference (ppm_fit_plan; no device needed): abi.FitInfo.  A pair of sizes more than 1 % off raises lib.PpmError
+    whose text names the best achievable pixel size."""
+    from .abi import FitInfo
+    info = FitInfo()
+    lib.check(lib.load().ppm_fit_plan(int(n_in), float(pixel_in), float(pixel_out), int(box), C.byref(info)))
+    return info
+
+
+def fit_reference(vol, pixel_in, pixel_out, box, out=None, device=0):
+    """Bring a reference map to the data's box and pixel size (ppm_fit_volume): resize to P, resample P -> M, resize to
+    `box`.  vol: cubic float32, numpy array or CUDA torch tensor.  Returns (map of the kind given, abi.FitInfo); info.pixel_achieved is the
+    pixel size the map really has (within 1 % of pixel_out)."""
+    from .abi import FitInfo
+    lib.init(device)
+    on_dev = bool(getattr(vol, "is_cuda", False))
+    if out is not None and on_dev != bool(getattr(out, "is_cuda", False)):
+        raise ValueError("ERROR: fit_reference: map and out must both be on the host or both on the device")
+    if not on_dev:
+        vol = np.ascontiguousarray(vol.numpy() if hasattr(vol, "numpy") else vol, dtype=np.float32)
+    shape = tuple(int(s) for s in vol.shape)
+    if len(shape) != 3 or len(set(shape)) != 1:
+        raise ValueError("ERROR: fit_reference: the map must be a cubic volume")
+    box = int(box)
+    oshape = (box, box, box)
+    if on_dev:
+        import torch
+        res = torch.empty(oshape, dtype=torch.float32, device=vol.device) if out is None else out
+        if tuple(res.shape) != oshape:
+            raise ValueError("ERROR: fit_reference: out has the wrong shape")
+        pv, _, _ = _volumes_arg(vol, 1, shape[0])
+        po, _, _ = _volumes_arg(res, 1, box)
+    else:
+        res = np.empty(oshape, dtype=np.float32) if out is None else out
+        if not isinstance(res, np.ndarray) or res.dtype != np.float32 or res.shape != oshape or not res.flags.c_contiguous:
+            raise ValueError("ERROR: fit_reference: out must be a contiguous float32 array of the box's shape")
+        pv, po = lib.ptr(vol), lib.ptr(res)
+    info = FitInfo()
+    lib.check(lib.load().ppm_fit_volume(pv, 1 if on_dev else 0, shape[0], float(pixel_in), float(pixel_out), box, po, C.byref(info)))
+    return res, info
+
+
 class PinnedBuffer:
     """Page-locked host memory as a float32 numpy array (ppm_host_alloc): staging for uploads that overlap compute."""
 

@@ -17,7 +17,7 @@ EXPORTS = [
     "ppm_finalize", "ppm_profile_enable", "ppm_profile_reset", "ppm_profile_get", "ppm_device_alloc",
     "ppm_device_free", "ppm_device_upload", "ppm_device_sync", "ppm_extract_boxes", "ppm_host_alloc", "ppm_host_free", "ppm_host_read",
     "ppm_comm_unique_id", "ppm_comm_create", "ppm_comm_count", "ppm_comm_destroy", "ppm_accum_reduce", "ppm_sva_insert", "ppm_sva_align_average", "ppm_mask_volume",
-    "ppm_create_mask", "ppm_postprocess", "ppm_local_resolution",
+    "ppm_create_mask", "ppm_postprocess", "ppm_local_resolution", "ppm_resample", "ppm_resize", "ppm_fit_plan", "ppm_fit_volume",
 ]
 
 
@@ -92,6 +92,10 @@ def load():
     L.ppm_create_mask.argtypes = [vp, ci, ci, vp, vp, vp]; L.ppm_create_mask.restype = ci
     L.ppm_postprocess.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]; L.ppm_postprocess.restype = ci
     L.ppm_local_resolution.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp]; L.ppm_local_resolution.restype = ci
+    L.ppm_resample.argtypes = [vp, ci, ci, cl, ci, ci, vp]; L.ppm_resample.restype = ci
+    L.ppm_resize.argtypes = [vp, ci, ci, cl, ci, ci, ci, vp, vp]; L.ppm_resize.restype = ci
+    L.ppm_fit_plan.argtypes = [ci, C.c_double, C.c_double, ci, vp]; L.ppm_fit_plan.restype = ci
+    L.ppm_fit_volume.argtypes = [vp, ci, ci, C.c_double, C.c_double, ci, vp, vp]; L.ppm_fit_volume.restype = ci
     _lib = L
     return L
 

@@ -11,7 +11,7 @@ from .formats.cistem import COL
 
 def iteration(vol, stack, rows, refine_cfg, *, pixel_size, molecular_mass_kda, symmetry="C1", keep_fraction=1.0,
               score_weight_bfactor=0.0, outer_radius=None, split_by_pind=False, mask=None, mask_cfg=None, auto_mask=None, postprocess=None,
-              local_resolution=None):
+              local_resolution=None, reference_pixel=None):
     """vol: current reference (N^3 float32); stack: [M, N, N] float32 (numpy or a CUDA torch tensor); rows: [M, 32].
     mask (N^3 float32, of the same kind as vol) with mask_cfg (abi.MaskCfg; default: PYP's edge of 3 voxels, weight 0): the
     reference is shape-masked on the device first, as `shape_mask_reference` (align/core.py:783-856) does with apply_mask.exe.
@@ -22,11 +22,19 @@ def iteration(vol, stack, rows, refine_cfg, *, pixel_size, molecular_mass_kda, s
     local_resolution (abi.LocresCfg): the half maps go through host.local_resolution (the work of ResMap in the same block,
     pyp_main.py:6815-6844) and its result is added as "local_resolution"; `mask` (or the one auto_mask made), where there is one, says
     which voxels are inside.
+    reference_pixel (A): vol may have any box and this pixel size; it is fitted to the stack's box and refine_cfg.pixel_size first
+    (host.fit_reference, the work of `resize_initial_model`, preprocess/core.py:796-832); the plan is added as "fit".  A mask refers to
+    the fitted map.
     Returns dict(rows=refined table incl. OCC after selection, half1, half2, filtered, stats=[N/2-1, 7] statistics table).
     """
     n = int(refine_cfg.box)
     if postprocess is not None and postprocess.mask_mode == 1 and mask is None and auto_mask is None:
         raise ValueError("ERROR: iteration: postprocess asks for an external mask, but neither mask nor auto_mask was given")
+    fit_info = None
+    if reference_pixel is not None:
+        vol, fit_info = host.fit_reference(vol, reference_pixel, refine_cfg.pixel_size, n)
+        if getattr(vol, "is_cuda", False) and mask is None and auto_mask is None:      # Reference takes a host array
+            vol = vol.cpu().numpy()
     if auto_mask is not None:
         if mask is not None:
             raise ValueError("ERROR: iteration: auto_mask and mask exclude each other")
@@ -58,6 +66,8 @@ def iteration(vol, stack, rows, refine_cfg, *, pixel_size, molecular_mass_kda, s
     finally:
         acc.close()
     result = dict(rows=used, half1=h1, half2=h2, filtered=filt, stats=np.asarray(stats))
+    if fit_info is not None:
+        result["fit"] = fit_info
     if postprocess is not None:
         if getattr(post_mask, "is_cuda", False):      # the half maps are host arrays
             post_mask = post_mask.cpu().numpy()

@@ -1122,3 +1122,192 @@ def resmap_main(argv=None, backend=None):
     _release_warm()
     print("\nResMap: Normal termination\n", flush=True)
     return 0
+
+
+# ------------------------------------------------------------------------------------------ resample / resize / resample_mp.exe / fit_reference
+RESAMPLE_CHUNK_BYTES = 256 << 20         # of input images held at a time: a stack need not fit in host memory
+
+
+def _resample_device_backend(kind):
+    """What the three programs compute with by default: host.resample / host.resize on the GPU, under the per-GPU lock (taken once, on
+    the first chunk, and kept until the program ends)."""
+    state = {}
+
+    def run(x, n_out, volume, normalize):
+        from .. import host, lib
+        dev = int(os.environ.get("PPM_DEVICE", "0"))
+        if "lock" not in state:
+            state["lock"] = gpu_lock(dev)
+            state["lock"].__enter__()
+        try:
+            if kind == "resize":
+                return host.resize(x, n_out, normalize=normalize, volume=volume, device=dev)
+            return host.resample(x, n_out, volume=volume, device=dev)
+        except lib.PpmError as e:
+            raise ValueError(str(e))
+
+    def close():
+        if "lock" in state:
+            state.pop("lock").__exit__(None, None, None)
+
+    run.close = close
+    return run
+
+
+def _resample_like_main(kind, prog, title, parse, stdin, backend):
+    """cistem2's resample / resize and frealign_v9.11's resample_mp.exe as PYP runs them (src/pyp/system/wrapper_functions.py:14-122,
+    src/pyp/analysis/image.py:71-147, :209-248): a volume is read in full, a stack streams through in chunks; the output appears under its
+    name only when complete.  backend: what computes (array, new size, volume, normalize) -> array."""
+    t0 = time.time()
+    try:
+        d = parse(prompts.read_answers(stdin or sys.stdin))
+    except prompts.PromptError as e:
+        _die(str(e))
+    print(f"\n        **   Welcome to {title} (MI355X / libpypmatch)   **\n")
+    for k, v in d.items():
+        if k != "notes":
+            print(f"{k:28s}: {v}")
+    for note in d["notes"]:
+        print(f"Note: {note}")
+    if not os.path.exists(d["input"]):
+        _die(f"ERROR: {prog}: input file {d['input']} does not exist")
+    try:
+        head = mrc.read_header(d["input"])
+        mm = mrc.mmap(d["input"])
+    except (IOError, ValueError) as e:
+        _die(str(e))
+    nz, ny, nx = (int(v) for v in mm.shape)
+    m, volume, fourier = d["size"], d["volume"], kind != "resize"
+    if nx != ny or (volume and nz != nx):
+        what = "cubic volumes" if volume else "square images"
+        extra = " (whole micrographs and tilt series are not: only particle stacks and maps)" if not volume else ""
+        _die(f"ERROR: {prog}: the input is {nx} x {ny}" + (f" x {nz}" if volume else f", {nz} images") + f"; only {what} are supported by this build{extra}")
+    if fourier:
+        for what, n in (("input", nx), ("new", m)):
+            if not prompts.resample_len_ok(n):
+                near = " and ".join(str(k) for k in prompts.resample_nearest_ok(n))
+                big = " (whole micrographs and tilt series are not supported: only particle stacks and maps)" if n > 512 else ""
+                _die(f"ERROR: {prog}: the {what} size {n} is not supported by this build{big}: the transforms take even sizes 32..512 with prime "
+                     f"factors 2, 3, 5 and 7 only; nearest: {near}")
+    elif not (8 <= nx <= 512 and 8 <= m <= 512):
+        _die(f"ERROR: {prog}: sizes must be 8..512, got {nx} -> {m}")
+    px_in = float(head["pixel_size"])
+    px_out = px_in * nx / m if fourier else px_in
+    normalize = bool(d.get("normalize", False))
+    run = backend if backend is not None else _resample_device_backend(kind)
+    tmp = d["output"] + ".tmp%d" % os.getpid()
+    t1 = time.time()
+    try:
+        try:
+            if volume:
+                out = np.asarray(run(np.asarray(mm, dtype=np.float32), m, True, normalize), dtype=np.float32)
+                mrc.write(out, tmp, pixel_size=px_out)
+            else:
+                per = max(1, RESAMPLE_CHUNK_BYTES // (4 * nx * nx))
+                omm = mrc.create(tmp, (nz, m, m), pixel_size=px_out)
+                lo, hi, s1, s2 = np.inf, -np.inf, 0.0, 0.0
+                for i0 in range(0, nz, per):
+                    o = np.asarray(run(np.asarray(mm[i0:i0 + per], dtype=np.float32), m, False, normalize), dtype=np.float32)
+                    omm[i0:i0 + len(o)] = o
+                    lo, hi = min(lo, float(o.min())), max(hi, float(o.max()))
+                    s1 += float(o.sum(dtype=np.float64)); s2 += float(np.square(o, dtype=np.float64).sum())
+                omm.flush()
+                del omm
+                cnt = float(nz) * m * m
+                mean = s1 / cnt
+                mrc.set_statistics(tmp, lo, hi, mean, max(s2 / cnt - mean * mean, 0.0) ** 0.5)
+            os.replace(tmp, d["output"])
+        finally:
+            if hasattr(run, "close"):
+                run.close()
+    except (ValueError, OSError) as e:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        _die(str(e) if "ERROR" in str(e) else f"ERROR: {prog}: could not write {d['output']}: {e}")
+    what = f"a {nx}^3 volume" if volume else f"{nz} images of {nx} x {nx}"
+    if fourier:
+        print(f"\nResampled {what} to {m}: pixel size {px_in:g} -> {px_out:g} A")
+    else:
+        print(f"\nResized {what} to {m}" + (", normalised and zero-floated" if normalize else "") + f": pixel size {px_in:g} A")
+        print("Build-defined (the program itself is not available): the pad value is the mean of the faces of a volume / of the four edges of "
+              "every image; normalisation comes before the padding")
+    print(f"Timing: input {t1 - t0:.2f} s, device and output {time.time() - t1:.2f} s")
+    _release_warm()
+    print(f"\n{title}: Normal termination\n", flush=True)
+    return 0
+
+
+def resample_main(argv=None, stdin=None, backend=None):
+    return _resample_like_main("resample", "resample", "Resample", prompts.parse_resample, stdin, backend)
+
+
+def resize_main(argv=None, stdin=None, backend=None):
+    return _resample_like_main("resize", "resize", "Resize", prompts.parse_resize, stdin, backend)
+
+
+def resample_mp_main(argv=None, stdin=None, backend=None):
+    return _resample_like_main("resample_mp", "resample_mp", "Resample_mp", prompts.parse_resample_mp, stdin, backend)
+
+
+def fit_reference_main(argv=None, backend=None):
+    """fit_reference IN.mrc OUT.mrc --pixel A --box B [--pixel-in A0]: bring a reference to the data's box and pixel size (what
+    resize_initial_model, src/pyp/preprocess/core.py:796-832, does with mtffilter and matchvol; INTEGRATION.md shows the edit).  The input's
+    pixel size comes from its header unless --pixel-in gives it; the output header carries the pixel size actually achieved.
+    backend: what computes (vol, pixel_in, pixel_out, box) -> (map, info with the fields of abi.FitInfo)."""
+    import argparse
+    t0 = time.time()
+    ap = argparse.ArgumentParser(prog="fit_reference", add_help=True)
+    ap.add_argument("input"); ap.add_argument("output")
+    ap.add_argument("--pixel", type=float, required=True); ap.add_argument("--box", type=int, required=True)
+    ap.add_argument("--pixel-in", type=float, default=None)
+    try:
+        a = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    except SystemExit as e:
+        if e.code in (0, None):
+            raise
+        _die("ERROR: fit_reference: usage: fit_reference IN.mrc OUT.mrc --pixel A --box B [--pixel-in A0]")
+    print("\n        **   Welcome to FitReference (MI355X / libpypmatch)   **\n")
+    if not os.path.exists(a.input):
+        _die(f"ERROR: fit_reference: input file {a.input} does not exist")
+    try:
+        head = mrc.read_header(a.input)
+        vol = mrc.read(a.input).astype(np.float32)
+    except (IOError, ValueError) as e:
+        _die(str(e))
+    if vol.ndim != 3 or len(set(vol.shape)) != 1:
+        _die(f"ERROR: fit_reference: the input map is {vol.shape}, only cubic maps are supported")
+    px_in = a.pixel_in if a.pixel_in is not None else float(head["pixel_size"])
+    if not (px_in > 0 and a.pixel > 0):
+        _die(f"ERROR: fit_reference: pixel sizes must be positive, got {px_in:g} and {a.pixel:g}")
+    if not 8 <= a.box <= 512 or not 8 <= vol.shape[0] <= 512:
+        _die(f"ERROR: fit_reference: boxes must be 8..512, got {vol.shape[0]} -> {a.box}")
+    t1 = time.time()
+    try:
+        if backend is not None:
+            out, info = backend(vol, px_in, a.pixel, a.box)
+        else:
+            from .. import host, lib
+            dev = int(os.environ.get("PPM_DEVICE", "0"))
+            try:
+                with gpu_lock(dev):
+                    out, info = host.fit_reference(vol, px_in, a.pixel, a.box, device=dev)
+            except lib.PpmError as e:
+                _die(str(e))
+    except ValueError as e:
+        _die(str(e))
+    tmp = a.output + ".tmp%d" % os.getpid()
+    try:
+        mrc.write(np.asarray(out, dtype=np.float32), tmp, pixel_size=info.pixel_achieved)
+        os.replace(tmp, a.output)
+    except OSError as e:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        _die(f"ERROR: fit_reference: could not write {a.output}: {e}")
+    print(f"Reference of {vol.shape[0]}^3 at {px_in:g} A -> box {a.box} at {a.pixel:g} A: shows {info.n_c} voxels of the input, resized to {info.P}, "
+          f"resampled to {info.M}")
+    print(f"Pixel size achieved            : {info.pixel_achieved:.6g} A ({100.0 * info.rel_error:.3f} % from the request)")
+    print(f"Pad values                     : {info.pad_value_1:g}, {info.pad_value_2:g}")
+    print(f"Timing: input {t1 - t0:.2f} s, device and output {time.time() - t1:.2f} s")
+    _release_warm()
+    print("\nFitReference: Normal termination\n", flush=True)
+    return 0

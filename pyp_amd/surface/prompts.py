@@ -5,6 +5,8 @@ booleans (src/pyp/refine/frealign/frealign.py:3918-3994 refine3d, :1780-1824 rec
 :1878-1888 local_merge3d, :2075-2093 merge3d; src/pyp/align/core.py:811-850 apply_mask.exe; src/pyp/inout/image/core.py:1583-1596
 create_mask; the `.par`-surface refine3d script
 is preserved at src/pyp/system/wrapper_functions.py:512-561).  Answer order: SURVEY.md §9.1-§9.3.
+cistem2's resample / resize and frealign_v9.11's resample_mp.exe: src/pyp/system/wrapper_functions.py:57-67, :109-118 and
+src/pyp/analysis/image.py:97-118, :226-241 (parse_resample, parse_resize, parse_resample_mp).
 postprocessing.py and ResMap take command lines (src/pyp_main.py:6638-6737, :6826): parse_postprocessing, parse_resmap.
 """
 
@@ -222,6 +224,81 @@ def parse_create_mask(answers):
     if d["lowpass"] != 0 and not 0 < d["rebin"] < 1:
         raise PromptError(f"ERROR: {prog}: re-bin value must lie strictly between 0 and 1, got '{a[7]}'")
     return d
+
+
+# ------------------------------------------------------------------------------------------ resample / resize / resample_mp.exe
+def resample_len_ok(n):
+    """Lengths the transforms take (box_ok of ppm_geom.h): even, 32..512, prime factors 2, 3, 5, 7 only."""
+    if n < 32 or n > 512 or n % 2:
+        return False
+    for p in (2, 3, 5, 7):
+        while n % p == 0:
+            n //= p
+    return n == 1
+
+
+def resample_nearest_ok(n):
+    """The supported lengths next to n, below and above (either may be missing)."""
+    lo = next((k for k in range(min(n, 512), 31, -1) if resample_len_ok(k)), None)
+    hi = next((k for k in range(max(n, 32), 513) if resample_len_ok(k)), None)
+    return [k for k in dict.fromkeys((lo, hi)) if k is not None]
+
+
+def _size_answers(prog, names, answers):
+    """Size answers are numbers (resample_and_resize sends a float, preprocess/core.py:776-782); a fractional part is rounded to the nearest
+    integer and the rounding is reported.  Returns (the one size all of them name, notes for the log)."""
+    sizes, notes = [], []
+    for name, s in zip(names, answers):
+        v = _num(s, name)
+        if not v == v or v in (float("inf"), float("-inf")):
+            raise PromptError(f"ERROR: {prog}: answer for '{name}' must be a finite number, got '{s}'")
+        r = int(round(v))
+        if r != v:
+            notes.append(f"{name}: {s} is not a whole number of pixels, rounded to {r}")
+        sizes.append(r)
+    if len(set(sizes)) != 1:
+        raise PromptError(f"ERROR: {prog}: only equal sizes along every axis are supported by this build (square images, cubic volumes), got "
+                          + " x ".join(str(v) for v in sizes))
+    if sizes[0] < 1:
+        raise PromptError(f"ERROR: {prog}: the new size must be positive, got {sizes[0]}")
+    return sizes[0], notes
+
+
+def _resample_like(prog, answers, real_space=False, normalize=False):
+    a = list(answers)
+    if a and a[-1].strip().upper() == "EOF":              # a here-doc closed by EOF, taken apart by split_heredoc (which knows `eot`)
+        a.pop()
+    head = [("input", str), ("output", str), ("volume", bool)] + ([("real_space_binning", bool)] if real_space else [])
+    d = _take(a, head, prog)
+    names = ["new_x", "new_y"] + (["new_z"] if d["volume"] else [])
+    want = len(head) + len(names) + (1 if normalize else 0)
+    if len(a) < want:
+        raise PromptError(f"ERROR: {prog}: expected {want} answers ({'a volume' if d['volume'] else 'a stack of images'}), got {len(a)}")
+    if len(a) > want and any(s != "" for s in a[want:]):
+        raise PromptError(f"ERROR: {prog}: expected {want} answers ({'a volume' if d['volume'] else 'a stack of images'}), got {len(a)}")
+    d["size"], d["notes"] = _size_answers(prog, names, a[len(head):len(head) + len(names)])
+    if normalize:
+        d["normalize"] = _bool(a[want - 1], "normalize")
+    if real_space and d["real_space_binning"]:
+        raise PromptError(f"ERROR: {prog}: real-space binning is not supported by this build (answer no: Fourier resampling)")
+    return d
+
+
+def parse_resample(answers):
+    """cistem2's resample, the answers of src/pyp/system/wrapper_functions.py:109-118: input, output, is the input a volume, new X, new Y,
+    and new Z only for a volume."""
+    return _resample_like("resample", answers)
+
+
+def parse_resize(answers):
+    """cistem2's resize (wrapper_functions.py:57-67): the answers of resample plus 'normalize and zero-float the input'."""
+    return _resample_like("resize", answers, normalize=True)
+
+
+def parse_resample_mp(answers):
+    """frealign_v9.11's resample_mp.exe (src/pyp/analysis/image.py:97-118, :226-241): input, output, volume, real-space binning (refused;
+    PYP sends no), new X, new Y, and new Z only for a volume."""
+    return _resample_like("resample_mp", answers, real_space=True)
 
 
 POSTPROCESSING_FLAGS = ("flip_x", "flip_y", "flip_z", "gaussian", "skip_fsc_weighting", "apply_fsc2", "automask", "xml")
