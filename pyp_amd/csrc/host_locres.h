@@ -60,11 +60,6 @@ void locres_tables(int n, double a, double lambda, float *band, float *window) {
     band[0] = 0.f;
 }
 
-long locres_rank(double p, long n) {
-    const double r = std::ceil((1.0 - p) * (double)n);
-    return r < 1.0 ? 1 : r > (double)n ? n : (long)r;
-}
-
 }  // namespace
 
 extern "C" int ppm_local_resolution(const ppm_locres_cfg *cfg, const void *half1, const void *half2, const void *mask, int on_device, int n,
@@ -84,37 +79,24 @@ extern "C" int ppm_local_resolution(const ppm_locres_cfg *cfg, const void *half1
     const size_t tab = (size_t)3 * (n / 2) * (n / 2) + 1;
 
     // working memory, owned by the call: two complex arrays, the map, the byte map, the tables, the histogram and the counters
-    DevTmp<float> t_h1, t_h2, t_mask, t_res, t_tab;
+    StagedMap s_h1, s_h2, s_mask;
+    DevTmp<float> t_res, t_tab;
     DevTmp<float2> t_z, t_w;
     DevTmp<unsigned char> t_state;
-    DevTmp<unsigned> t_hist;
     DevTmp<unsigned long long> t_count;
-    const float *d_h1 = (const float *)half1, *d_h2 = (const float *)half2, *d_mask = (const float *)mask;
+    RankPasses rank_passes;
     // the kernels read 16 bytes at a time: host arrays, and device arrays that do not start on such a boundary, go through a copy
-    auto stage_in = [&](DevTmp<float> &t, const float *&d) -> int {
-        if (!d || (on_device && ((uintptr_t)d & 15) == 0)) return 0;
-        HIPCHK(t.alloc(n3));
-        HIPCHK(hipMemcpyAsync(t.p, d, n3 * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-        d = t.p;
-        return 0;
-    };
-    if (int rc = stage_in(t_h1, d_h1)) return rc;
-    if (int rc = stage_in(t_h2, d_h2)) return rc;
-    if (int rc = stage_in(t_mask, d_mask)) return rc;
+    if (int rc = s_h1.in(half1, n3, on_device, true)) return rc;
+    if (int rc = s_h2.in(half2, n3, on_device, true)) return rc;
+    if (int rc = s_mask.in(mask, n3, on_device, true)) return rc;
+    const float *d_h1 = s_h1.p, *d_h2 = s_h2.p, *d_mask = s_mask.p;
     HIPCHK(t_z.alloc(n3)); HIPCHK(t_w.alloc(n3)); HIPCHK(t_res.alloc(n3)); HIPCHK(t_state.alloc(n3));
-    HIPCHK(t_tab.alloc((size_t)2 * L * tab)); HIPCHK(t_hist.alloc(65536)); HIPCHK(t_count.alloc((size_t)L + 1));
+    HIPCHK(t_tab.alloc((size_t)2 * L * tab));
+    if (int rc = rank_passes.alloc()) return rc;
+    HIPCHK(t_count.alloc((size_t)L + 1));
     if (int rc = raise_lds_limit((const void *)k_lr_key_hist0, kLrHist0Bins * (int)sizeof(unsigned))) return rc;
 
-    // PPM_TRACE: device time per stage, by pairs of events on the call's stream
-    enum { S_SETUP, S_FORWARD, S_BAND, S_BAND_BACK, S_SQUARE, S_SQUARE_FWD, S_WINDOW, S_WINDOW_BACK, S_THRESHOLD, S_ASSIGN, S_COUNT };
-    static const char *const stage_name[S_COUNT] = {"init + pack", "forward transform", "band", "band back", "square", "squares forward", "window", "window back",
-                                                    "threshold (2 histogram passes)", "assign"};
-    const bool trace = getenv("PPM_TRACE") != nullptr;
-    struct Span { int stage; hipEvent_t a, b; };
-    std::vector<Span> spans;
-    struct Releaser { std::vector<Span> &s; ~Releaser() { std::lock_guard<std::mutex> lk(g_mu); for (auto &x : s) { g.pool.push_back(x.a); g.pool.push_back(x.b); } } } releaser{spans};
-    auto begin = [&](int stage) { if (trace) { spans.push_back({stage, ev_get(), ev_get()}); (void)hipEventRecord(spans.back().a, st); } };
-    auto end = [&]() { if (trace) (void)hipEventRecord(spans.back().b, st); };
+    StageTimer timer;
     const auto wall0 = std::chrono::steady_clock::now();
 
     const dim3 b256(256), g_quads((unsigned)((quads + 255) / 256)), g_pairs((unsigned)((pairs + 255) / 256));
@@ -125,15 +107,15 @@ extern "C" int ppm_local_resolution(const ppm_locres_cfg *cfg, const void *half1
     int transforms = 0;
     auto transform = [&](float2 *zb, bool inverse) -> int { transforms++; return fft3d(zb, n, inverse); };
 
-    begin(S_SETUP);
+    timer.begin("init + pack");
     HIPCHK(hipMemsetAsync(t_count.p, 0, ((size_t)L + 1) * sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_lr_init, g_loop, b256, 0, st, d_mask, t_state.p, t_res.p, n, PPM_LOCRES_UNASSIGNED, t_count.p);
     hipLaunchKernelGGL(k_lr_pack, g_quads, b256, 0, st, d_h1, d_h2, t_z.p, quads);
     HIPCHK(hipGetLastError());
-    end();
-    begin(S_FORWARD);
+    timer.end();
+    timer.begin("forward transform");
     if (int rc = transform(t_z.p, false)) return rc;
-    end();
+    timer.end();
     // the tables of every level, made while the device transforms
     std::vector<float> tables((size_t)2 * L * tab);
     for (int i = 0; i < L; i++) locres_tables(n, cfg->pixel_size, lv[i], &tables[(size_t)2 * i * tab], &tables[(size_t)(2 * i + 1) * tab]);
@@ -145,61 +127,51 @@ extern "C" int ppm_local_resolution(const ppm_locres_cfg *cfg, const void *half1
     const long rank = locres_rank(cfg->p_value, (long)n_inside);
 
     std::vector<float> tau(L);
-    std::vector<unsigned> hist(65536);
     for (int i = L - 1; i >= 0; i--) {                      // from the coarsest level to the finest
         const float *d_band = t_tab.p + (size_t)2 * i * tab, *d_win = d_band + tab;
-        begin(S_BAND);
+        timer.begin("band");
         hipLaunchKernelGGL(k_lr_band, g_rows, b_rows, 0, st, t_z.p, t_w.p, d_band, n);
         HIPCHK(hipGetLastError());
-        end();
-        begin(S_BAND_BACK);
+        timer.end();
+        timer.begin("band back");
         if (int rc = transform(t_w.p, true)) return rc;
-        end();
-        begin(S_SQUARE);
+        timer.end();
+        timer.begin("square");
         hipLaunchKernelGGL(k_lr_square, g_pairs, b256, 0, st, t_w.p, pairs);
         HIPCHK(hipGetLastError());
-        end();
-        begin(S_SQUARE_FWD);
+        timer.end();
+        timer.begin("squares forward");
         if (int rc = transform(t_w.p, false)) return rc;
-        end();
-        begin(S_WINDOW);
+        timer.end();
+        timer.begin("window");
         hipLaunchKernelGGL(k_lr_window, g_rows, b_rows, 0, st, t_w.p, d_win, n);
         HIPCHK(hipGetLastError());
-        end();
-        begin(S_WINDOW_BACK);
+        timer.end();
+        timer.begin("window back");
         if (int rc = transform(t_w.p, true)) return rc;
-        end();
+        timer.end();
         if (cfg->keep_levels)
-            HIPCHK(hipMemcpyAsync((float2 *)level_maps + (size_t)i * n3, t_w.p, n3 * sizeof(float2), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+            if (int rc = copy_out((float2 *)level_maps + (size_t)i * n3, t_w.p, 2 * n3, on_device)) return rc;
         // tau: the rank-th smallest E_D over the inside voxels, 16 bits of its integer image at a time
-        begin(S_THRESHOLD);
-        long long want = rank;
-        unsigned prefix = 0, key = 0;
-        for (int pass = 0; pass < 2; pass++) {
-            const int bins = pass == 0 ? kLrHist0Bins : 65536;
-            HIPCHK(hipMemsetAsync(t_hist.p, 0, bins * sizeof(unsigned), st));
-            if (pass == 0) hipLaunchKernelGGL(k_lr_key_hist0, g_hist0, dim3(1024), kLrHist0Bins * sizeof(unsigned), st, t_w.p, t_state.p, quads, t_hist.p);
-            else hipLaunchKernelGGL(k_lr_key_hist1, g_loop, b256, 0, st, t_w.p, t_state.p, quads, prefix, t_hist.p);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(hist.data(), t_hist.p, bins * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            long long below = 0;
-            int b = 0;
-            for (; b < bins; b++) { if (below + hist[b] >= want) break; below += hist[b]; }
-            if (b == bins) return fail(-5, "local_resolution: the histogram holds fewer voxels than the mask (a value that is not a number?)");
-            want -= below;
-            if (pass == 0) prefix = (unsigned)b; else key = (prefix << 16) | (unsigned)b;
-        }
-        end();
+        timer.begin("threshold (2 histogram passes)");
+        unsigned key = 0;
+        const int found = rank_passes.run(kLrHist0Bins, false, [&](const unsigned *, int) { return (long long)rank; },
+                                          [&](int pass, unsigned prefix, unsigned *d_hist) {
+                                              if (pass == 0) hipLaunchKernelGGL(k_lr_key_hist0, g_hist0, dim3(1024), kLrHist0Bins * sizeof(unsigned), st, t_w.p, t_state.p, quads, d_hist);
+                                              else hipLaunchKernelGGL(k_lr_key_hist1, g_loop, b256, 0, st, t_w.p, t_state.p, quads, prefix, d_hist);
+                                          }, &key);
+        if (found < 0) return found;
+        if (found != 0) return fail(-5, "local_resolution: the histogram holds fewer voxels than the mask (a value that is not a number?)");
+        timer.end();
         memcpy(&tau[i], &key, sizeof(float));
-        begin(S_ASSIGN);
+        timer.begin("assign");
         hipLaunchKernelGGL(k_lr_assign, g_loop, b256, 0, st, t_w.p, t_state.p, t_res.p, quads, tau[i], (float)lv[i], t_count.p + 1 + i);
         HIPCHK(hipGetLastError());
-        end();
+        timer.end();
     }
     std::vector<unsigned long long> alive((size_t)L + 1);
     HIPCHK(hipMemcpyAsync(alive.data(), t_count.p, alive.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out_res, t_res.p, n3 * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    if (int rc = copy_out(out_res, t_res.p, n3, on_device)) return rc;
     HIPCHK(hipStreamSynchronize(st));
     if (info) {
         memset(info, 0, sizeof(*info));
@@ -216,13 +188,11 @@ extern "C" int ppm_local_resolution(const ppm_locres_cfg *cfg, const void *half1
         }
         snprintf(info->notes, sizeof(info->notes), "%s", notes.c_str());
     }
-    if (trace) {
-        double ms[S_COUNT] = {};
-        for (auto &x : spans) { float t = 0; (void)hipEventElapsedTime(&t, x.a, x.b); ms[x.stage] += t; }
-        const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-        fprintf(stderr, "ppm_local_resolution: box %d, %d levels, %d transforms, %.3f ms wall; on the device, summed over the levels:", n, L, transforms, wall);
-        for (int k = 0; k < S_COUNT; k++) fprintf(stderr, "%s %s %.3f ms", k ? "," : "", stage_name[k], ms[k]);
-        fprintf(stderr, "\n");
+    if (timer.on) {
+        char header[160];
+        snprintf(header, sizeof(header), "box %d, %d levels, %d transforms, %.3f ms wall; on the device, summed over the levels", n, L, transforms,
+                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count());
+        timer.report("ppm_local_resolution", header);
     }
     return 0;
 }

@@ -11,24 +11,6 @@ std::vector<float> mask_edge_table(int w) {
     return t;
 }
 
-// H(|k|) / n^3 by the integer |k|^2, up to the first radius at which the filter is zero for good
-std::vector<float> mask_lowpass_table(int n, double r_c, double e) {
-    const double r_end = r_c + 0.5 * e, r_one = r_c - 0.5 * e;
-    const long k2_box = 3L * (n / 2) * (n / 2);
-    const long nh = std::min(k2_box, (long)std::floor(r_end * r_end) + 1) + 1;
-    const double inv = 1.0 / ((double)n * n * n);
-    std::vector<float> t((size_t)nh);
-    for (long k2 = 0; k2 < nh; k2++) {
-        const double r = std::sqrt((double)k2);
-        double h;
-        if (r <= r_one) h = 1.0;
-        else if (r >= r_end) h = 0.0;
-        else h = 0.5 * (1.0 + std::cos(kPi * (r - r_one) / e));
-        t[k2] = (float)(h * inv);
-    }
-    return t;
-}
-
 }  // namespace
 
 extern "C" int ppm_mask_volume(const void *map, const void *mask, int on_device, int n, const ppm_mask_cfg *cfg, void *out) {
@@ -51,20 +33,17 @@ extern "C" int ppm_mask_volume(const void *map, const void *mask, int on_device,
     const bool filtered = cfg->filter == 2 && weight != 0.f;
     hipStream_t st = cur_stream();
 
-    DevTmp<float> t_map, t_mask, t_edge, t_h;
+    StagedMap s_map, s_mask;
+    DevTmp<float> t_edge;
     DevTmp<unsigned short> t_d1, t_d2;
     DevTmp<float2> t_f;
-    const float *d_map = (const float *)map, *d_mask = (const float *)mask;
-    float *d_out = (float *)out;
-    if (!on_device) {
-        HIPCHK(t_map.alloc(n3));
-        HIPCHK(t_mask.alloc(n3));
-        HIPCHK(hipMemcpyAsync(t_map.p, map, n3 * sizeof(float), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(t_mask.p, mask, n3 * sizeof(float), hipMemcpyHostToDevice, st));
-        d_map = t_map.p; d_mask = t_mask.p; d_out = t_map.p;        // every voxel of the blend reads and writes its own index only
-    }
+    if (int rc = s_map.in(map, n3, on_device)) return rc;
+    if (int rc = s_mask.in(mask, n3, on_device)) return rc;
+    const float *d_map = s_map.p, *d_mask = s_mask.p;
+    float *d_out = on_device ? (float *)out : s_map.copy.p;          // every voxel of the blend reads and writes its own index only
     // temporaries and tables first, so that the launches below follow each other without a host allocation in between
-    std::vector<float> edge, h;                                      // outlive the asynchronous uploads
+    std::vector<float> edge;                                         // outlives the asynchronous upload
+    LowPass lowpass;
     if (w > 0) {
         edge = mask_edge_table(w);
         HIPCHK(t_edge.alloc(edge.size()));
@@ -72,13 +51,11 @@ extern "C" int ppm_mask_volume(const void *map, const void *mask, int on_device,
         HIPCHK(t_d2.alloc(n3));
     }
     if (filtered) {
-        h = mask_lowpass_table(n, n * cfg->pixel_size / cfg->filter_radius_A, cfg->filter_edge_px);
-        HIPCHK(t_h.alloc(h.size()));
+        if (int rc = lowpass.init(n, n * cfg->pixel_size / cfg->filter_radius_A, cfg->filter_edge_px)) return rc;
         HIPCHK(t_f.alloc(n3));
     }
-    // PPM_TRACE: device time of the call between the uploads and the download, by two events on the call's stream
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (getenv("PPM_TRACE")) { ev0 = ev_get(); ev1 = ev_get(); (void)hipEventRecord(ev0, st); }
+    StageTimer timer;
+    timer.begin("on the device");
     const unsigned nt = (unsigned)((n + kMaskTX - 1) / kMaskTX), na = (unsigned)((n + kMaskTL - 1) / kMaskTL);
     MaskBlendP B; B.map = nullptr; B.mask = nullptr; B.outside = nullptr; B.edge = nullptr; B.out = nullptr; B.weight = 0.f;
     if (w > 0) {
@@ -90,27 +67,18 @@ extern "C" int ppm_mask_volume(const void *map, const void *mask, int on_device,
         HIPCHK(hipGetLastError());
     }
     if (filtered) {
-        HIPCHK(hipMemcpyAsync(t_h.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_mask_r2c, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, d_map, t_f.p, n3);
-        HIPCHK(hipGetLastError());
-        if (int rc = fft3d(t_f.p, n, false)) return rc;
-        hipLaunchKernelGGL(k_mask_lowpass, dim3((unsigned)((n + 63) / 64), (unsigned)n, (unsigned)n), dim3(64), 0, st, t_f.p, t_h.p, (int)h.size(), n);
-        HIPCHK(hipGetLastError());
-        if (int rc = fft3d(t_f.p, n, true)) return rc;
+        if (int rc = real_to_complex(d_map, t_f.p, n3)) return rc;
+        if (int rc = lowpass.apply(t_f.p)) return rc;
     }
     B.map = d_map; B.mask = d_mask; B.outside = filtered ? t_f.p : nullptr; B.edge = t_edge.p; B.out = d_out; B.weight = weight;
     hipLaunchKernelGGL(k_mask_dline<true>, dim3(nt, na, (unsigned)n), dim3(256), 0, st, w > 0 ? t_d2.p : nullptr, (unsigned short *)nullptr, n, w,
                        (size_t)n * n, (size_t)n, B);
     HIPCHK(hipGetLastError());
-    if (ev1) (void)hipEventRecord(ev1, st);
-    if (!on_device) HIPCHK(hipMemcpyAsync(out, d_out, n3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    timer.end();
+    if (int rc = copy_out(out, d_out, n3, on_device)) return rc;
     HIPCHK(hipStreamSynchronize(st));
-    if (ev1) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, ev0, ev1);
-        fprintf(stderr, "ppm_mask_volume: box %d, edge %d, filter %s: %.3f ms on the device\n", n, w, filtered ? "2" : "none", ms);
-        std::lock_guard<std::mutex> lk(g_mu);
-        g.pool.push_back(ev0); g.pool.push_back(ev1);
-    }
+    char header[96];
+    snprintf(header, sizeof(header), "box %d, edge %d, filter %s", n, w, filtered ? "2" : "none");
+    timer.report("ppm_mask_volume", header);
     return 0;
 }

@@ -1,5 +1,5 @@
 // host_post.h — ppm_postprocess: corrected FSC, resolution, B-factor and the sharpened map of two half maps (the work of PYP's
-// external/postprocessing/postprocessing.py).  Included by ppm_lib.hip only, after host_mask.h and host_label.h.
+// external/postprocessing/postprocessing.py).  Included by ppm_lib.hip only, after host_volume.h, host_mask.h and host_label.h.
 #pragma once
 
 namespace {
@@ -126,24 +126,20 @@ extern "C" int ppm_postprocess(const void *half1, const void *half2, const void 
     const int nblocks = n * kPostYSplit;
     const double px = cfg->pixel_size;
 
-    DevTmp<float> t_h1, t_h2, t_mask, t_un, t_ma, t_w, t_a;
+    StagedMap s_h1, s_h2, s_mask;
+    DevTmp<float> t_mask, t_un, t_ma, t_w, t_a;
     DevTmp<float2> t_zu, t_zr;
     DevTmp<unsigned short> t_shell;
     DevTmp<double> t_partial, t_sums, t_sph;
-    DevTmp<unsigned> t_hist;
     DevTmp<unsigned long long> t_count;
-    const float *d_h1 = (const float *)half1, *d_h2 = (const float *)half2, *d_mask = (const float *)mask;
+    if (int rc = s_h1.in(half1, n3, on_device)) return rc;
+    if (int rc = s_h2.in(half2, n3, on_device)) return rc;
+    if (int rc = s_mask.in(mask, n3, on_device)) return rc;
+    const float *d_h1 = s_h1.p, *d_h2 = s_h2.p, *d_mask = s_mask.p;
     float *d_un = (float *)unmasked_out, *d_ma = (float *)masked_out;
     if (!on_device) {
-        HIPCHK(t_h1.alloc(n3)); HIPCHK(t_h2.alloc(n3)); HIPCHK(t_un.alloc(n3)); HIPCHK(t_ma.alloc(n3));
-        HIPCHK(hipMemcpyAsync(t_h1.p, half1, n3 * sizeof(float), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(t_h2.p, half2, n3 * sizeof(float), hipMemcpyHostToDevice, st));
-        d_h1 = t_h1.p; d_h2 = t_h2.p; d_un = t_un.p; d_ma = t_ma.p;
-        if (mask) {
-            HIPCHK(t_mask.alloc(n3));
-            HIPCHK(hipMemcpyAsync(t_mask.p, mask, n3 * sizeof(float), hipMemcpyHostToDevice, st));
-            d_mask = t_mask.p;
-        }
+        HIPCHK(t_un.alloc(n3)); HIPCHK(t_ma.alloc(n3));
+        d_un = t_un.p; d_ma = t_ma.p;
     }
     const std::vector<unsigned short> shells = post_shell_table(n);          // outlives the asynchronous upload
     HIPCHK(t_shell.alloc(shells.size()));
@@ -152,19 +148,7 @@ extern "C" int ppm_postprocess(const void *half1, const void *half2, const void 
     HIPCHK(t_partial.alloc((size_t)nblocks * ns * 4)); HIPCHK(t_sums.alloc((size_t)3 * ns * 4)); HIPCHK(t_w.alloc(ns));
     HIPCHK(t_count.alloc(1));
 
-    // PPM_TRACE: device time per stage, by events on the call's stream
-    const bool trace = getenv("PPM_TRACE") != nullptr;
-    constexpr int kEv = 8;
-    hipEvent_t ev[kEv] = {};
-    if (trace) for (auto &e : ev) e = ev_get();
-    auto mark = [&](int k) { if (trace) (void)hipEventRecord(ev[k], st); };
-    auto release = [&]() {
-        if (!trace) return;
-        std::lock_guard<std::mutex> lk(g_mu);
-        for (auto e : ev) g.pool.push_back(e);
-    };
-    struct Releaser { std::function<void()> f; ~Releaser() { f(); } } releaser{release};
-
+    StageTimer timer;
     const dim3 b256(256), g_vox((unsigned)((n3 + 255) / 256)), g_rows((unsigned)((n + 63) / 64), (unsigned)n, (unsigned)n);
     const size_t shells_lds = (size_t)4 * (ns + 1) * 4 * sizeof(double);
     int transforms = 0;
@@ -176,10 +160,12 @@ extern "C" int ppm_postprocess(const void *half1, const void *half2, const void 
         return 0;
     };
 
-    mark(0);
     // ---- the mask
+    timer.begin("mask");
     double threshold_used = 0.0;
     long mask_voxels = (long)n3;
+    LowPass lowpass;
+    RankPasses rank;
     if (cfg->mask_mode == 2) {
         HIPCHK(t_mask.alloc(n3));
         HIPCHK(t_a.alloc(n3));
@@ -191,19 +177,12 @@ extern "C" int ppm_postprocess(const void *half1, const void *half2, const void 
         const long long r2 = (long long)std::floor(rr);
         double t = cfg->threshold_value;
         if (cfg->threshold_method != 0) {
-            // the low-passed map as ppm_create_mask will see it: the same kernels in the same order give the same bits
-            hipLaunchKernelGGL(k_mask_r2c, g_vox, b256, 0, st, t_a.p, t_zr.p, n3);
-            HIPCHK(hipGetLastError());
+            // the low-passed map as ppm_create_mask will see it: the same LowPass of the same (n, r_c, edge)
+            if (int rc = real_to_complex(t_a.p, t_zr.p, n3)) return rc;
             if (lp) {
-                const std::vector<float> h = mask_lowpass_table(n, r_c, edge);
-                DevTmp<float> t_h;
-                HIPCHK(t_h.alloc(h.size()));
-                HIPCHK(hipMemcpyAsync(t_h.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice, st));
-                if (int rc = transform(t_zr.p, false)) return rc;
-                hipLaunchKernelGGL(k_mask_lowpass, g_rows, dim3(64), 0, st, t_zr.p, t_h.p, (int)h.size(), n);
-                HIPCHK(hipGetLastError());
-                if (int rc = transform(t_zr.p, true)) return rc;
-                HIPCHK(hipStreamSynchronize(st));                       // h and t_h end here
+                if (int rc = lowpass.init(n, r_c, edge)) return rc;
+                if (int rc = lowpass.apply(t_zr.p)) return rc;
+                transforms += 2;
             }
             if (cfg->threshold_method == 1) {
                 HIPCHK(t_sph.alloc((size_t)kPostSumBlocks * 3 + 3));
@@ -217,31 +196,14 @@ extern "C" int ppm_postprocess(const void *half1, const void *half2, const void 
                 t = mean + cfg->threshold_value * std::sqrt(var);
             } else {
                 // the ceil(f n_sphere)-th largest value, 16 bits of its integer image at a time
-                HIPCHK(t_hist.alloc(65536));
-                std::vector<unsigned> hist(65536);
-                unsigned prefix = 0, key = 0;
-                long long want = 0;
-                for (int pass = 0; pass < 2; pass++) {
-                    HIPCHK(hipMemsetAsync(t_hist.p, 0, 65536 * sizeof(unsigned), st));
-                    hipLaunchKernelGGL(k_post_key_hist, g_vox, b256, 0, st, t_zr.p, n, r2, pass, prefix, t_hist.p);
-                    HIPCHK(hipGetLastError());
-                    HIPCHK(hipMemcpyAsync(hist.data(), t_hist.p, 65536 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-                    HIPCHK(hipStreamSynchronize(st));
-                    if (pass == 0) {
-                        long long tot = 0;
-                        for (unsigned v : hist) tot += v;
-                        want = (long long)std::ceil(cfg->threshold_value * (double)tot);
-                        want = std::max(1LL, std::min(want, tot));
-                    }
-                    long long above = 0;
-                    int b = 65535;
-                    for (; b > 0; b--) { if (above + hist[b] >= want) break; above += hist[b]; }
-                    want -= above;
-                    if (pass == 0) prefix = (unsigned)b; else key = (prefix << 16) | (unsigned)b;
-                }
-                const unsigned u = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
-                float tf; memcpy(&tf, &u, sizeof(tf));
-                t = tf;
+                unsigned key = 0;
+                if (int rc = rank.alloc()) return rc;
+                const int rc = rank.run(65536, true, [&](const unsigned *h, int bins) { return rank_of_fraction(cfg->threshold_value, rank_total(h, bins)); },
+                                        [&](int pass, unsigned prefix, unsigned *d_hist) {
+                                            hipLaunchKernelGGL(k_post_key_hist, g_vox, b256, 0, st, t_zr.p, n, r2, pass, prefix, d_hist);
+                                        }, &key);
+                if (rc < 0) return rc;                  // the count is a share of the very histogram walked: it is always found
+                t = rank_signed_key_value(key);
             }
         }
         threshold_used = t;
@@ -265,8 +227,9 @@ extern "C" int ppm_postprocess(const void *half1, const void *half2, const void 
         HIPCHK(hipStreamSynchronize(st));
         mask_voxels = (long)c;
     }
-    mark(1);
+    timer.end();
     // ---- transform 1: the unmasked pair; its shell sums decide s_r
+    timer.begin("unmasked sums");
     hipLaunchKernelGGL(k_post_pack, g_vox, b256, 0, st, d_h1, d_h2, (const float *)nullptr, t_zu.p, n3);
     HIPCHK(hipGetLastError());
     if (int rc = transform(t_zu.p, false)) return rc;
@@ -282,8 +245,9 @@ extern "C" int ppm_postprocess(const void *half1, const void *half2, const void 
         for (int s = 1; s < ns; s++) if (post_fsc(&sums[4 * s]) < cfg->randomize_value) { s_r = s; break; }
     }
     s_r = std::max(1, std::min(s_r, ns - 1));
-    mark(2);
+    timer.end();
     // ---- transforms 2 and 3: randomised phases, back, mask, forward
+    timer.begin("randomised sums");
     hipLaunchKernelGGL(k_post_randomise, g_rows, dim3(64), 0, st, t_zu.p, t_zr.p, t_shell.p, n, s_r, (unsigned)cfg->seed * 0x9E3779B9u);
     HIPCHK(hipGetLastError());
     if (int rc = transform(t_zr.p, true)) return rc;
@@ -291,16 +255,18 @@ extern "C" int ppm_postprocess(const void *half1, const void *half2, const void 
     HIPCHK(hipGetLastError());
     if (int rc = transform(t_zr.p, false)) return rc;
     if (int rc = shell_sums(t_zr.p, 2)) return rc;
-    mark(3);
+    timer.end();
     // ---- transform 4: the masked pair
+    timer.begin("masked sums");
     hipLaunchKernelGGL(k_post_pack, g_vox, b256, 0, st, d_h1, d_h2, d_mask, t_zr.p, n3);
     HIPCHK(hipGetLastError());
     if (int rc = transform(t_zr.p, false)) return rc;
     if (int rc = shell_sums(t_zr.p, 1)) return rc;
     HIPCHK(hipMemcpyAsync(sums.data(), t_sums.p, sums.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    mark(4);
+    timer.end();
     // ---- curves, resolution, B and the filter table on the host
+    timer.begin("filter");
     PostCurves R;
     if (int rc = post_curves(cfg, n, s_r, &sums[0], &sums[(size_t)ns * 4], &sums[(size_t)2 * ns * 4], curves, R)) return rc;
     if (shell_count) for (int s = 0; s < ns; s++) shell_count[s] = (long)sums[4 * s + 3];
@@ -309,16 +275,15 @@ extern "C" int ppm_postprocess(const void *half1, const void *half2, const void 
     hipLaunchKernelGGL(k_post_weight, g_rows, dim3(64), 0, st, t_zu.p, t_shell.p, t_w.p, n);
     HIPCHK(hipGetLastError());
     if (int rc = transform(t_zu.p, true)) return rc;
-    mark(5);
+    timer.end();
+    timer.begin("outputs");
     hipLaunchKernelGGL(k_post_out, g_rows, dim3(64), 0, st, t_zu.p, d_mask, d_un, d_ma, n, cfg->flip_x ? 1 : 0, cfg->flip_y ? 1 : 0, cfg->flip_z ? 1 : 0);
     HIPCHK(hipGetLastError());
-    mark(6);
-    if (!on_device) {
-        HIPCHK(hipMemcpyAsync(unmasked_out, d_un, n3 * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(masked_out, d_ma, n3 * sizeof(float), hipMemcpyDeviceToHost, st));
-    }
+    timer.end();
+    if (int rc = copy_out(unmasked_out, d_un, n3, on_device)) return rc;
+    if (int rc = copy_out(masked_out, d_ma, n3, on_device)) return rc;
     if (mask_out) {
-        if (d_mask) HIPCHK(hipMemcpyAsync(mask_out, d_mask, n3 * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+        if (d_mask) { if (int rc = copy_out(mask_out, d_mask, n3, on_device)) return rc; }
         else if (on_device) { hipLaunchKernelGGL(k_post_fill, g_vox, b256, 0, st, (float *)mask_out, 1.f, n3); HIPCHK(hipGetLastError()); }
         else std::fill((float *)mask_out, (float *)mask_out + n3, 1.f);
     }
@@ -327,11 +292,6 @@ extern "C" int ppm_postprocess(const void *half1, const void *half2, const void 
         info->s_r = s_r; info->res_shell = R.s_res; info->fit_shells = R.fit_shells; info->transforms = transforms;
         info->resolution = R.resolution; info->bfactor = R.bfactor; info->threshold = threshold_used; info->mask_voxels = mask_voxels;
     }
-    if (trace) {
-        float ms[6] = {};
-        for (int k = 0; k < 6; k++) (void)hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
-        fprintf(stderr, "ppm_postprocess: box %d, %d transforms: mask %.3f ms, unmasked sums %.3f ms, randomised sums %.3f ms, masked sums %.3f ms, "
-                        "filter %.3f ms, outputs %.3f ms on the device\n", n, transforms, ms[0], ms[1], ms[2], ms[3], ms[4], ms[5]);
-    }
+    timer.report("ppm_postprocess", "box " + std::to_string(n) + ", " + std::to_string(transforms) + " transforms");
     return 0;
 }

@@ -202,15 +202,12 @@ extern "C" int ppm_fit_volume(const void *vol, int on_device, int n_in, double p
     hipStream_t st = cur_stream();
     const int P = info->P, M = info->M, B = box_out;
     const size_t n3 = (size_t)n_in * n_in * n_in, p3 = (size_t)P * P * P, m3 = (size_t)M * M * M, b3 = (size_t)B * B * B;
-    DevTmp<float> t_in, t_p, t_m, t_tmp, t_out;
-    const float *d_in = (const float *)vol;
+    StagedMap s_in;
+    DevTmp<float> t_p, t_m, t_tmp, t_out;
+    if (int rc = s_in.in(vol, n3, on_device)) return rc;
+    const float *d_in = s_in.p;
     float *d_out = (float *)out;
-    if (!on_device) {
-        HIPCHK(t_in.alloc(n3));
-        HIPCHK(t_out.alloc(b3));
-        HIPCHK(hipMemcpyAsync(t_in.p, vol, n3 * sizeof(float), hipMemcpyHostToDevice, st));
-        d_in = t_in.p; d_out = t_out.p;
-    }
+    if (!on_device) { HIPCHK(t_out.alloc(b3)); d_out = t_out.p; }
     HIPCHK(t_p.alloc(p3));
     HIPCHK(t_m.alloc(m3));
     if (P != M) HIPCHK(t_tmp.alloc(resample_tmp_floats(3, 1, P, M)));
@@ -218,7 +215,7 @@ extern "C" int ppm_fit_volume(const void *vol, int on_device, int n_in, double p
     if (int rc = resize_device(d_in, t_p.p, 3, 1, n_in, P, 0, &pad1, 0)) return rc;
     if (int rc = resample_device(t_p.p, t_m.p, 3, 1, P, M, t_tmp.p)) return rc;
     if (int rc = resize_device(t_m.p, d_out, 3, 1, M, B, 0, &pad2, 0)) return rc;
-    if (!on_device) HIPCHK(hipMemcpyAsync(out, d_out, b3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (int rc = copy_out(out, d_out, b3, on_device)) return rc;
     HIPCHK(hipStreamSynchronize(st));
     info->pad_value_1 = pad1; info->pad_value_2 = pad2;
     return 0;

@@ -37,6 +37,7 @@
 #include "ppm_locres_kernels.h"
 #include "ppm_resample_plan.h"
 #include "ppm_resample_kernels.h"
+#include "ppm_rank.h"
 
 using namespace ppm;
 
@@ -46,6 +47,7 @@ using namespace ppm;
 #include "host_csp.h"
 #include "host_frames.h"
 #include "host_sva.h"
+#include "host_volume.h"
 #include "host_mask.h"
 #include "host_label.h"
 #include "host_post.h"

@@ -336,37 +336,52 @@ def extract_boxes(micrograph, coords, box, radius_A, pixel_size, coordinate_binn
     return res
 
 
+def _cubes(who, maps, out=None, out_box=None):
+    """Shared front of the map entry points: `maps` = the maps of a call to `who`, N^3 float32 of one shape, all numpy arrays or all CUDA
+    torch tensors; `out` = the caller's own array for the result (of the same kind; a cube of out_box, default N) or None.  Returns
+    (on_device, N, maps, pointers, keep-alive); host maps come back as contiguous float32 arrays."""
+    on_dev = bool(getattr(maps[0], "is_cuda", False))
+    if any(bool(getattr(m, "is_cuda", False)) != on_dev for m in list(maps) + ([out] if out is not None else [])):
+        raise ValueError(f"ERROR: {who}: the maps and out must all be on the host or all on the device")
+    if not on_dev:
+        maps = [np.ascontiguousarray(m.numpy() if hasattr(m, "numpy") else m, dtype=np.float32) for m in maps]
+    shape = tuple(int(x) for x in maps[0].shape)
+    if len(shape) != 3 or len(set(shape)) != 1:
+        raise ValueError(f"ERROR: {who}: the maps must be cubic volumes")
+    if any(tuple(int(x) for x in m.shape) != shape for m in maps):
+        raise ValueError(f"ERROR: {who}: the maps have different dimensions")
+    n = shape[0]
+    if out is not None:
+        oshape = (n if out_box is None else int(out_box),) * 3
+        if on_dev and tuple(out.shape) != oshape:
+            raise ValueError(f"ERROR: {who}: out has the wrong shape")
+        if not on_dev and (not isinstance(out, np.ndarray) or out.dtype != np.float32 or out.shape != oshape or not out.flags.c_contiguous):
+            raise ValueError(f"ERROR: {who}: out must be a contiguous float32 array of shape {oshape}")
+    if on_dev:
+        keep = [_volumes_arg(m, 1, n) for m in maps]
+        return True, n, list(maps), [k[0] for k in keep], keep
+    return False, n, maps, [lib.ptr(m) for m in maps], maps
+
+
+def _cube_out(like, on_dev, box, out=None):
+    """(result, pointer): `out` where the caller gave one (checked by _cubes), else a new box^3 float32 array of the kind of `like`."""
+    if on_dev:
+        import torch
+        res = torch.empty((box,) * 3, dtype=torch.float32, device=like.device) if out is None else out
+        return res, _volumes_arg(res, 1, box)[0]
+    res = np.empty((box,) * 3, dtype=np.float32) if out is None else out
+    return res, lib.ptr(res)
+
+
 def mask_volume(vol, mask, cfg, out=None, device=0):
     """Shape-mask a map (ppm_mask_volume, what apply_mask.exe does to last iteration's map): vol, mask = N^3 float32, both numpy
     arrays or both CUDA torch tensors; cfg: abi.MaskCfg.  Returns an array of the kind it was given; `out` (same kind and shape, may
     be `vol` itself) receives the result in place of a new array."""
     lib.init(device)
-    on_dev = bool(getattr(vol, "is_cuda", False))
-    if on_dev != bool(getattr(mask, "is_cuda", False)) or (out is not None and on_dev != bool(getattr(out, "is_cuda", False))):
-        raise ValueError("ERROR: mask_volume: map, mask and out must all be on the host or all on the device")
-    if not on_dev:
-        vol = np.ascontiguousarray(vol.numpy() if hasattr(vol, "numpy") else vol, dtype=np.float32)
-        mask = np.ascontiguousarray(mask.numpy() if hasattr(mask, "numpy") else mask, dtype=np.float32)
-    shape = tuple(int(x) for x in vol.shape)
-    if len(shape) != 3 or len(set(shape)) != 1:
-        raise ValueError("ERROR: mask_volume: the map must be a cubic volume")
-    if tuple(int(x) for x in mask.shape) != shape:
-        raise ValueError("ERROR: mask_volume: map and mask have different dimensions")
-    n = shape[0]
-    if on_dev:
-        import torch
-        res = torch.empty_like(vol) if out is None else out
-        if tuple(res.shape) != shape:
-            raise ValueError("ERROR: mask_volume: out has the wrong shape")
-        pv, _, _ = _volumes_arg(vol, 1, n)
-        pm, _, _ = _volumes_arg(mask, 1, n)
-        po, _, _ = _volumes_arg(res, 1, n)
-    else:
-        res = np.empty_like(vol) if out is None else out
-        if not isinstance(res, np.ndarray) or res.dtype != np.float32 or res.shape != shape or not res.flags.c_contiguous:
-            raise ValueError("ERROR: mask_volume: out must be a contiguous float32 array of the map's shape")
-        pv, pm, po = lib.ptr(vol), lib.ptr(mask), lib.ptr(res)
+    on_dev, n, maps, (pv, pm), keep = _cubes("mask_volume", [vol, mask], out)
+    res, po = _cube_out(maps[0], on_dev, n, out)
     lib.check(lib.load().ppm_mask_volume(pv, pm, 1 if on_dev else 0, n, C.byref(cfg), po))
+    del keep
     return res
 
 
@@ -376,29 +391,11 @@ def create_mask(vol, cfg, out=None, device=0):
     (`out`, same kind and shape, receives it in place of a new array), info an abi.CreateMaskInfo.  A refusal - a threshold no voxel
     reaches among them - raises lib.PpmError and leaves `out` as it was."""
     lib.init(device)
-    on_dev = bool(getattr(vol, "is_cuda", False))
-    if out is not None and on_dev != bool(getattr(out, "is_cuda", False)):
-        raise ValueError("ERROR: create_mask: map and out must both be on the host or both on the device")
-    if not on_dev:
-        vol = np.ascontiguousarray(vol.numpy() if hasattr(vol, "numpy") else vol, dtype=np.float32)
-    shape = tuple(int(x) for x in vol.shape)
-    if len(shape) != 3 or len(set(shape)) != 1:
-        raise ValueError("ERROR: create_mask: the map must be a cubic volume")
-    n = shape[0]
-    if on_dev:
-        import torch
-        res = torch.empty_like(vol) if out is None else out
-        if tuple(res.shape) != shape:
-            raise ValueError("ERROR: create_mask: out has the wrong shape")
-        pv, _, _ = _volumes_arg(vol, 1, n)
-        po, _, _ = _volumes_arg(res, 1, n)
-    else:
-        res = np.empty_like(vol) if out is None else out
-        if not isinstance(res, np.ndarray) or res.dtype != np.float32 or res.shape != shape or not res.flags.c_contiguous:
-            raise ValueError("ERROR: create_mask: out must be a contiguous float32 array of the map's shape")
-        pv, po = lib.ptr(vol), lib.ptr(res)
+    on_dev, n, maps, (pv,), keep = _cubes("create_mask", [vol], out)
+    res, po = _cube_out(maps[0], on_dev, n, out)
     info = CreateMaskInfo()
     lib.check(lib.load().ppm_create_mask(pv, 1 if on_dev else 0, n, C.byref(cfg), po, C.byref(info)))
+    del keep
     return res, info
 
 
@@ -408,32 +405,13 @@ def postprocess(half1, half2, cfg, mask=None, device=0):
     must be "external").  Returns dict(unmasked, masked, mask = maps of the kind given; curves = [4, N/2 + 1] float64 (unmasked,
     masked, phase-randomised, corrected FSC); shell_count = [N/2 + 1] int64; info = abi.PostInfo).  A refusal raises lib.PpmError."""
     lib.init(device)
-    maps = [half1, half2] + ([mask] if mask is not None else [])
-    on_dev = bool(getattr(half1, "is_cuda", False))
-    if any(bool(getattr(m, "is_cuda", False)) != on_dev for m in maps):
-        raise ValueError("ERROR: postprocess: the half maps and the mask must all be on the host or all on the device")
-    if not on_dev:
-        maps = [np.ascontiguousarray(m.numpy() if hasattr(m, "numpy") else m, dtype=np.float32) for m in maps]
-    shape = tuple(int(x) for x in maps[0].shape)
-    if len(shape) != 3 or len(set(shape)) != 1:
-        raise ValueError("ERROR: postprocess: the half maps must be cubic volumes")
-    if any(tuple(int(x) for x in m.shape) != shape for m in maps):
-        raise ValueError("ERROR: postprocess: the half maps and the mask have different dimensions")
-    n = shape[0]
-    if on_dev:
-        import torch
-        outs = [torch.empty_like(maps[0]) for _ in range(3)]
-        keep = [_volumes_arg(m, 1, n) for m in maps + outs]
-        ptrs = [k[0] for k in keep]
-    else:
-        outs = [np.empty_like(maps[0]) for _ in range(3)]
-        ptrs = [lib.ptr(m) for m in maps + outs]
-    pm = ptrs[2] if mask is not None else None
-    po = ptrs[-3:]
+    on_dev, n, maps, ptrs, keep = _cubes("postprocess", [half1, half2] + ([mask] if mask is not None else []))
+    outs, po = zip(*[_cube_out(maps[0], on_dev, n) for _ in range(3)])
     ns = n // 2 + 1
     curves, counts, info = np.zeros((4, ns), dtype=np.float64), np.zeros(ns, dtype=np.int64), PostInfo()
-    lib.check(lib.load().ppm_postprocess(ptrs[0], ptrs[1], pm, 1 if on_dev else 0, n, C.byref(cfg), po[0], po[1], po[2], lib.ptr(curves),
-                                         lib.ptr(counts), C.byref(info)))
+    lib.check(lib.load().ppm_postprocess(ptrs[0], ptrs[1], ptrs[2] if mask is not None else None, 1 if on_dev else 0, n, C.byref(cfg),
+                                         po[0], po[1], po[2], lib.ptr(curves), lib.ptr(counts), C.byref(info)))
+    del keep
     return dict(unmasked=outs[0], masked=outs[1], mask=outs[2], curves=curves, shell_count=counts, info=info)
 
 
@@ -445,42 +423,26 @@ def local_resolution(half1, half2, cfg, mask=None, device=0):
     [L, N, N, N, 2] float32 of the kind given: E_A and E_D of every level.  A refusal raises lib.PpmError."""
     from . import abi
     lib.init(device)
-    maps = [half1, half2] + ([mask] if mask is not None else [])
-    on_dev = bool(getattr(half1, "is_cuda", False))
-    if any(bool(getattr(m, "is_cuda", False)) != on_dev for m in maps):
-        raise ValueError("ERROR: local_resolution: the half maps and the mask must all be on the host or all on the device")
-    if not on_dev:
-        maps = [np.ascontiguousarray(m.numpy() if hasattr(m, "numpy") else m, dtype=np.float32) for m in maps]
-    shape = tuple(int(x) for x in maps[0].shape)
-    if len(shape) != 3 or len(set(shape)) != 1:
-        raise ValueError("ERROR: local_resolution: the half maps must be cubic volumes")
-    if any(tuple(int(x) for x in m.shape) != shape for m in maps):
-        raise ValueError("ERROR: local_resolution: the half maps and the mask have different dimensions")
-    n = shape[0]
+    on_dev, n, maps, ptrs, keep = _cubes("local_resolution", [half1, half2] + ([mask] if mask is not None else []))
     call = LocresCfg(pixel_size=cfg.pixel_size, p_value=cfg.p_value, min_res=cfg.min_res, max_res=cfg.max_res, step=cfg.step, keep_levels=0)
-    energies = None
+    energies, pe = None, None
     if cfg.keep_levels:
         try:
             call.keep_levels = len(abi.locres_levels(n, cfg.pixel_size, cfg.min_res, cfg.max_res, cfg.step)[0])
         except ValueError as e:
             raise lib.PpmError(str(e))
-    if on_dev:
-        import torch
-        out = torch.empty_like(maps[0])
-        if call.keep_levels:
-            energies = torch.empty((call.keep_levels,) + shape + (2,), dtype=torch.float32, device=maps[0].device)
-        keep = [_volumes_arg(m, 1, n) for m in maps + [out]]
-        ptrs = [k[0] for k in keep]
-        pe = C.c_void_p(energies.data_ptr()) if energies is not None else None
-    else:
-        out = np.empty_like(maps[0])
-        if call.keep_levels:
-            energies = np.empty((call.keep_levels,) + shape + (2,), dtype=np.float32)
-        ptrs = [lib.ptr(m) for m in maps + [out]]
-        pe = lib.ptr(energies) if energies is not None else None
+        if on_dev:
+            import torch
+            energies = torch.empty((call.keep_levels, n, n, n, 2), dtype=torch.float32, device=maps[0].device)
+            pe = C.c_void_p(energies.data_ptr())
+        else:
+            energies = np.empty((call.keep_levels, n, n, n, 2), dtype=np.float32)
+            pe = lib.ptr(energies)
+    out, po = _cube_out(maps[0], on_dev, n)
     info = LocresInfo()
     lib.check(lib.load().ppm_local_resolution(C.byref(call), ptrs[0], ptrs[1], ptrs[2] if mask is not None else None, 1 if on_dev else 0, n,
-                                              ptrs[-1], pe, C.byref(info)))
+                                              po, pe, C.byref(info)))
+    del keep
     L = info.n_levels
     res = dict(resolution=out, levels=np.array(info.levels[:L], dtype=np.float32), tau=np.array(info.tau[:L], dtype=np.float32),
                counts=np.array(info.counts[:L], dtype=np.int64), info=info)
@@ -566,30 +528,12 @@ def fit_reference(vol, pixel_in, pixel_out, box, out=None, device=0):
     pixel size the map really has (within 1 % of pixel_out)."""
     from .abi import FitInfo
     lib.init(device)
-    on_dev = bool(getattr(vol, "is_cuda", False))
-    if out is not None and on_dev != bool(getattr(out, "is_cuda", False)):
-        raise ValueError("ERROR: fit_reference: map and out must both be on the host or both on the device")
-    if not on_dev:
-        vol = np.ascontiguousarray(vol.numpy() if hasattr(vol, "numpy") else vol, dtype=np.float32)
-    shape = tuple(int(s) for s in vol.shape)
-    if len(shape) != 3 or len(set(shape)) != 1:
-        raise ValueError("ERROR: fit_reference: the map must be a cubic volume")
     box = int(box)
-    oshape = (box, box, box)
-    if on_dev:
-        import torch
-        res = torch.empty(oshape, dtype=torch.float32, device=vol.device) if out is None else out
-        if tuple(res.shape) != oshape:
-            raise ValueError("ERROR: fit_reference: out has the wrong shape")
-        pv, _, _ = _volumes_arg(vol, 1, shape[0])
-        po, _, _ = _volumes_arg(res, 1, box)
-    else:
-        res = np.empty(oshape, dtype=np.float32) if out is None else out
-        if not isinstance(res, np.ndarray) or res.dtype != np.float32 or res.shape != oshape or not res.flags.c_contiguous:
-            raise ValueError("ERROR: fit_reference: out must be a contiguous float32 array of the box's shape")
-        pv, po = lib.ptr(vol), lib.ptr(res)
+    on_dev, n, maps, (pv,), keep = _cubes("fit_reference", [vol], out, out_box=box)
+    res, po = _cube_out(maps[0], on_dev, box, out)
     info = FitInfo()
-    lib.check(lib.load().ppm_fit_volume(pv, 1 if on_dev else 0, shape[0], float(pixel_in), float(pixel_out), box, po, C.byref(info)))
+    lib.check(lib.load().ppm_fit_volume(pv, 1 if on_dev else 0, n, float(pixel_in), float(pixel_out), box, po, C.byref(info)))
+    del keep
     return res, info
 
 

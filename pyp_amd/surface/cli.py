@@ -795,6 +795,63 @@ def merge3d_main(argv=None, stdin=None):
     return 0
 
 
+# ------------------------------------------------------------------------------------------ the map programs: shared steps
+def _read_cubes(prog, paths):
+    """The input maps of a map program, read in full as float32: every file exists, all are cubic and of one shape, or the run ends with
+    ERROR.  Returns (maps, pixel size in the header of the first)."""
+    for p in paths:
+        if not os.path.exists(p):
+            _die(f"ERROR: {prog}: input file {p} does not exist")
+    try:
+        px = float(mrc.read_header(paths[0])["pixel_size"])
+        vols = [mrc.read(p).astype(np.float32) for p in paths]
+    except (IOError, ValueError) as e:
+        _die(str(e))
+    if vols[0].ndim != 3 or len(set(vols[0].shape)) != 1:
+        _die(f"ERROR: {prog}: {paths[0]} is {vols[0].shape}, only cubic maps are supported")
+    for p, v in zip(paths[1:], vols[1:]):
+        if v.shape != vols[0].shape:
+            _die(f"ERROR: {prog}: {paths[0]} is {vols[0].shape}, {p} is {v.shape}")
+    return vols, px
+
+
+def _run_on_gpu(backend, entry, *args):
+    """What a map program computes: backend(*args) where a backend was given, else host.<entry>(*args, device=PPM_DEVICE) on the GPU, under
+    the per-GPU lock.  A refusal (lib.PpmError, ValueError) ends the run with its text."""
+    try:
+        if backend is not None:
+            return backend(*args)
+        from .. import host, lib
+        dev = int(os.environ.get("PPM_DEVICE", "0"))
+        try:
+            with gpu_lock(dev):
+                return getattr(host, entry)(*args, device=dev)
+        except lib.PpmError as e:
+            _die(str(e))
+    except ValueError as e:
+        _die(str(e))
+
+
+def _write_complete(prog, files, pixel, what):
+    """files = [(path, text or map)]: every file is written under path.tmp<pid>; when all are complete they take their names in the order
+    given (so the one whose existence PYP tests goes last).  A failure removes the temporaries and ends the run with ERROR."""
+    tmps = [path + ".tmp%d" % os.getpid() for path, _ in files]
+    try:
+        for (_, content), tmp in zip(files, tmps):
+            if isinstance(content, str):
+                with open(tmp, "w") as f:
+                    f.write(content)
+            else:
+                mrc.write(np.asarray(content, dtype=np.float32), tmp, pixel_size=pixel)
+        for (path, _), tmp in zip(files, tmps):
+            os.replace(tmp, path)
+    except OSError as e:
+        for tmp in tmps:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+        _die(f"ERROR: {prog}: could not write {what}: {e}")
+
+
 # ------------------------------------------------------------------------------------------ apply_mask.exe
 def apply_mask_main(argv=None, stdin=None, backend=None):
     """frealign_v9.11's apply_mask.exe as PYP runs it on last iteration's map (src/pyp/align/core.py:783-856): both files are read in
@@ -808,47 +865,16 @@ def apply_mask_main(argv=None, stdin=None, backend=None):
     print("\n        **   Welcome to ApplyMask (MI355X / libpypmatch)   **\n")
     for k, v in d.items():
         print(f"{k:28s}: {v}")
-    for p in (d["map"], d["mask"]):
-        if not os.path.exists(p):
-            _die(f"ERROR: apply_mask: input file {p} does not exist")
-    try:
-        head = mrc.read_header(d["map"])
-        vol = mrc.read(d["map"]).astype(np.float32)
-        mask = mrc.read(d["mask"]).astype(np.float32)
-    except (IOError, ValueError) as e:
-        _die(str(e))
-    if vol.ndim != 3 or len(set(vol.shape)) != 1:
-        _die(f"ERROR: apply_mask: the input map is {vol.shape}, only cubic maps are supported")
-    if mask.shape != vol.shape:
-        _die(f"ERROR: apply_mask: the map is {vol.shape}, the mask {mask.shape}")
-    px = d["pixel_size"] if d["pixel_size"] is not None else float(head["pixel_size"])
+    (vol, mask), head_px = _read_cubes("apply_mask", [d["map"], d["mask"]])
+    px = d["pixel_size"] if d["pixel_size"] is not None else head_px
     if not px > 0:
         _die(f"ERROR: apply_mask: pixel size {px:g} is not positive")
     cfg = MaskCfg.make(pixel_size=px, edge_width=d["edge_width"], outside_weight=d["outside_weight"], filter=d["filter"],
                        filter_radius_A=d["filter_radius"] if d["filter"] == 2 else 1.0, filter_edge_px=d["filter_edge"])
     t1 = time.time()
-    try:
-        if backend is not None:
-            out = backend(vol, mask, cfg)
-        else:
-            from .. import host, lib
-            dev = int(os.environ.get("PPM_DEVICE", "0"))
-            try:
-                with gpu_lock(dev):
-                    out = host.mask_volume(vol, mask, cfg, device=dev)
-            except lib.PpmError as e:
-                _die(str(e))
-    except ValueError as e:
-        _die(str(e))
+    out = _run_on_gpu(backend, "mask_volume", vol, mask, cfg)
     t2 = time.time()
-    tmp = d["output"] + ".tmp%d" % os.getpid()
-    try:
-        mrc.write(np.asarray(out, dtype=np.float32), tmp, pixel_size=px)
-        os.replace(tmp, d["output"])
-    except OSError as e:
-        if os.path.exists(tmp):
-            os.remove(tmp)
-        _die(f"ERROR: apply_mask: could not write {d['output']}: {e}")
+    _write_complete("apply_mask", [(d["output"], out)], px, d["output"])
     print(f"\nMasked a {vol.shape[0]}^3 map at {px:g} A/pixel: edge {d['edge_width']} pixels, weight outside {d['outside_weight']:g}, filter {d['filter']}")
     print(f"Timing: inputs {t1 - t0:.2f} s, device {t2 - t1:.2f} s, output {time.time() - t2:.2f} s")
     _release_warm()
@@ -870,41 +896,15 @@ def create_mask_main(argv=None, stdin=None, backend=None):
     print("\n        **   Welcome to CreateMask (MI355X / libpypmatch)   **\n")
     for k, v in d.items():
         print(f"{k:28s}: {v}")
-    if not os.path.exists(d["input"]):
-        _die(f"ERROR: create_mask: input file {d['input']} does not exist")
-    try:
-        vol = mrc.read(d["input"]).astype(np.float32)
-    except (IOError, ValueError) as e:
-        _die(str(e))
-    if vol.ndim != 3 or len(set(vol.shape)) != 1:
-        _die(f"ERROR: create_mask: the input map is {vol.shape}, only cubic maps are supported")
+    (vol,), _ = _read_cubes("create_mask", [d["input"]])
     px, n = d["pixel_size"], vol.shape[0]
     edge = min(prompts.CREATE_MASK_EDGE_PX, 2.0 * n * px / d["lowpass"]) if d["lowpass"] > 0 else 0.0
     cfg = CreateMaskCfg.make(pixel_size=px, outer_radius_A=d["outer_radius"], threshold=d["threshold"], lowpass_A=d["lowpass"],
                              lowpass_edge_px=edge, rebin=d["rebin"])
     t1 = time.time()
-    try:
-        if backend is not None:
-            mask, info = backend(vol, cfg)
-        else:
-            from .. import host, lib
-            dev = int(os.environ.get("PPM_DEVICE", "0"))
-            try:
-                with gpu_lock(dev):
-                    mask, info = host.create_mask(vol, cfg, device=dev)
-            except lib.PpmError as e:
-                _die(str(e))
-    except ValueError as e:
-        _die(str(e))
+    mask, info = _run_on_gpu(backend, "create_mask", vol, cfg)
     t2 = time.time()
-    tmp = d["output"] + ".tmp%d" % os.getpid()
-    try:
-        mrc.write(np.asarray(mask, dtype=np.float32), tmp, pixel_size=px)
-        os.replace(tmp, d["output"])
-    except OSError as e:
-        if os.path.exists(tmp):
-            os.remove(tmp)
-        _die(f"ERROR: create_mask: could not write {d['output']}: {e}")
+    _write_complete("create_mask", [(d["output"], mask)], px, d["output"])
     print(f"\nMask of a {n}^3 map at {px:g} A/pixel: outer radius {d['outer_radius']:g} A, threshold {d['threshold']:g}, "
           f"low-pass {d['lowpass']:g} A (edge {edge:g} Fourier pixels), re-bin value {d['rebin']:g}")
     print(f"Density inside the radius      : {info.density_min:g} .. {info.density_max:g}")
@@ -953,18 +953,7 @@ def postprocessing_main(argv=None, backend=None):
     for k, v in d.items():
         print(f"{k:28s}: {v}")
     inputs = [d["half1"], d["half2"]] + ([d["mask"]] if d["mask"] is not None else [])
-    for p in inputs:
-        if not os.path.exists(p):
-            _die(f"ERROR: postprocessing: input file {p} does not exist")
-    try:
-        vols = [mrc.read(p).astype(np.float32) for p in inputs]
-    except (IOError, ValueError) as e:
-        _die(str(e))
-    if vols[0].ndim != 3 or len(set(vols[0].shape)) != 1:
-        _die(f"ERROR: postprocessing: the first half map is {vols[0].shape}, only cubic maps are supported")
-    for p, v in zip(inputs[1:], vols[1:]):
-        if v.shape != vols[0].shape:
-            _die(f"ERROR: postprocessing: {inputs[0]} is {vols[0].shape}, {p} is {v.shape}")
+    vols, _ = _read_cubes("postprocessing", inputs)
     n, px = vols[0].shape[0], d["angpix"]
     if not prompts.postprocessing_box_ok(n):
         _die(f"ERROR: postprocessing: the box must be even, 32..512, with prime factors 2, 3, 5, 7, got {n}")
@@ -972,19 +961,7 @@ def postprocessing_main(argv=None, backend=None):
         print("--xml: nothing in PYP reads such a file; none is written")
     cfg = post_cfg_from_options(d)
     t1 = time.time()
-    try:
-        if backend is not None:
-            res = backend(vols[0], vols[1], cfg, vols[2] if len(vols) > 2 else None)
-        else:
-            from .. import host, lib
-            dev = int(os.environ.get("PPM_DEVICE", "0"))
-            try:
-                with gpu_lock(dev):
-                    res = host.postprocess(vols[0], vols[1], cfg, mask=vols[2] if len(vols) > 2 else None, device=dev)
-            except lib.PpmError as e:
-                _die(str(e))
-    except ValueError as e:
-        _die(str(e))
+    res = _run_on_gpu(backend, "postprocess", vols[0], vols[1], cfg, vols[2] if len(vols) > 2 else None)
     t2 = time.time()
     info = res["info"]
     header = [f"postprocessing: box {n}, pixel size {px:g} A, mask {d['mask_mode']}",
@@ -997,23 +974,7 @@ def postprocessing_main(argv=None, backend=None):
     if d["mask_mode"] == "auto":
         files.append((out + "-automask.mrc", res["mask"]))
     files += [(out + "_data.fsc", format_fsc_file(res["curves"], n, px, header)), (out + "-masked.mrc", res["masked"])]
-    tmps = []
-    try:
-        for path, what in files:
-            tmp = path + ".tmp%d" % os.getpid()
-            tmps.append(tmp)
-            if isinstance(what, str):
-                with open(tmp, "w") as f:
-                    f.write(what)
-            else:
-                mrc.write(np.asarray(what, dtype=np.float32), tmp, pixel_size=px)
-        for (path, _), tmp in zip(files, tmps):
-            os.replace(tmp, path)
-    except OSError as e:
-        for tmp in tmps:
-            if os.path.exists(tmp):
-                os.remove(tmp)
-        _die(f"ERROR: postprocessing: could not write the outputs of {out}: {e}")
+    _write_complete("postprocessing", files, px, f"the outputs of {out}")
     print(f"\nPost-processed two {n}^3 half maps at {px:g} A/pixel with {info.transforms} transforms")
     if d["mask_mode"] == "auto":
         print(f"Automatic mask                 : threshold {info.threshold:g} ({d['threshold_method']}), {info.mask_voxels} voxels in its body")
@@ -1049,19 +1010,8 @@ def resmap_main(argv=None, backend=None):
     for k, v in d.items():
         print(f"{k:28s}: {v}")
     inputs = [d["half1"], d["half2"]] + ([d["maskVol"]] if d["maskVol"] is not None else [])
-    for p in inputs:
-        if not os.path.exists(p):
-            _die(f"ERROR: resmap: input file {p} does not exist")
-    try:
-        vols = [mrc.read(p).astype(np.float32) for p in inputs]
-        px = d["vxSize"] if d["vxSize"] is not None else float(mrc.read_header(d["half1"])["pixel_size"])
-    except (IOError, ValueError) as e:
-        _die(str(e))
-    if vols[0].ndim != 3 or len(set(vols[0].shape)) != 1:
-        _die(f"ERROR: resmap: the first half map is {vols[0].shape}, only cubic maps are supported")
-    for p, v in zip(inputs[1:], vols[1:]):
-        if v.shape != vols[0].shape:
-            _die(f"ERROR: resmap: {inputs[0]} is {vols[0].shape}, {p} is {v.shape}")
+    vols, head_px = _read_cubes("resmap", inputs)
+    px = d["vxSize"] if d["vxSize"] is not None else head_px
     n = vols[0].shape[0]
     if not prompts.postprocessing_box_ok(n):
         _die(f"ERROR: resmap: the box must be even, 32..512, with prime factors 2, 3, 5, 7, got {n}")
@@ -1072,42 +1022,14 @@ def resmap_main(argv=None, backend=None):
         _die(str(e))
     mask = vols[2] if len(vols) > 2 else None
     t1 = time.time()
-    try:
-        if backend is not None:
-            res = backend(vols[0], vols[1], cfg, mask)
-        else:
-            from .. import host, lib
-            dev = int(os.environ.get("PPM_DEVICE", "0"))
-            try:
-                with gpu_lock(dev):
-                    res = host.local_resolution(vols[0], vols[1], cfg, mask=mask, device=dev)
-            except lib.PpmError as e:
-                _die(str(e))
-    except ValueError as e:
-        _die(str(e))
+    res = _run_on_gpu(backend, "local_resolution", vols[0], vols[1], cfg, mask)
     t2 = time.time()
     info = res["info"]
     L = info.n_levels
     out_map, out_cmd = prompts.resmap_output_names(d["half1"])
     files = [(out_cmd, format_chimera_script(d["half1"], d["half2"], out_map, float(info.levels[0]), float(info.levels[L - 1]))),
              (out_map, res["resolution"])]
-    tmps = []
-    try:
-        for path, what in files:
-            tmp = path + ".tmp%d" % os.getpid()
-            tmps.append(tmp)
-            if isinstance(what, str):
-                with open(tmp, "w") as f:
-                    f.write(what)
-            else:
-                mrc.write(np.asarray(what, dtype=np.float32), tmp, pixel_size=px)
-        for (path, _), tmp in zip(files, tmps):
-            os.replace(tmp, path)
-    except OSError as e:
-        for tmp in tmps:
-            if os.path.exists(tmp):
-                os.remove(tmp)
-        _die(f"ERROR: resmap: could not write {out_map}: {e}")
+    _write_complete("resmap", files, px, out_map)
     print(f"\nLocal resolution of two {n}^3 half maps at {px:g} A/pixel: p-value {d['pVal']:g}, {info.n_inside} voxels inside the mask, "
           f"{L} levels, {info.transforms} transforms")
     print("   level (A)      threshold   voxels assigned")
@@ -1267,42 +1189,15 @@ def fit_reference_main(argv=None, backend=None):
             raise
         _die("ERROR: fit_reference: usage: fit_reference IN.mrc OUT.mrc --pixel A --box B [--pixel-in A0]")
     print("\n        **   Welcome to FitReference (MI355X / libpypmatch)   **\n")
-    if not os.path.exists(a.input):
-        _die(f"ERROR: fit_reference: input file {a.input} does not exist")
-    try:
-        head = mrc.read_header(a.input)
-        vol = mrc.read(a.input).astype(np.float32)
-    except (IOError, ValueError) as e:
-        _die(str(e))
-    if vol.ndim != 3 or len(set(vol.shape)) != 1:
-        _die(f"ERROR: fit_reference: the input map is {vol.shape}, only cubic maps are supported")
-    px_in = a.pixel_in if a.pixel_in is not None else float(head["pixel_size"])
+    (vol,), head_px = _read_cubes("fit_reference", [a.input])
+    px_in = a.pixel_in if a.pixel_in is not None else head_px
     if not (px_in > 0 and a.pixel > 0):
         _die(f"ERROR: fit_reference: pixel sizes must be positive, got {px_in:g} and {a.pixel:g}")
     if not 8 <= a.box <= 512 or not 8 <= vol.shape[0] <= 512:
         _die(f"ERROR: fit_reference: boxes must be 8..512, got {vol.shape[0]} -> {a.box}")
     t1 = time.time()
-    try:
-        if backend is not None:
-            out, info = backend(vol, px_in, a.pixel, a.box)
-        else:
-            from .. import host, lib
-            dev = int(os.environ.get("PPM_DEVICE", "0"))
-            try:
-                with gpu_lock(dev):
-                    out, info = host.fit_reference(vol, px_in, a.pixel, a.box, device=dev)
-            except lib.PpmError as e:
-                _die(str(e))
-    except ValueError as e:
-        _die(str(e))
-    tmp = a.output + ".tmp%d" % os.getpid()
-    try:
-        mrc.write(np.asarray(out, dtype=np.float32), tmp, pixel_size=info.pixel_achieved)
-        os.replace(tmp, a.output)
-    except OSError as e:
-        if os.path.exists(tmp):
-            os.remove(tmp)
-        _die(f"ERROR: fit_reference: could not write {a.output}: {e}")
+    out, info = _run_on_gpu(backend, "fit_reference", vol, px_in, a.pixel, a.box)
+    _write_complete("fit_reference", [(a.output, out)], info.pixel_achieved, a.output)
     print(f"Reference of {vol.shape[0]}^3 at {px_in:g} A -> box {a.box} at {a.pixel:g} A: shows {info.n_c} voxels of the input, resized to {info.P}, "
           f"resampled to {info.M}")
     print(f"Pixel size achieved            : {info.pixel_achieved:.6g} A ({100.0 * info.rel_error:.3f} % from the request)")

@@ -164,6 +164,39 @@ def test_device_tensors_and_reproducibility(H):
     assert np.array_equal(a, b) and bytes(ai) == bytes(bi) and np.array_equal(a, want)
 
 
+def test_tracing_changes_no_bit(H, monkeypatch, capfd):
+    """PPM_TRACE=1 times the stages with events on the call's stream: the mask and every number of info stay what they are without it,
+    and stderr gets one line that names the four stages."""
+    c, _, _ = lowpass(32)
+    cfg = cfg_of(c)
+    a, ai = H.create_mask(c["vol"], cfg)
+    capfd.readouterr()
+    monkeypatch.setenv("PPM_TRACE", "1")
+    b, bi = H.create_mask(c["vol"], cfg)
+    monkeypatch.delenv("PPM_TRACE")
+    assert np.array_equal(a, b) and bytes(ai) == bytes(bi)
+    lines = [ln for ln in capfd.readouterr().err.splitlines() if ln.startswith("ppm_create_mask:")]
+    assert len(lines) == 1, lines
+    for stage in ("low-pass", "threshold", "labelling", "re-bin"):
+        assert f" {stage} " in lines[0] and " ms" in lines[0], (stage, lines[0])
+
+
+def test_empty_threshold_is_refused_under_tracing(H, monkeypatch):
+    """The refusal of test_empty_threshold_is_refused leaves the call between two stages: the text is the same with PPM_TRACE=1, and the
+    next call of the process gives what it gives without tracing."""
+    from pyp_amd import lib
+    c, _, _ = lowpass(32)
+    want, wi = H.create_mask(c["vol"], cfg_of(c))
+    monkeypatch.setenv("PPM_TRACE", "1")
+    vol, radius, _, _, _ = exact("equal_bodies", 65)
+    out = np.full_like(vol, 7.0)
+    with pytest.raises(lib.PpmError, match="ERROR.*ranges from 0 to 1"):
+        H.create_mask(vol, CreateMaskCfg.make(1.0, radius, 1.5), out=out)
+    assert (out == 7.0).all()
+    got, gi = H.create_mask(c["vol"], cfg_of(c))
+    assert np.array_equal(got, want) and bytes(gi) == bytes(wi)
+
+
 def test_refusals(H):
     from pyp_amd import lib
     v4, v33, v32 = (np.ones((k, k, k), np.float32) for k in (4, 33, 32))

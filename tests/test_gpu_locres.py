@@ -97,6 +97,29 @@ def test_two_calls_agree_and_the_debug_output_changes_nothing(H):
     assert np.array_equal(again["energies"], g["energies"])
 
 
+def test_tracing_changes_no_bit(H, monkeypatch, capfd):
+    """PPM_TRACE=1 times the stages with pairs of events on the call's stream, summed over three levels: map, energies and info stay what
+    they are without it, and stderr gets one line that names every stage."""
+    n = 32
+    h1, h2, m = F.gpu_inputs(n, True)
+    lo, hi, _ = F.gpu_level_grid(n)
+    cfg = LocresCfg.make(PX, p_value=F.GPU_P, min_res=lo, max_res=hi, step=(hi - lo) / 2.0, keep_levels=True)
+    plain = H.local_resolution(h1, h2, cfg, mask=m)
+    capfd.readouterr()
+    monkeypatch.setenv("PPM_TRACE", "1")
+    traced = H.local_resolution(h1, h2, cfg, mask=m)
+    monkeypatch.delenv("PPM_TRACE")
+    assert plain["info"].n_levels == 3 and plain["info"].transforms == 10
+    assert np.array_equal(traced["resolution"], plain["resolution"]) and np.array_equal(traced["energies"], plain["energies"])
+    assert np.array_equal(traced["tau"], plain["tau"]) and np.array_equal(traced["counts"], plain["counts"]) and bytes(traced["info"]) == bytes(plain["info"])
+    lines = [ln for ln in capfd.readouterr().err.splitlines() if ln.startswith("ppm_local_resolution:")]
+    assert len(lines) == 1, lines
+    assert "box 32, 3 levels, 10 transforms" in lines[0] and " ms wall" in lines[0], lines[0]
+    for stage in ("init + pack", "forward transform", "band", "band back", "square", "squares forward", "window", "window back",
+                  "threshold (2 histogram passes)", "assign"):
+        assert f" {stage} " in lines[0], (stage, lines[0])
+
+
 def test_device_maps_off_a_16_byte_boundary(H):
     n = 32
     g = gpu_case(H, n, True)

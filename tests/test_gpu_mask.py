@@ -180,6 +180,21 @@ def test_device_tensors_and_reproducibility(H):
     assert H.mask_volume(tv, tm, cfg, out=tv) is tv and np.array_equal(tv.cpu().numpy(), a)
 
 
+def test_tracing_changes_no_bit(H, monkeypatch, capfd):
+    """PPM_TRACE=1 times the call with events on its stream: the masked map stays what it is without it, and stderr gets one line."""
+    v, m = inputs(32)
+    cfg = MaskCfg.make(PX, edge_width=3, outside_weight=0.5, filter=2, filter_radius_A=8.0, filter_edge_px=4.0)
+    a = H.mask_volume(v, m, cfg)
+    capfd.readouterr()
+    monkeypatch.setenv("PPM_TRACE", "1")
+    b = H.mask_volume(v, m, cfg)
+    monkeypatch.delenv("PPM_TRACE")
+    assert np.array_equal(a, b)
+    lines = [ln for ln in capfd.readouterr().err.splitlines() if ln.startswith("ppm_mask_volume:")]
+    assert len(lines) == 1, lines
+    assert "box 32, edge 3, filter 2" in lines[0] and " on the device " in lines[0] and " ms" in lines[0], lines[0]
+
+
 # ------------------------------------------------------------------------------------------ 8: the executable
 def test_executable_overwrites_its_input(H, tmp_path, monkeypatch):
     from pyp_amd.formats import mrc

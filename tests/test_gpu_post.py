@@ -241,6 +241,44 @@ def test_automask_sigma_and_volume(H, n):
         assert t == float(np.float32(t))
 
 
+def _same(a, b):
+    for k in ("unmasked", "masked", "mask"):
+        x, y = (r[k].cpu().numpy() if hasattr(r[k], "is_cuda") else r[k] for r in (a, b))
+        assert np.array_equal(x, y), k
+    assert np.array_equal(a["curves"], b["curves"]) and np.array_equal(a["shell_count"], b["shell_count"])
+    assert bytes(a["info"]) == bytes(b["info"])
+
+
+def test_automask_host_and_device_agree(H):
+    """Host arrays and CUDA tensors give the same bits with the automatic mask by sigma (test_two_calls_agree holds the two kinds to each
+    other with an external mask)."""
+    a = auto_case(32)
+    cfg = cfg_of(P.options(mask="auto", automask_lp=P.AUTOMASK_LP, threshold_method="sigma", threshold_value=1.5))
+    t = [torch.from_numpy(np.array(x)).cuda() for x in (a["h1"], a["h2"])]
+    host, dev = H.postprocess(a["h1"], a["h2"], cfg), H.postprocess(t[0], t[1], cfg)
+    assert dev["mask"].is_cuda and host["info"].transforms == 11
+    _same(host, dev)
+
+
+def test_tracing_changes_no_bit(H, monkeypatch, capfd):
+    """PPM_TRACE=1 times the stages with events on the call's stream; with the automatic mask by volume fraction the two histogram passes
+    and the low-pass run inside the first stage.  Maps, curves and info stay what they are without it, and stderr gets one line of
+    ppm_postprocess that names the six stages."""
+    a = auto_case(32)
+    cfg = cfg_of(P.options(mask="auto", automask_lp=P.AUTOMASK_LP, threshold_method="volume", threshold_value=0.3))
+    plain = H.postprocess(a["h1"], a["h2"], cfg)
+    capfd.readouterr()
+    monkeypatch.setenv("PPM_TRACE", "1")
+    traced = H.postprocess(a["h1"], a["h2"], cfg)
+    monkeypatch.delenv("PPM_TRACE")
+    assert plain["info"].transforms == 11
+    _same(plain, traced)
+    lines = [ln for ln in capfd.readouterr().err.splitlines() if ln.startswith("ppm_postprocess:")]
+    assert len(lines) == 1, lines
+    for stage in ("mask", "unmasked sums", "randomised sums", "masked sums", "filter", "outputs"):
+        assert f" {stage} " in lines[0] and " ms" in lines[0], (stage, lines[0])
+
+
 # ------------------------------------------------------------------------------------------ 4: refusals
 def test_refusals(H):
     from pyp_amd import lib
