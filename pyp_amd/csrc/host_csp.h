@@ -21,26 +21,42 @@ struct CspUnits {
     std::vector<unsigned char> refined;
     std::vector<int> unit_slot, active;             // active: refined units with at least one usable row
     std::vector<int> eval_rows, final_rows;         // usable rows of the active units, grouped by unit; all rows of the refined units
+    std::vector<int> uoff;                          // [active + 1] the active units' offsets in eval_rows (csp_upload_tables)
     int n_slots = 0;
 };
 // free parameters and step schedule of the compass search
 struct CspSearch { int en[6] = { 0, 0, 0, 0, 0, 0 }; double tol[6] = { 0, 0, 0, 0, 0, 0 }; int nfree = 0, T = 0; double ha0 = 0, hs0 = 0; };
+// where the poses of a compass search live on the device, and what it scores into
+struct CompassPoses {
+    int kind = PPM_CSP_PARTICLES, n_active = 0;
+    double *Nmat = nullptr; int nstride = 9;        // rotation matrices, doubles from one unit's to the next
+    double *pshift = nullptr; int pstride = 3;      // shifts likewise (the sub-volume search keeps N and p in one row of 12)
+    double *tl = nullptr;                           // tilt parameters (null: particles only)
+    const int *active = nullptr, *unit_slot = nullptr;      // active list and slot table (null: the identity)
+    double *delta = nullptr, *mean = nullptr;       // [slot][ncand][6] candidates of the compass sweep and its [unit][ncand] means
+};
 // One compass search on the stream, for every search whose state and decisions live on the device (k_csp_step_*): the first candidates,
 // then per iteration band -> candidates' scores -> trial step -> its score -> accept, steps halved after each; nothing waits on the host.
-// The caller fills SP but for the steps and the two score buffers (mean: [unit][ncand] of the compass sweep, tmean: [unit] of the trial); band_of(ha, hs) gives an iteration's band, eval(delta, ncand, band, means_out) enqueues the
-// caller's evaluation of `ncand` candidates per unit (non-zero: give up with that code).
+// `ws` is the state (ensured by the caller for at.n_active states, ws.acc filled); en / tol: free parameters and their bounds, 1 + 2 per
+// free parameter candidates a sweep.  band_of(ha, hs) gives an iteration's band, eval(delta, ncand, band, means_out) enqueues the caller's
+// evaluation of `ncand` candidates per unit (1: the trial step; non-zero: give up with that code).
 template <class BandOf, class Eval>
-static int compass_enqueue(CspStepP &SP, double *mean, double *tmean, int T, double ha, double hs, BandOf band_of, Eval eval) {
-    SP.mean = mean; SP.tmean = tmean;
+static int compass_enqueue(CompassWs &ws, const CompassPoses &at, const int *en, const double *tol, int T, double ha, double hs, BandOf band_of, Eval eval) {
+    CspStepP SP;
+    SP.kind = at.kind; SP.n_active = at.n_active; SP.ncand = 1; SP.active = at.active; SP.unit_slot = at.unit_slot;
+    for (int i = 0; i < 6; i++) { SP.en[i] = en[i]; SP.tol[i] = tol[i]; SP.ncand += en[i] ? 2 : 0; }
+    SP.acc = ws.acc.p; SP.dtrial = ws.dtrial.p; SP.fpm = ws.fpm.p; SP.delta_c = at.delta; SP.delta_t = ws.delta_t.p;
+    SP.Nmat = at.Nmat; SP.pshift = at.pshift; SP.tl = at.tl; SP.nstride = at.nstride; SP.pstride = at.pstride;
+    SP.mean = at.mean; SP.tmean = ws.tmean.p;
     const unsigned gstep = (unsigned)((SP.n_active + 127) / 128);
     SP.ha = ha; SP.hs = hs; SP.ha_next = ha; SP.hs_next = hs;
     hipLaunchKernelGGL(k_csp_step_init, dim3(gstep), dim3(128), 0, cur_stream(), SP);
     for (int it = 0; it < T; it++) {
         const double band = band_of(ha, hs);
         SP.ha = ha; SP.hs = hs; SP.ha_next = 0.5 * ha; SP.hs_next = 0.5 * hs;
-        if (int rc = eval(SP.delta_c, SP.ncand, band, mean)) return rc;
+        if (int rc = eval(SP.delta_c, SP.ncand, band, at.mean)) return rc;
         hipLaunchKernelGGL(k_csp_step_trial, dim3(gstep), dim3(128), 0, cur_stream(), SP);
-        if (int rc = eval(SP.delta_t, 1, band, tmean)) return rc;
+        if (int rc = eval(SP.delta_t, 1, band, ws.tmean.p)) return rc;
         hipLaunchKernelGGL(k_csp_step_accept, dim3(gstep), dim3(128), 0, cur_stream(), SP);
         ha *= 0.5; hs *= 0.5;
     }
@@ -54,7 +70,7 @@ struct CspRun {
     int kind = 0, n_proj = 0, n_part = 0, n_tilt = 0;
     CspEvalP EP; bool tab = false;
     const double *particles_in = nullptr;           // the caller's particle block (identifiers of the searched particles)
-    std::vector<double> hN, hp, htl;                // the units as the device holds them
+    std::vector<double> hN, hp, htl, rowtab;        // staging: the units as the device holds them, the exhaustive stage's row tables
     double acct_gathers = 0; long acct_sweeps = 0;  // for the roofline (ppm_refine_last_counts)
     double bf() const { return cfg->band_factor == 0 ? 3.0 : cfg->band_factor; }
     int prefix_of(double rband) const { int rg = (int)std::ceil(rband); if (rg > gm.B + 1) rg = gm.B + 1; return sl.ring_off[rg]; }
@@ -71,24 +87,24 @@ static int csp_prepare_spectra(CspRun &c, const void *images, int images_on_devi
     if (int rc = ref->samples.ensure(S_pad)) return rc;
     HIPCHK(hipMemcpyAsync(ref->samples.p, c.sl.packed.data(), S_pad * sizeof(uint32_t), hipMemcpyHostToDevice, cur_stream()));
     const int CH = (int)std::min<size_t>((size_t)n_proj, std::max<size_t>(64, ((size_t)2 << 30) / (NN * 4 + HW * 8)));
-    if (int rc = ref->c_Il.ensure((size_t)n_proj * S_pad)) return rc;
-    if (int rc = ref->c_cw.ensure((size_t)n_proj * S_pad)) return rc;
-    if (int rc = ref->c_band.ensure((size_t)CH * HW)) return rc;
-    if (int rc = ref->c_rows.ensure((size_t)n_proj * PPM_NCOL)) return rc;
-    if (mode4) if (int rc = ref->c_wring.ensure((size_t)n_proj * (gm.B + 2))) return rc;
-    if (!images_on_device) if (int rc = ref->c_img.ensure((size_t)CH * NN)) return rc;
-    HIPCHK(hipMemcpyAsync(ref->c_rows.p, rows, (size_t)n_proj * PPM_NCOL * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    if (int rc = ref->spectra.Il.ensure((size_t)n_proj * S_pad)) return rc;
+    if (int rc = ref->spectra.cw.ensure((size_t)n_proj * S_pad)) return rc;
+    if (int rc = ref->spectra.band.ensure((size_t)CH * HW)) return rc;
+    if (int rc = ref->spectra.rows.ensure((size_t)n_proj * PPM_NCOL)) return rc;
+    if (mode4) if (int rc = ref->spectra.wring.ensure((size_t)n_proj * (gm.B + 2))) return rc;
+    if (!images_on_device) if (int rc = ref->spectra.img.ensure((size_t)CH * NN)) return rc;
+    HIPCHK(hipMemcpyAsync(ref->spectra.rows.p, rows, (size_t)n_proj * PPM_NCOL * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
     const double fall = cfg->mask_falloff > 0 ? cfg->mask_falloff : 20.0;
     for (int c0 = 0; c0 < n_proj; c0 += CH) {
         const int nb = std::min(CH, n_proj - c0);
         const float *d_img = (const float *)images + (size_t)c0 * NN;
         if (!images_on_device) {
-            HIPCHK(hipMemcpyAsync(ref->c_img.p, (const float *)images + (size_t)c0 * NN, (size_t)nb * NN * sizeof(float), hipMemcpyHostToDevice, cur_stream()));
-            d_img = ref->c_img.p;
+            HIPCHK(hipMemcpyAsync(ref->spectra.img.p, (const float *)images + (size_t)c0 * NN, (size_t)nb * NN * sizeof(float), hipMemcpyHostToDevice, cur_stream()));
+            d_img = ref->spectra.img.p;
         }
-        if (int rc = launch_prep(ref->spill, d_img, ref->c_rows.p + (size_t)c0 * PPM_NCOL, nb, gm, c.rm_px, (float)(fall / gm.a), cfg->normalize, cfg->invert, 1, 1,
-                                 ref->c_band.p, mode4 ? ref->c_wring.p + (size_t)c0 * (gm.B + 2) : nullptr, ref->samples.p, S_pad, ref->c_Il.p + (size_t)c0 * S_pad,
-                                 ref->c_cw.p + (size_t)c0 * S_pad, nullptr, nullptr, nullptr)) return rc;
+        if (int rc = launch_prep(ref->spill, d_img, ref->spectra.rows.p + (size_t)c0 * PPM_NCOL, nb, gm, c.rm_px, (float)(fall / gm.a), cfg->normalize, cfg->invert, 1, 1,
+                                 ref->spectra.band.p, mode4 ? ref->spectra.wring.p + (size_t)c0 * (gm.B + 2) : nullptr, ref->samples.p, S_pad, ref->spectra.Il.p + (size_t)c0 * S_pad,
+                                 ref->spectra.cw.p + (size_t)c0 * S_pad, nullptr, nullptr, nullptr)) return rc;
         if (!images_on_device) HIPCHK(hipStreamSynchronize(cur_stream()));     // the staging buffer is reused by the next chunk
     }
     return 0;
@@ -174,14 +190,14 @@ static int csp_defocus_sweep(CspRun &c, const CspUnits &U, double *rows) {
     const double step = cc->defocus_step > 0 ? cc->defocus_step : 50.0;
     const int nt = ppm::defocus_steps(cc->defocus_range, step, PPM_MAX_DEFOCUS_STEPS);
     const int Tn = 2 * nt + 1;
-    if (int rc = ref->c_states.ensure(n_proj)) return rc;
-    if (int rc = ref->c_out.ensure((size_t)n_proj * Tn)) return rc;
-    hipLaunchKernelGGL(k_states_from_rows, dim3((n_proj + 255) / 256), dim3(256), 0, cur_stream(), ref->c_rows.p, ref->c_states.p, n_proj, gm.a, 1.0, 1.0);
-    launch_defocus(cube_view(ref), gm, ref->samples.p, c.S_pad, ref->c_Il.p, ref->c_wring.p, ref->c_rows.p, ref->c_states.p, n_proj, nt, (float)step,
-                   nullptr, ref->c_out.p, 0.f);
+    if (int rc = ref->csp.states.ensure(n_proj)) return rc;
+    if (int rc = ref->csp.out.ensure((size_t)n_proj * Tn)) return rc;
+    hipLaunchKernelGGL(k_states_from_rows, dim3((n_proj + 255) / 256), dim3(256), 0, cur_stream(), ref->spectra.rows.p, ref->csp.states.p, n_proj, gm.a, 1.0, 1.0);
+    launch_defocus(cube_view(ref), gm, ref->samples.p, c.S_pad, ref->spectra.Il.p, ref->spectra.wring.p, ref->spectra.rows.p, ref->csp.states.p, n_proj, nt, (float)step,
+                   nullptr, ref->csp.out.p, 0.f);
     HIPCHK(hipGetLastError());
     std::vector<double> sc((size_t)n_proj * Tn);
-    HIPCHK(hipMemcpyAsync(sc.data(), ref->c_out.p, sc.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipMemcpyAsync(sc.data(), ref->csp.out.p, sc.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
     HIPCHK(hipStreamSynchronize(cur_stream()));
     for (int u = 0; u < c.n_tilt; u++) {
         if (!U.refined[u]) continue;
@@ -202,54 +218,68 @@ static int csp_defocus_sweep(CspRun &c, const CspUnits &U, double *rows) {
     return 0;
 }
 
-// the units' state -> device (from U.parts / U.tls through the staging vectors of the run)
+// the units' state -> device and back (U.parts / U.tls through the staging vectors of the run); both wait for their copies
 static int csp_upload_units(CspRun &c, const CspUnits &U) {
     ppm_ref *ref = c.ref;
     for (int i = 0; i < c.n_part; i++) { std::memcpy(&c.hN[(size_t)9 * i], U.parts[i].N, 9 * sizeof(double)); std::memcpy(&c.hp[(size_t)3 * i], U.parts[i].p, 3 * sizeof(double)); }
     for (int i = 0; i < c.n_tilt; i++) std::memcpy(&c.htl[(size_t)4 * i], U.tls[i].tl, 4 * sizeof(double));
-    HIPCHK(hipMemcpyAsync(ref->c_N.p, c.hN.data(), c.hN.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
-    HIPCHK(hipMemcpyAsync(ref->c_p.p, c.hp.data(), c.hp.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
-    HIPCHK(hipMemcpyAsync(ref->c_tl.p, c.htl.data(), c.htl.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->csp.N.p, c.hN.data(), c.hN.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->csp.p.p, c.hp.data(), c.hp.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->csp.tl.p, c.htl.data(), c.htl.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
     HIPCHK(hipStreamSynchronize(cur_stream()));
+    return 0;
+}
+static int csp_download_units(CspRun &c, CspUnits &U) {
+    ppm_ref *ref = c.ref;
+    HIPCHK(hipMemcpyAsync(c.hN.data(), ref->csp.N.p, c.hN.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipMemcpyAsync(c.hp.data(), ref->csp.p.p, c.hp.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipMemcpyAsync(c.htl.data(), ref->csp.tl.p, c.htl.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipStreamSynchronize(cur_stream()));
+    for (int i = 0; i < c.n_part; i++) { std::memcpy(U.parts[i].N, &c.hN[(size_t)9 * i], 9 * sizeof(double)); std::memcpy(U.parts[i].p, &c.hp[(size_t)3 * i], 3 * sizeof(double)); }
+    for (int i = 0; i < c.n_tilt; i++) std::memcpy(U.tls[i].tl, &c.htl[(size_t)4 * i], 4 * sizeof(double));
     return 0;
 }
 
 // static tables of the search on the device, the evaluation parameters (c.EP) and the units' start state
-static int csp_upload_tables(CspRun &c, const CspUnits &U, int ncand_max) {
+static int csp_upload_tables(CspRun &c, CspUnits &U, int ncand_max) {
     ppm_ref *ref = c.ref; const Geom &gm = c.gm; const int n_proj = c.n_proj, n_part = c.n_part, n_tilt = c.n_tilt, n_slots = U.n_slots;
-    if (int rc = ref->c_rp.ensure(n_proj)) return rc;
-    if (int rc = ref->c_rt.ensure(n_proj)) return rc;
-    if (int rc = ref->c_slot.ensure(U.nu_all)) return rc;
-    if (int rc = ref->c_s0.ensure((size_t)2 * n_proj)) return rc;
-    if (int rc = ref->c_g0.ensure((size_t)2 * n_proj)) return rc;
-    if (int rc = ref->c_N.ensure((size_t)9 * n_part)) return rc;
-    if (int rc = ref->c_p.ensure((size_t)3 * n_part)) return rc;
-    if (int rc = ref->c_tl.ensure((size_t)4 * n_tilt)) return rc;
+    CspWs &w = ref->csp;
+    // Every ensure of a buffer c.EP names happens HERE, ahead of its filling below, and nowhere later in the call (out and eval are sized
+    // for the search and the final scores alike); samples, spectra.Il and spectra.cw were ensured by csp_prepare_spectra.  What later stages
+    // grow (csp.active, csp.states, csp.search.*, the compass state) is read from its DevBuf where it is used.
+    if (int rc = w.rp.ensure(n_proj)) return rc;
+    if (int rc = w.rt.ensure(n_proj)) return rc;
+    if (int rc = w.slot.ensure(U.nu_all)) return rc;
+    if (int rc = w.s0.ensure((size_t)2 * n_proj)) return rc;
+    if (int rc = w.g0.ensure((size_t)2 * n_proj)) return rc;
+    if (int rc = w.N.ensure((size_t)9 * n_part)) return rc;
+    if (int rc = w.p.ensure((size_t)3 * n_part)) return rc;
+    if (int rc = w.tl.ensure((size_t)4 * n_tilt)) return rc;
     if (ncand_max > kMaxCand) return fail(-22, "csp: too many free parameters");
-    if (int rc = ref->c_delta.ensure((size_t)std::max(n_slots, 1) * ncand_max * 6)) return rc;
-    if (int rc = ref->c_eval.ensure(std::max(U.eval_rows.size(), U.final_rows.size()))) return rc;
-    if (int rc = ref->c_out.ensure(std::max(U.eval_rows.size() * ncand_max, U.final_rows.size()))) return rc;
-    HIPCHK(hipMemcpyAsync(ref->c_rp.p, U.row_part.data(), n_proj * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
-    HIPCHK(hipMemcpyAsync(ref->c_rt.p, U.row_tilt.data(), n_proj * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
-    HIPCHK(hipMemcpyAsync(ref->c_slot.p, U.unit_slot.data(), U.nu_all * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
-    HIPCHK(hipMemcpyAsync(ref->c_s0.p, U.s0.data(), U.s0.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
-    HIPCHK(hipMemcpyAsync(ref->c_g0.p, U.g0.data(), U.g0.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    if (int rc = w.delta.ensure((size_t)std::max(n_slots, 1) * ncand_max * 6)) return rc;
+    if (int rc = w.eval.ensure(std::max(U.eval_rows.size(), U.final_rows.size()))) return rc;
+    if (int rc = w.out.ensure(std::max(U.eval_rows.size() * ncand_max, U.final_rows.size()))) return rc;
+    if (int rc = w.uoff.ensure(U.active.size() + 1)) return rc;
+    if (int rc = w.mean.ensure(std::max<size_t>(U.active.size() * ncand_max, 1))) return rc;
+    HIPCHK(hipMemcpyAsync(w.rp.p, U.row_part.data(), n_proj * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(w.rt.p, U.row_tilt.data(), n_proj * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(w.slot.p, U.unit_slot.data(), U.nu_all * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(w.s0.p, U.s0.data(), U.s0.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(w.g0.p, U.g0.data(), U.g0.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
     c.hN.resize((size_t)9 * n_part); c.hp.resize((size_t)3 * n_part); c.htl.resize((size_t)4 * n_tilt);
     CspEvalP &EP = c.EP;
     EP.cv = cube_view(ref);
-    EP.samples = ref->samples.p; EP.Il = ref->c_Il.p; EP.cw = ref->c_cw.p; EP.S_pad = c.S_pad; EP.N = gm.N; EP.nr = c.nrings;
+    EP.samples = ref->samples.p; EP.Il = ref->spectra.Il.p; EP.cw = ref->spectra.cw.p; EP.S_pad = c.S_pad; EP.N = gm.N; EP.nr = c.nrings;
     EP.tabR = cube_tab_radius(gm.B, EP.cv.scale);
     c.tab = local_tables_wanted(EP.tabR) && tables_fit_lds(ring_lds_bytes8(4, kMaxCand, c.nrings), EP.tabR);
     EP.rlo2 = (float)(gm.r_lo * gm.r_lo); EP.ring_signed = (float)std::min(gm.ring_signed, 1e30);
-    EP.kind = c.kind; EP.eval_rows = ref->c_eval.p; EP.row_part = ref->c_rp.p; EP.row_tilt = ref->c_rt.p; EP.unit_slot = ref->c_slot.p;
-    EP.Nmat = ref->c_N.p; EP.pshift = ref->c_p.p; EP.tl = ref->c_tl.p; EP.delta = ref->c_delta.p; EP.s0 = ref->c_s0.p; EP.g0 = ref->c_g0.p; EP.out = ref->c_out.p;
+    EP.kind = c.kind; EP.eval_rows = w.eval.p; EP.row_part = w.rp.p; EP.row_tilt = w.rt.p; EP.unit_slot = w.slot.p;
+    EP.Nmat = w.N.p; EP.pshift = w.p.p; EP.tl = w.tl.p; EP.delta = w.delta.p; EP.s0 = w.s0.p; EP.g0 = w.g0.p; EP.out = w.out.p;
     // evaluation list of the search (the usable rows of the active units, grouped by unit) and the units' offsets in it: uploaded once
-    std::vector<int> uoff(U.active.size() + 1, 0);
-    for (size_t a = 0; a < U.active.size(); a++) { int n = 0; for (int j : U.urows[U.active[a]]) n += U.usable[j] ? 1 : 0; uoff[a + 1] = uoff[a] + n; }
-    if (int rc = ref->c_uoff.ensure(uoff.size())) return rc;
-    if (int rc = ref->c_mean.ensure(std::max<size_t>(U.active.size() * ncand_max, 1))) return rc;
-    HIPCHK(hipMemcpyAsync(ref->c_uoff.p, uoff.data(), uoff.size() * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
-    return csp_upload_units(c, U);      // (its synchronisation also covers `uoff`)
+    U.uoff.assign(U.active.size() + 1, 0);
+    for (size_t a = 0; a < U.active.size(); a++) { int n = 0; for (int j : U.urows[U.active[a]]) n += U.usable[j] ? 1 : 0; U.uoff[a + 1] = U.uoff[a] + n; }
+    HIPCHK(hipMemcpyAsync(w.uoff.p, U.uoff.data(), U.uoff.size() * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    return csp_upload_units(c, U);
 }
 
 // one block of 256 threads per evaluation row
@@ -264,50 +294,33 @@ static void launch_csp_eval(const CspRun &c, size_t n_rows) {
 // each (candidates, unit means, trial step, its score, its means, accept) and no host wait until the units come back at the end.
 // The bands follow from the step schedule alone, so the host knows them up front.
 static int csp_compass(CspRun &c, CspUnits &U, const CspSearch &P, int ncand_max) {
-    ppm_ref *ref = c.ref; const Geom &gm = c.gm; CspEvalP &EP = c.EP; const int n_slots = U.n_slots;
-    const int na = (int)U.active.size();
-    DevBuf<double> &d_acc = ref->c_acc, &d_dtrial = ref->c_dtrial, &d_fpm = ref->c_fpm, &d_delta = ref->c_delta, &d_delta_t = ref->c_delta_t, &d_tmean = ref->c_tmean;
-    DevBuf<int> &d_active = ref->c_active;
-    if (int rc = d_acc.ensure((size_t)na * 6)) return rc;
-    if (int rc = d_dtrial.ensure((size_t)na * 6)) return rc;
-    if (int rc = d_fpm.ensure((size_t)na * 12)) return rc;
-    if (int rc = d_delta_t.ensure((size_t)std::max(n_slots, 1) * 6)) return rc;
-    if (int rc = d_tmean.ensure((size_t)na)) return rc;
-    if (int rc = d_active.ensure((size_t)na)) return rc;
-    HIPCHK(hipMemcpyAsync(d_active.p, U.active.data(), (size_t)na * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
-    HIPCHK(hipMemcpyAsync(ref->c_eval.p, U.eval_rows.data(), U.eval_rows.size() * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
-    HIPCHK(hipMemsetAsync(d_delta.p, 0, (size_t)std::max(n_slots, 1) * ncand_max * 6 * sizeof(double), cur_stream()));      // slots of units without usable rows stay zero
-    HIPCHK(hipMemsetAsync(d_delta_t.p, 0, (size_t)std::max(n_slots, 1) * 6 * sizeof(double), cur_stream()));
-    int ncand = 1;
-    for (int i = 0; i < 6; i++) ncand += P.en[i] ? 2 : 0;
-    CspStepP SP;
-    SP.kind = c.kind; SP.n_active = na; SP.ncand = ncand; SP.active = d_active.p; SP.unit_slot = ref->c_slot.p;
-    for (int i = 0; i < 6; i++) { SP.en[i] = P.en[i]; SP.tol[i] = P.tol[i]; }
-    SP.acc = d_acc.p; SP.dtrial = d_dtrial.p; SP.fpm = d_fpm.p;
-    SP.delta_c = d_delta.p; SP.delta_t = d_delta_t.p; SP.Nmat = ref->c_N.p; SP.pshift = ref->c_p.p; SP.tl = ref->c_tl.p; SP.nstride = 9; SP.pstride = 3;
-    HIPCHK(hipMemsetAsync(d_acc.p, 0, (size_t)na * 6 * sizeof(double), cur_stream()));
+    ppm_ref *ref = c.ref; const Geom &gm = c.gm; CspEvalP &EP = c.EP; CspWs &w = ref->csp;
+    const int na = (int)U.active.size(); const size_t n_slots = (size_t)std::max(U.n_slots, 1);
+    if (int rc = ref->compass.ensure(n_slots)) return rc;       // delta_t has a row per slot, the rest per active unit: slots >= active units
+    if (int rc = w.active.ensure((size_t)na)) return rc;
+    HIPCHK(hipMemcpyAsync(w.active.p, U.active.data(), (size_t)na * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(w.eval.p, U.eval_rows.data(), U.eval_rows.size() * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemsetAsync(w.delta.p, 0, n_slots * ncand_max * 6 * sizeof(double), cur_stream()));      // slots of units without usable rows stay zero
+    HIPCHK(hipMemsetAsync(ref->compass.delta_t.p, 0, n_slots * 6 * sizeof(double), cur_stream()));
+    HIPCHK(hipMemsetAsync(ref->compass.acc.p, 0, (size_t)na * 6 * sizeof(double), cur_stream()));
+    CompassPoses at;
+    at.kind = c.kind; at.n_active = na; at.Nmat = w.N.p; at.nstride = 9; at.pshift = w.p.p; at.pstride = 3; at.tl = w.tl.p;
+    at.active = w.active.p; at.unit_slot = w.slot.p; at.delta = w.delta.p; at.mean = w.mean.p;
     int nrot_c = 0;         // accounting: gathers = samples x rotations that differ (shift candidates share the centre's)
     for (int i = 0; i < 3; i++) nrot_c += P.en[i] ? 2 : 0;
     const bool any_ang = P.en[0] || P.en[1] || P.en[2], any_sh = P.en[3] || P.en[4] || P.en[5];
-    if (int rc = compass_enqueue(SP, ref->c_mean.p, d_tmean.p, P.T, P.ha0, P.hs0,
+    if (int rc = compass_enqueue(ref->compass, at, P.en, P.tol, P.T, P.ha0, P.hs0,
             [&](double ha, double hs) { return march_band(c.bf(), gm.N, c.rm_px, ha, hs, any_ang, any_sh, gm.r_hi); },
             [&](const double *delta, int nc, double rband, double *means) {
                 EP.delta = delta; EP.ncand = nc; EP.S_used = c.prefix_of(rband); EP.rmax2 = (float)(rband * rband);
                 c.acct_gathers += (double)U.eval_rows.size() * EP.S_used * (nc > 1 ? 1 + nrot_c : 1); c.acct_sweeps++;
                 launch_csp_eval(c, U.eval_rows.size());
                 const int nm = na * nc;
-                hipLaunchKernelGGL(k_csp_unit_means, dim3((nm + 255) / 256), dim3(256), 0, cur_stream(), ref->c_out.p, ref->c_uoff.p, na, nc, means);
+                hipLaunchKernelGGL(k_csp_unit_means, dim3((nm + 255) / 256), dim3(256), 0, cur_stream(), w.out.p, w.uoff.p, na, nc, means);
                 return 0;
             })) return rc;
-    // the units as the search left them
-    HIPCHK(hipMemcpyAsync(c.hN.data(), ref->c_N.p, c.hN.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
-    HIPCHK(hipMemcpyAsync(c.hp.data(), ref->c_p.p, c.hp.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
-    HIPCHK(hipMemcpyAsync(c.htl.data(), ref->c_tl.p, c.htl.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
-    HIPCHK(hipStreamSynchronize(cur_stream()));
-    for (int i = 0; i < c.n_part; i++) { std::memcpy(U.parts[i].N, &c.hN[(size_t)9 * i], 9 * sizeof(double)); std::memcpy(U.parts[i].p, &c.hp[(size_t)3 * i], 3 * sizeof(double)); }
-    for (int i = 0; i < c.n_tilt; i++) std::memcpy(U.tls[i].tl, &c.htl[(size_t)4 * i], 4 * sizeof(double));
-    EP.delta = d_delta.p;
-    return 0;
+    EP.delta = w.delta.p;
+    return csp_download_units(c, U);        // the units as the search left them
 }
 
 // ---- exhaustive particle search (ppm_csp_cfg.search_points; the plan: ppm_csp_search.h)
@@ -320,7 +333,8 @@ static int csp_global_rank(CspRun &c, const CspUnits &U, const ppm_csp_search_in
     ppm_ref *ref = c.ref; const Geom &gm = c.gm;
     const int na = (int)U.active.size(), K = G.n_candidates;
     const size_t n_eval = U.eval_rows.size();
-    std::vector<double> rowtab(n_eval * kCspRowTab);
+    std::vector<double> &rowtab = c.rowtab;
+    rowtab.resize(n_eval * kCspRowTab);
     for (size_t e = 0; e < n_eval; e++) {
         const int j = U.eval_rows[e], it = U.row_tilt[j];
         const TiltRot &r = U.trot[it]; const CUnit &tu = U.tls[it];
@@ -329,25 +343,25 @@ static int csp_global_rank(CspRun &c, const CspUnits &U, const ppm_csp_search_in
         std::memcpy(t + 9, A, 6 * sizeof(double));
         t[15] = U.s0[2 * j] - U.g0[2 * j] + tu.tl[2]; t[16] = U.s0[2 * j + 1] - U.g0[2 * j + 1] + tu.tl[3];
     }
-    if (int rc = ref->c_rowtab.ensure(rowtab.size())) return rc;
-    if (int rc = ref->c_active.ensure((size_t)na)) return rc;
-    HIPCHK(hipMemcpyAsync(ref->c_rowtab.p, rowtab.data(), rowtab.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
-    HIPCHK(hipMemcpyAsync(ref->c_active.p, U.active.data(), (size_t)na * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
-    HIPCHK(hipMemcpyAsync(ref->c_eval.p, U.eval_rows.data(), n_eval * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    if (int rc = ref->csp.search.rowtab.ensure(rowtab.size())) return rc;
+    if (int rc = ref->csp.active.ensure((size_t)na)) return rc;
+    HIPCHK(hipMemcpyAsync(ref->csp.search.rowtab.p, rowtab.data(), rowtab.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->csp.active.p, U.active.data(), (size_t)na * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->csp.eval.p, U.eval_rows.data(), n_eval * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
     const size_t n_rot = (size_t)G.n_rot;
     const int chunk = (int)std::min<size_t>(std::min<size_t>((size_t)na, 65535), std::max<size_t>(1, kCspSearchTableBytes / (n_rot * 8)));
-    if (int rc = ref->c_gbest.ensure((size_t)chunk * n_rot)) return rc;
-    if (int rc = ref->c_gshift.ensure((size_t)chunk * n_rot)) return rc;
-    if (int rc = ref->c_crot.ensure((size_t)na * K)) return rc;
-    if (int rc = ref->c_cshift.ensure((size_t)na * K)) return rc;
-    if (int rc = ref->c_cscore.ensure((size_t)na * K)) return rc;
+    if (int rc = ref->csp.search.gbest.ensure((size_t)chunk * n_rot)) return rc;
+    if (int rc = ref->csp.search.gshift.ensure((size_t)chunk * n_rot)) return rc;
+    if (int rc = ref->csp.search.crot.ensure((size_t)na * K)) return rc;
+    if (int rc = ref->csp.search.cshift.ensure((size_t)na * K)) return rc;
+    if (int rc = ref->csp.search.cscore.ensure((size_t)na * K)) return rc;
     long cap = kCspSearchRotsPerLaunch;
     if (const char *e = std::getenv("PPM_CSP_SEARCH_ROTS")) { long v = std::atol(e); if (v > 0) cap = std::min(cap, v); }   // tests: force several launches
     CspGlobalP GP;
-    GP.cv = c.EP.cv; GP.samples = ref->samples.p; GP.Il = ref->c_Il.p; GP.cw = ref->c_cw.p; GP.S_pad = c.S_pad; GP.N = gm.N;
+    GP.cv = c.EP.cv; GP.samples = ref->samples.p; GP.Il = ref->spectra.Il.p; GP.cw = ref->spectra.cw.p; GP.S_pad = c.S_pad; GP.N = gm.N;
     GP.rlo2 = c.EP.rlo2; GP.ring_signed = c.EP.ring_signed; GP.S_used = c.prefix_of(G.r_g); GP.rmax2 = (float)(G.r_g * G.r_g);
-    GP.eval_rows = ref->c_eval.p; GP.uoff = ref->c_uoff.p; GP.active = ref->c_active.p; GP.Nmat = ref->c_N.p; GP.pshift = ref->c_p.p;
-    GP.rowtab = ref->c_rowtab.p; GP.G = G; GP.best = ref->c_gbest.p; GP.best_shift = ref->c_gshift.p;
+    GP.eval_rows = ref->csp.eval.p; GP.uoff = ref->csp.uoff.p; GP.active = ref->csp.active.p; GP.Nmat = ref->csp.N.p; GP.pshift = ref->csp.p.p;
+    GP.rowtab = ref->csp.search.rowtab.p; GP.G = G; GP.best = ref->csp.search.gbest.p; GP.best_shift = ref->csp.search.gshift.p;
     GP.edge_ring = (int)std::floor(G.r_g); GP.max_rows = 1;
     for (int u : U.active) { int n = 0; for (int j : U.urows[u]) n += U.usable[j] ? 1 : 0; GP.max_rows = std::max(GP.max_rows, n); }
     const size_t lds = csp_global_lds_bytes(GP.S_used, GP.max_rows);
@@ -361,17 +375,17 @@ static int csp_global_rank(CspRun &c, const CspUnits &U, const ppm_csp_search_in
             ProfScope ps(PPM_K_GLOBAL);
             hipLaunchKernelGGL(k_csp_global, dim3((unsigned)((GP.nrot + GP.rc - 1) / GP.rc), (unsigned)npc), dim3(64), lds, cur_stream(), GP);
         }
-        hipLaunchKernelGGL(k_csp_global_topk, dim3((unsigned)npc), dim3(256), 0, cur_stream(), ref->c_gbest.p, ref->c_gshift.p, (long)G.n_rot, K,
-                           ref->c_crot.p + (size_t)a0 * K, ref->c_cshift.p + (size_t)a0 * K, ref->c_cscore.p + (size_t)a0 * K);
+        hipLaunchKernelGGL(k_csp_global_topk, dim3((unsigned)npc), dim3(256), 0, cur_stream(), ref->csp.search.gbest.p, ref->csp.search.gshift.p, (long)G.n_rot, K,
+                           ref->csp.search.crot.p + (size_t)a0 * K, ref->csp.search.cshift.p + (size_t)a0 * K, ref->csp.search.cscore.p + (size_t)a0 * K);
         HIPCHK(hipGetLastError());
     }
     const long passes = (G.n_shift + 64 * kCspGlobalShifts - 1) / (64 * kCspGlobalShifts);
     c.acct_gathers += (double)n_eval * (double)G.n_rot * GP.S_used * (double)passes;
-    ref->cand_K = K;
-    ref->cand_unit.resize(na); ref->cand_rot.resize((size_t)na * K); ref->cand_shift.resize((size_t)na * K); ref->cand_score.resize((size_t)na * K);
-    HIPCHK(hipMemcpyAsync(ref->cand_rot.data(), ref->c_crot.p, (size_t)na * K * sizeof(long), hipMemcpyDeviceToHost, cur_stream()));
-    HIPCHK(hipMemcpyAsync(ref->cand_shift.data(), ref->c_cshift.p, (size_t)na * K * sizeof(int), hipMemcpyDeviceToHost, cur_stream()));
-    HIPCHK(hipMemcpyAsync(ref->cand_score.data(), ref->c_cscore.p, (size_t)na * K * sizeof(float), hipMemcpyDeviceToHost, cur_stream()));
+    ref->csp.search.cand_K = K;
+    ref->csp.search.cand_unit.resize(na); ref->csp.search.cand_rot.resize((size_t)na * K); ref->csp.search.cand_shift.resize((size_t)na * K); ref->csp.search.cand_score.resize((size_t)na * K);
+    HIPCHK(hipMemcpyAsync(ref->csp.search.cand_rot.data(), ref->csp.search.crot.p, (size_t)na * K * sizeof(long), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->csp.search.cand_shift.data(), ref->csp.search.cshift.p, (size_t)na * K * sizeof(int), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->csp.search.cand_score.data(), ref->csp.search.cscore.p, (size_t)na * K * sizeof(float), hipMemcpyDeviceToHost, cur_stream()));
     HIPCHK(hipStreamSynchronize(cur_stream()));
     return 0;
 }
@@ -379,15 +393,15 @@ static int csp_global_rank(CspRun &c, const CspUnits &U, const ppm_csp_search_in
 // mean score of every active unit at its current state on the band `rband` (zero displacement) -> hmean[active unit]
 static int csp_unit_scores(CspRun &c, const CspUnits &U, int ncand_max, double rband, std::vector<double> &hmean) {
     ppm_ref *ref = c.ref; CspEvalP &EP = c.EP; const int na = (int)U.active.size();
-    HIPCHK(hipMemsetAsync(ref->c_delta.p, 0, (size_t)std::max(U.n_slots, 1) * ncand_max * 6 * sizeof(double), cur_stream()));
-    HIPCHK(hipMemcpyAsync(ref->c_eval.p, U.eval_rows.data(), U.eval_rows.size() * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
-    EP.delta = ref->c_delta.p; EP.ncand = 1; EP.S_used = c.prefix_of(rband); EP.rmax2 = (float)(rband * rband);
+    HIPCHK(hipMemsetAsync(ref->csp.delta.p, 0, (size_t)std::max(U.n_slots, 1) * ncand_max * 6 * sizeof(double), cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->csp.eval.p, U.eval_rows.data(), U.eval_rows.size() * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    EP.delta = ref->csp.delta.p; EP.ncand = 1; EP.S_used = c.prefix_of(rband); EP.rmax2 = (float)(rband * rband);
     c.acct_gathers += (double)U.eval_rows.size() * EP.S_used; c.acct_sweeps++;
     launch_csp_eval(c, U.eval_rows.size());
-    hipLaunchKernelGGL(k_csp_unit_means, dim3((na + 255) / 256), dim3(256), 0, cur_stream(), ref->c_out.p, ref->c_uoff.p, na, 1, ref->c_mean.p);
+    hipLaunchKernelGGL(k_csp_unit_means, dim3((na + 255) / 256), dim3(256), 0, cur_stream(), ref->csp.out.p, ref->csp.uoff.p, na, 1, ref->csp.mean.p);
     HIPCHK(hipGetLastError());
     hmean.resize(na);
-    HIPCHK(hipMemcpyAsync(hmean.data(), ref->c_mean.p, (size_t)na * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipMemcpyAsync(hmean.data(), ref->csp.mean.p, (size_t)na * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
     HIPCHK(hipStreamSynchronize(cur_stream()));
     return 0;
 }
@@ -401,7 +415,7 @@ static int csp_exhaustive(CspRun &c, CspUnits &U, const CspSearch &P, const ppm_
     if (int rc = csp_global_rank(c, U, G)) return rc;
     ppm_ref *ref = c.ref;
     const int na = (int)U.active.size(), K = G.n_candidates;
-    for (int a = 0; a < na; a++) ref->cand_unit[a] = (long)c.particles_in[(size_t)U.active[a] * PPM_NPCOL];
+    for (int a = 0; a < na; a++) ref->csp.search.cand_unit[a] = (long)c.particles_in[(size_t)U.active[a] * PPM_NPCOL];
     const double hs_grid = G.shift_grid ? G.h_s : cc->tol_shift;
     const bool any_ang = P.en[0] || P.en[1] || P.en[2], any_sh = P.en[3] || P.en[4] || P.en[5];
     CspSearch P2 = P;
@@ -413,8 +427,8 @@ static int csp_exhaustive(CspRun &c, CspUnits &U, const CspSearch &P, const ppm_
     for (int k = 0; k < K; k++) {
         for (int a = 0; a < na; a++) {
             CUnit q = start[U.active[a]];
-            const long rot = ref->cand_rot[(size_t)a * K + k];
-            if (rot >= 0) { double d[6]; csp_search_delta(G, rot, ref->cand_shift[(size_t)a * K + k], d); unit_apply_delta(q.N, q.p, d); }
+            const long rot = ref->csp.search.cand_rot[(size_t)a * K + k];
+            if (rot >= 0) { double d[6]; csp_search_delta(G, rot, ref->csp.search.cand_shift[(size_t)a * K + k], d); unit_apply_delta(q.N, q.p, d); }
             U.parts[U.active[a]] = q;
         }
         if (int rc = csp_upload_units(c, U)) return rc;
@@ -435,14 +449,14 @@ static int csp_exhaustive(CspRun &c, CspUnits &U, const CspSearch &P, const ppm_
 // scores of every row of the refined units at the full band, at the units' current state (zero displacement) -> hout[final row]
 static int csp_final_scores(CspRun &c, const CspUnits &U, std::vector<double> &hout) {
     ppm_ref *ref = c.ref; const Geom &gm = c.gm; CspEvalP &EP = c.EP;
-    HIPCHK(hipMemsetAsync(ref->c_delta.p, 0, (size_t)U.n_slots * 6 * sizeof(double), cur_stream()));
-    HIPCHK(hipMemcpyAsync(ref->c_eval.p, U.final_rows.data(), U.final_rows.size() * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemsetAsync(ref->csp.delta.p, 0, (size_t)U.n_slots * 6 * sizeof(double), cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->csp.eval.p, U.final_rows.data(), U.final_rows.size() * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
     EP.ncand = 1; EP.S_used = c.prefix_of(gm.r_hi); EP.rmax2 = (float)(gm.r_hi * gm.r_hi);
     c.acct_gathers += (double)U.final_rows.size() * EP.S_used; c.acct_sweeps++;
     launch_csp_eval(c, U.final_rows.size());
     HIPCHK(hipGetLastError());
     hout.resize(U.final_rows.size());
-    HIPCHK(hipMemcpyAsync(hout.data(), ref->c_out.p, hout.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipMemcpyAsync(hout.data(), ref->csp.out.p, hout.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
     HIPCHK(hipStreamSynchronize(cur_stream()));
     return 0;
 }
@@ -487,7 +501,7 @@ extern "C" int ppm_csp_refine(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const p
     if (cc->search_points < 0 || cc->search_candidates < 0) return fail(-22, "csp: search_points and search_candidates must not be negative");
     if (n_proj <= 0) return 0;
     if (n_part <= 0 || n_tilt <= 0) return fail(-22, "csp: the extended parameters hold no particles or no tilts");
-    ref->cand_K = 0; ref->cand_unit.clear();       // ppm_csp_search_candidates answers from the last call
+    ref->csp.search.cand_K = 0; ref->csp.search.cand_unit.clear();       // ppm_csp_search_candidates answers from the last call
     CspRun c; c.particles_in = particles; c.ref = ref; c.cfg = cfg; c.cc = cc; c.kind = cc->unit; c.n_proj = n_proj; c.n_part = n_part; c.n_tilt = n_tilt;
     const Geom &gm = c.gm;
     ppm_refine_cfg c2 = *cfg; c2.global_search = 0;
@@ -501,13 +515,15 @@ extern "C" int ppm_csp_refine(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const p
     c.S_pad = (int)c.sl.packed.size(); c.nrings = gm.B + 2;
     const bool mode4 = cc->refine_defocus != 0;
     if (mode4 && c.kind != PPM_CSP_MICROGRAPHS) return fail(-22, "csp: defocus refinement works on tilts (unit = micrographs)");
+    CspUnits U; std::vector<double> hout;
+    DrainOnError drain;             // below c, U and hout: what the asynchronous copies of this call read and write outlives the drain
+    drain.armed = true;
     if (int rc = csp_prepare_spectra(c, images, images_on_device, rows, mode4)) return rc;
-    CspUnits U;
     if (int rc = csp_build_units(c, rows, particles, tilts, U)) return rc;
-    if (U.final_rows.empty()) return 0;
+    if (U.final_rows.empty()) return 0;         // (still armed: the copy of the caller's rows may be in flight)
     const CspSearch P = csp_search_plan(cc, c.kind, !U.active.empty());
     trace_.mark("host tables");
-    if (mode4) return csp_defocus_sweep(c, U, rows);
+    if (mode4) { if (int rc = csp_defocus_sweep(c, U, rows)) return rc; return drain.ok(); }
     const int ncand_max = 1 + 2 * P.nfree;
     if (int rc = csp_upload_tables(c, U, ncand_max)) return rc;
     trace_.mark("spectra prepared, units uploaded");
@@ -528,7 +544,6 @@ extern "C" int ppm_csp_refine(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const p
     if (G.active) { if (int rc = csp_exhaustive(c, U, P, G, ncand_max)) return rc; }
     else if (P.T > 0) if (int rc = csp_compass(c, U, P, ncand_max)) return rc;
     trace_.mark("searched");
-    std::vector<double> hout;
     if (int rc = csp_final_scores(c, U, hout)) return rc;
     trace_.mark("final scores");
     csp_write_back(c, U, hout, rows, particles, tilts);
@@ -536,7 +551,7 @@ extern "C" int ppm_csp_refine(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const p
     // samples per projection summed over the sweeps
     ref->last_counts[0] = G.active ? G.n_rot * G.n_shift : 0; ref->last_counts[1] = c.acct_sweeps; ref->last_counts[2] = (long)std::floor(kPi * gm.r_hi * gm.r_hi / 2);
     ref->last_counts[3] = (long)(c.acct_gathers / std::max(n_proj, 1));
-    return 0;
+    return drain.ok();
 }
 
 extern "C" int ppm_csp_search_plan(const ppm_refine_cfg *cfg, const ppm_csp_cfg *cc, ppm_csp_search_info *out) {
@@ -551,14 +566,14 @@ extern "C" int ppm_csp_search_plan(const ppm_refine_cfg *cfg, const ppm_csp_cfg 
 
 extern "C" int ppm_csp_search_candidates(ppm_ref_t *ref, long unit, int max_k, long *rot_index, long *shift_index, double *score) {
     if (!ref || max_k < 0 || (max_k > 0 && (!rot_index || !shift_index || !score))) return fail(-22, "null argument");
-    for (size_t a = 0; a < ref->cand_unit.size(); a++) {
-        if (ref->cand_unit[a] != unit) continue;
-        const int K = std::min(max_k, ref->cand_K);
+    for (size_t a = 0; a < ref->csp.search.cand_unit.size(); a++) {
+        if (ref->csp.search.cand_unit[a] != unit) continue;
+        const int K = std::min(max_k, ref->csp.search.cand_K);
         int n = 0;
         for (int k = 0; k < K; k++) {
-            const size_t o = a * ref->cand_K + k;
-            if (ref->cand_rot[o] < 0) break;
-            rot_index[n] = ref->cand_rot[o]; shift_index[n] = ref->cand_shift[o]; score[n] = 100.0 * (double)ref->cand_score[o]; n++;
+            const size_t o = a * ref->csp.search.cand_K + k;
+            if (ref->csp.search.cand_rot[o] < 0) break;
+            rot_index[n] = ref->csp.search.cand_rot[o]; shift_index[n] = ref->csp.search.cand_shift[o]; score[n] = 100.0 * (double)ref->csp.search.cand_score[o]; n++;
         }
         return n;
     }

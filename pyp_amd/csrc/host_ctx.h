@@ -190,6 +190,53 @@ struct DevTmp {
 // which the first such call allocates (ensure_lane, host_refine.h).
 struct Lane { DevBuf<double> rows_in, rows_out; DevBuf<float> wring, cw, ddef; DevBuf<float2> Il; DevBuf<Hit> hits; DevBuf<LState> states, states2; };
 
+// Workspaces of the searches without a grid search, by owner (DevBufs: grown on demand, reused across calls, freed with the handle).  An
+// ensure may move a pointer: kernel parameters take `.p` after the last ensure of the buffers they name (see where CspEvalP / SvaEvalP are filled).
+// Prepared spectra of a tilt series.  Grown and filled by csp_prepare_spectra only; read by csp, csp mode 4 and the frame refinement.
+struct SpectraWs { DevBuf<float2> Il, band; DevBuf<float> cw, img, wring; DevBuf<double> rows; };
+// State of the device-resident compass search (k_csp_step_*), one row per state.  Grown by ensure() only: csp_compass calls it per
+// search, ppm_sva_align once per call for a chunk's states (allocating and freeing these per call cost 7 ms of a 57 ms alignment).
+struct CompassWs {
+    DevBuf<double> acc, dtrial, fpm, delta_t, tmean;
+    int ensure(size_t n_states) {
+        if (int rc = acc.ensure(n_states * 6)) return rc;
+        if (int rc = dtrial.ensure(n_states * 6)) return rc;
+        if (int rc = fpm.ensure(n_states * 12)) return rc;
+        if (int rc = delta_t.ensure(n_states * 6)) return rc;
+        return tmean.ensure(n_states);
+    }
+};
+// The constrained search proper.  Grown by csp_upload_tables (the unit tables, delta, eval, out, uoff, mean), csp_compass and
+// csp_global_rank (active), csp_defocus_sweep (states, out).
+struct CspWs {
+    DevBuf<double> N, p, tl, delta, s0, g0, out, mean; DevBuf<int> eval, rp, rt, slot, uoff, active; DevBuf<LState> states;
+    // its exhaustive stage (k_csp_global), grown by csp_global_rank: per-row tables, per-rotation maxima of a particle chunk, the kept
+    // candidates; and what ppm_csp_search_candidates answers from (the last call's candidates: PIND of every searched particle, K entries each)
+    struct Search {
+        DevBuf<double> rowtab; DevBuf<float> gbest, cscore; DevBuf<int> gshift, cshift; DevBuf<long> crot;
+        std::vector<long> cand_unit, cand_rot; std::vector<int> cand_shift; std::vector<float> cand_score; int cand_K = 0;
+    } search;
+};
+// Movie-frame refinement, grown by ppm_frame_refine only: the frame tables, the own and pooled maps, the slice store of a band too wide for LDS.
+struct FrameWs { DevBuf<int> ints; DevBuf<float> flts, own, pool; DevBuf<double> dbls; DevBuf<float2> store; };
+// Sub-volume transforms: the two work arrays (grown by sva_bind_work), staged host volumes and, in a reference, the band-limited transforms
+// of a chunk (grown by ppm_sva_align / ppm_sva_insert).  GBs: allocating and freeing them on every call cost ~20 ms of a 120 ms call.
+struct SvaWork { DevBuf<float2> f, g, F; DevBuf<float> vols; };
+// The alignment's band: the sample list (built and sorted on the host: ~25 ms at 192^3 / 452 k samples) is kept while the band-pass settings
+// stay, the window's transform at the samples (Fw) while the window stays; keys compare bit for bit.  Grown by sva_band_plan and sva_transform_chunk.
+struct SvaBandKey {
+    float box = 0, highpass_cutoff = 0, highpass_decay = 0, lowpass_cutoff = 0, lowpass_decay = 0;
+    bool operator==(const SvaBandKey &o) const { return std::memcmp(this, &o, sizeof(o)) == 0; }
+};
+struct SvaWindowKey {
+    float w[3] = { 0, 0, 0 }, sigma = 0;
+    bool operator==(const SvaWindowKey &o) const { return std::memcmp(this, &o, sizeof(o)) == 0; }
+};
+struct SvaBandPlan {
+    bool valid = false, fw_valid = false; SvaBandKey key; SvaWindowKey wkey;
+    int S = 0; std::vector<int> shell_off; DevBuf<uint32_t> samples, pos; DevBuf<float> bandw; DevBuf<float2> Fw;
+};
+
 struct ppm_ref {
     hipStream_t stream = nullptr, copy = nullptr;       // this handle's compute and copy streams (StreamScope)
     hipStream_t local = nullptr;                        // second compute stream: the local stage of chunk i beside the search of chunk i + 1 (made on first use)
@@ -199,20 +246,8 @@ struct ppm_ref {
     Lane lane[2];
     DevBuf<double> dir_theta, dir_phi;
     DevBuf<float> images, C2, nP, nI, cc, mats;
-    // constrained search (ppm_csp_refine)
-    DevBuf<float2> c_Il, c_band; DevBuf<float> c_cw, c_img, c_wring; DevBuf<double> c_rows, c_N, c_p, c_tl, c_delta, c_s0, c_g0, c_out;
-    DevBuf<int> c_eval, c_rp, c_rt, c_slot, c_uoff, c_active; DevBuf<LState> c_states; DevBuf<double> c_mean, c_tmean, c_acc, c_dtrial, c_fpm, c_delta_t;
-    // ... its exhaustive stage (k_csp_global): per-row tables, per-rotation maxima of a particle chunk, the kept candidates; and what
-    // ppm_csp_search_candidates answers from (the last call's candidates: PIND of every searched particle, K entries each)
-    DevBuf<double> c_rowtab; DevBuf<float> c_gbest, c_cscore; DevBuf<int> c_gshift, c_cshift; DevBuf<long> c_crot;
-    std::vector<long> cand_unit, cand_rot; std::vector<int> cand_shift; std::vector<float> cand_score; int cand_K = 0;
-    // movie-frame refinement (ppm_frame_refine): the frame tables, the own and pooled maps, the slice store of a band too wide for LDS
-    DevBuf<int> f_int; DevBuf<float> f_flt, f_own, f_pool; DevBuf<double> f_dbl; DevBuf<float2> f_store;
-    // sub-tomogram alignment (ppm_sva_align): the transforms' work array, the band-limited transforms of a chunk, staged host volumes
-    // (GBs: allocating and freeing them on every call cost ~20 ms of a 120 ms call)
-    DevBuf<float2> s_f, s_g, s_F; DevBuf<float> s_vols;
-    // the band's sample list (built and sorted on the host: ~25 ms at 192^3 / 452 k samples) is kept while the band-pass settings stay
-    struct { bool valid = false; float key[5] = { 0, 0, 0, 0, 0 }; int S = 0; std::vector<int> shell_off; DevBuf<uint32_t> samples, pos; DevBuf<float> bandw; DevBuf<float2> Fw; bool fw_valid = false; float wkey[4] = { 0, 0, 0, 0 }; } s_plan;    // Fw: the window's transform at the samples
+    SpectraWs spectra; CompassWs compass; CspWs csp; FrameWs frames;    // ppm_csp_refine, ppm_frame_refine (and the compass state of ppm_sva_align)
+    SvaWork sva; SvaBandPlan sva_band;                                  // ppm_sva_align
     DevBuf<float2> band, Wp, bank, twN;
     DevBuf<float2> spill;            // k_prep outside the scratch-free path: the half spectrum between the row and the column phase, [n][N][W]
     DevBuf<float4> rowtw;            // k_global's row-pair twiddles for this reference's current search grid
@@ -241,7 +276,7 @@ struct ppm_accum {
     unsigned *d_max = nullptr;       // chunk maxima for the fixed-point scales of k_insert_bricks
     long counts[2] = { 0, 0 };
     DevBuf<double> rows; DevBuf<float> images, dose; DevBuf<float2> band, spill; DevBuf<PartIns> pp; DevBuf<CullEnt> cull; DevBuf<BrickItem> items;
-    DevBuf<float2> s_f, s_g; DevBuf<float> s_vols;      // ppm_sva_insert: the transforms' work arrays and staged host volumes
+    SvaWork sva;                     // ppm_sva_insert: the transforms' work arrays and staged host volumes
     std::vector<float> brick_load; float load_r = -1.f; int n_items = 0, items_cap = -1;
 };
 
@@ -285,6 +320,15 @@ struct ChunkStager {
         HIPCHK(hipStreamSynchronize(cur_copy()));
         return 0;
     }
+};
+
+// Error returns after a call's first enqueue drain the stream: pageable host memory that asynchronous copies still read or write (the
+// run's own vectors, the caller's rows) must not go out of scope under them.  Declared BELOW every such host buffer, so that it is
+// destroyed first; armed where the first enqueue happens; a success return goes through ok() and waits for nothing.
+struct DrainOnError {
+    bool armed = false;
+    int ok() { armed = false; return 0; }
+    ~DrainOnError() { if (armed) (void)hipStreamSynchronize(cur_stream()); }
 };
 
 static __global__ void k_noop() {}

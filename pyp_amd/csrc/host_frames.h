@@ -124,53 +124,57 @@ extern "C" int ppm_frame_refine(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const
     c.rm_px = cfg->mask_radius / gm.a;
     build_samples(gm, c.sl);
     c.S_pad = (int)c.sl.packed.size(); c.nrings = gm.B + 2;
+    // host tables and results: declared ahead of the guard, so that they outlive the drain of an error return
+    std::vector<int> ti; std::vector<float> tf, h_own, h_pool, h_score; std::vector<double> gw, h_delta;
+    DrainOnError drain;
+    drain.armed = true;
     if (int rc = csp_prepare_spectra(c, images, images_on_device, rows, false)) return rc;
     trace_.mark("spectra prepared");
     const int S_used = c.prefix_of(gm.r_hi);
     if (S_used <= 0 || (S_used & 15)) return fail(-22, "frame refinement: the band holds no samples");
-    // tables: ints [goff | frow | fproc | fnew | ffind], floats [fm6 | fsh], the pooling weights
+    // tables: ints [goff | frow | fproc | fnew | ffind], floats [fm6 | fsh], the pooling weights.  The ensures below are the call's only
+    // ones on the frame workspace and come before MP and PP are filled; the spectra were ensured by csp_prepare_spectra.
     const int hw = fc->half_width;
     int span = 0;
     for (int gi = 0; gi < ng; gi++) span = std::max(span, L.ffind[L.goff[gi + 1] - 1] - L.ffind[L.goff[gi]]);
     const int n_gw = std::min(hw, span) + 1;
-    std::vector<double> gw(n_gw, 1.0);
+    gw.assign(n_gw, 1.0);
     for (int d = 1; d < n_gw; d++) gw[d] = std::exp(-((double)d * d) / (2.0 * (0.5 * hw) * (0.5 * hw)));
-    std::vector<int> ti; ti.reserve(ng + 1 + 4 * (size_t)nf);
+    ti.reserve(ng + 1 + 4 * (size_t)nf);
     ti.insert(ti.end(), L.goff.begin(), L.goff.end()); ti.insert(ti.end(), L.frow.begin(), L.frow.end());
     ti.insert(ti.end(), L.fproc.begin(), L.fproc.end()); ti.insert(ti.end(), L.fnew.begin(), L.fnew.end()); ti.insert(ti.end(), L.ffind.begin(), L.ffind.end());
-    std::vector<float> tf; tf.reserve(8 * (size_t)nf);
+    tf.reserve(8 * (size_t)nf);
     tf.insert(tf.end(), L.fm6.begin(), L.fm6.end()); tf.insert(tf.end(), L.fsh.begin(), L.fsh.end());
     const bool in_lds = frame_store_in_lds(S_used);
-    if (int rc = ref->f_int.ensure(ti.size() + (size_t)nf)) return rc;            // + amax
-    if (int rc = ref->f_flt.ensure(tf.size() + 2 * (size_t)nf)) return rc;        // + score
-    if (int rc = ref->f_dbl.ensure((size_t)n_gw + 2 * (size_t)nf)) return rc;     // + delta
-    if (int rc = ref->f_own.ensure((size_t)nf * npts)) return rc;
-    if (int rc = ref->f_pool.ensure((size_t)nf * npts)) return rc;
-    if (!in_lds) if (int rc = ref->f_store.ensure((size_t)ng * S_used)) return rc;
-    HIPCHK(hipMemcpyAsync(ref->f_int.p, ti.data(), ti.size() * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
-    HIPCHK(hipMemcpyAsync(ref->f_flt.p, tf.data(), tf.size() * sizeof(float), hipMemcpyHostToDevice, cur_stream()));
-    HIPCHK(hipMemcpyAsync(ref->f_dbl.p, gw.data(), gw.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    if (int rc = ref->frames.ints.ensure(ti.size() + (size_t)nf)) return rc;            // + amax
+    if (int rc = ref->frames.flts.ensure(tf.size() + 2 * (size_t)nf)) return rc;        // + score
+    if (int rc = ref->frames.dbls.ensure((size_t)n_gw + 2 * (size_t)nf)) return rc;     // + delta
+    if (int rc = ref->frames.own.ensure((size_t)nf * npts)) return rc;
+    if (int rc = ref->frames.pool.ensure((size_t)nf * npts)) return rc;
+    if (!in_lds) if (int rc = ref->frames.store.ensure((size_t)ng * S_used)) return rc;
+    HIPCHK(hipMemcpyAsync(ref->frames.ints.p, ti.data(), ti.size() * sizeof(int), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->frames.flts.p, tf.data(), tf.size() * sizeof(float), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(ref->frames.dbls.p, gw.data(), gw.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
     FrameMapP MP;
-    MP.cv = cube_view(ref); MP.samples = ref->samples.p; MP.Il = ref->c_Il.p; MP.cw = ref->c_cw.p; MP.S_pad = c.S_pad; MP.N = gm.N; MP.S_used = S_used;
+    MP.cv = cube_view(ref); MP.samples = ref->samples.p; MP.Il = ref->spectra.Il.p; MP.cw = ref->spectra.cw.p; MP.S_pad = c.S_pad; MP.N = gm.N; MP.S_used = S_used;
     MP.rlo2 = (float)(gm.r_lo * gm.r_lo); MP.rmax2 = (float)(gm.r_hi * gm.r_hi); MP.W = W; MP.h = h;
-    MP.goff = ref->f_int.p; MP.frow = MP.goff + (ng + 1); MP.fproc = MP.frow + nf; MP.fnew = MP.fproc + nf;
-    const int *d_ffind = MP.fnew + nf; int *d_amax = ref->f_int.p + ti.size();
-    MP.fm6 = ref->f_flt.p; MP.fsh = MP.fm6 + 6 * (size_t)nf;
-    float *d_score = ref->f_flt.p + tf.size();
-    MP.scratch = in_lds ? nullptr : ref->f_store.p; MP.own = ref->f_own.p;
+    MP.goff = ref->frames.ints.p; MP.frow = MP.goff + (ng + 1); MP.fproc = MP.frow + nf; MP.fnew = MP.fproc + nf;
+    const int *d_ffind = MP.fnew + nf; int *d_amax = ref->frames.ints.p + ti.size();
+    MP.fm6 = ref->frames.flts.p; MP.fsh = MP.fm6 + 6 * (size_t)nf;
+    float *d_score = ref->frames.flts.p + tf.size();
+    MP.scratch = in_lds ? nullptr : ref->frames.store.p; MP.own = ref->frames.own.p;
     FramePeakP PP;
-    PP.W = W; PP.h = h; PP.half_width = hw; PP.goff = MP.goff; PP.ffind = d_ffind; PP.gw = ref->f_dbl.p; PP.n_gw = n_gw;
-    PP.own = ref->f_own.p; PP.pooled = ref->f_pool.p; PP.amax = d_amax; PP.delta = ref->f_dbl.p + n_gw; PP.score = d_score;
+    PP.W = W; PP.h = h; PP.half_width = hw; PP.goff = MP.goff; PP.ffind = d_ffind; PP.gw = ref->frames.dbls.p; PP.n_gw = n_gw;
+    PP.own = ref->frames.own.p; PP.pooled = ref->frames.pool.p; PP.amax = d_amax; PP.delta = ref->frames.dbls.p + n_gw; PP.score = d_score;
     {
         ProfScope ps(PPM_K_LOCAL);
         hipLaunchKernelGGL(k_frame_maps, dim3((unsigned)ng), dim3(kFrameThreads), frame_lds_bytes(S_used), cur_stream(), MP);
         hipLaunchKernelGGL(k_frame_peak, dim3((unsigned)ng), dim3(64), (size_t)npts * sizeof(double), cur_stream(), PP);
     }
     HIPCHK(hipGetLastError());
-    std::vector<float> h_own, h_pool, h_score(2 * (size_t)nf);
-    std::vector<double> h_delta(2 * (size_t)nf);
-    if (own_maps) { h_own.resize((size_t)nf * npts); HIPCHK(hipMemcpyAsync(h_own.data(), ref->f_own.p, h_own.size() * sizeof(float), hipMemcpyDeviceToHost, cur_stream())); }
-    if (pooled_maps) { h_pool.resize((size_t)nf * npts); HIPCHK(hipMemcpyAsync(h_pool.data(), ref->f_pool.p, h_pool.size() * sizeof(float), hipMemcpyDeviceToHost, cur_stream())); }
+    h_score.resize(2 * (size_t)nf); h_delta.resize(2 * (size_t)nf);
+    if (own_maps) { h_own.resize((size_t)nf * npts); HIPCHK(hipMemcpyAsync(h_own.data(), ref->frames.own.p, h_own.size() * sizeof(float), hipMemcpyDeviceToHost, cur_stream())); }
+    if (pooled_maps) { h_pool.resize((size_t)nf * npts); HIPCHK(hipMemcpyAsync(h_pool.data(), ref->frames.pool.p, h_pool.size() * sizeof(float), hipMemcpyDeviceToHost, cur_stream())); }
     HIPCHK(hipMemcpyAsync(h_score.data(), d_score, h_score.size() * sizeof(float), hipMemcpyDeviceToHost, cur_stream()));
     HIPCHK(hipMemcpyAsync(h_delta.data(), PP.delta, h_delta.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
     HIPCHK(hipStreamSynchronize(cur_stream()));
@@ -194,5 +198,5 @@ extern "C" int ppm_frame_refine(ppm_ref_t *ref, const ppm_refine_cfg *cfg, const
     if (info) *info = fi;
     ref->last_counts[0] = npts; ref->last_counts[1] = 1; ref->last_counts[2] = (long)std::floor(kPi * gm.r_hi * gm.r_hi / 2);
     ref->last_counts[3] = (long)((double)L.models * S_used / std::max(n_rows, 1));
-    return 0;
+    return drain.ok();
 }

@@ -39,6 +39,28 @@ struct SvaXform {
 };
 }  // namespace
 
+// the transform of box N pruned to the band radius R (R = N / 2: the full one), windowed as `window` says (null: the whole sub-volumes, no window)
+static SvaXform sva_xform(int N, int R, const ppm_sva_cfg *window) {
+    SvaXform T;
+    T.N = N; T.R = R; T.KX = sva_kx(N, R); T.KY = sva_ky(N, R);
+    T.fast16 = N % 16 == 0 && getenv("PPM_SVA_GENERIC_FFT") == nullptr;
+    T.fold = !(getenv("PPM_SVA_FOLD") && atoi(getenv("PPM_SVA_FOLD")) == 0);
+    for (int k = 0; k < 3; k++) T.W.w[k] = window ? window->window[k] : 0.f;
+    T.W.sigma = window ? window->window_sigma : 0.f;
+    return T;
+}
+// its work arrays for `NB` sub-volumes per launch: grows w.f (and w.g, two-step only), allocates the x pass's partial sums, and only then
+// reads the pointers into T
+static int sva_bind_work(SvaXform &T, SvaWork &w, int NB, DevTmp<double> &spart) {
+    if (int rc = w.f.ensure((size_t)NB * T.N * T.N * T.KX)) return rc;
+    if (T.fast16) {
+        if (int rc = w.g.ensure((size_t)NB * T.KX * T.KY * T.N)) return rc;
+        HIPCHK(spart.alloc(sva_xpass_partials(T.N, NB)));
+    }
+    T.A = w.f.p; T.B = w.g.p; T.spart = spart.p;
+    return 0;
+}
+
 // Transforms of `mv` sub-volumes at `vols`.  mode 1: the sub-volumes, normalised by their statistics and windowed; mode 2 (two-step
 // only): the window's own transform.  Statistics: the two-step x pass gathers them into stats[mv][2]; the generic path (k_sva_xpass +
 // k_fft_lines) reads them there (k_sva_stats, the caller's).  Sink: with `F` the band's samples go to F[mv][S] (through `pos` in the
@@ -49,7 +71,7 @@ static int sva_transform(const SvaXform &T, int mode, const float *vols, int mv,
     const long NN2 = (long)N * N;
     if (int rc = ensure_plan(N)) return rc;
     if (T.fast16) {
-        const int L16 = N <= 256 ? 16 : 8;
+        const int L16 = sva_lines_per_block(N);
         const size_t lds = (size_t)L16 * (N + 1) * sizeof(float2);
         SvaX16P X; X.vol = vols; X.stats = mode == 1 ? T.spart : nullptr; X.A = T.A; X.tw = g.plans[N].plan.tw; X.n = N; X.L = L16; X.KX = KX; X.mode = mode;
         X.nlines = (long)mv * NN2; X.W = T.W;
@@ -92,19 +114,12 @@ static int sva_insert_device(ppm_accum_t *a, const ppm_sva_cfg *cfg, const float
     if (a->nsym < 1 || a->nsym > kSvaInsMaxSym) return fail(-22, "sub-tomogram averaging: the accumulator has more point-group operators than the kernel holds");
     const size_t n3 = (size_t)N * N * N;
     const int NB = std::min(n_vol, kSvaInsBatch);
-    SvaXform T;
-    T.N = N; T.R = N / 2; T.KX = N / 2 + 1; T.KY = N;
-    T.fast16 = N % 16 == 0 && getenv("PPM_SVA_GENERIC_FFT") == nullptr;
+    SvaXform T = sva_xform(N, N / 2, nullptr);        // the average is made of the whole sub-volumes: no window, no band-pass
     if (int rc = ensure_plan(N)) return rc;
-    if (int rc = a->s_f.ensure((size_t)NB * N * N * T.KX)) return rc;
-    if (T.fast16) if (int rc = a->s_g.ensure((size_t)NB * T.KX * T.KY * N)) return rc;
     DevTmp<double> d_spart, d_stats, d_poses; DevTmp<float> d_wedges; DevTmp<int> d_half;
-    const int L16 = N <= 256 ? 16 : 8;
-    HIPCHK(d_spart.alloc((size_t)2 * NB * ((size_t)N * N / L16 + 1))); HIPCHK(d_stats.alloc((size_t)2 * NB)); HIPCHK(d_poses.alloc((size_t)12 * NB));
+    if (int rc = sva_bind_work(T, a->sva, NB, d_spart)) return rc;
+    HIPCHK(d_stats.alloc((size_t)2 * NB)); HIPCHK(d_poses.alloc((size_t)12 * NB));
     HIPCHK(d_wedges.alloc((size_t)2 * NB)); HIPCHK(d_half.alloc(NB));
-    T.A = a->s_f.p; T.B = a->s_g.p; T.spart = d_spart.p;
-    for (int k = 0; k < 3; k++) T.W.w[k] = 0.f;       // the average is made of the whole sub-volumes: no window, no band-pass
-    T.W.sigma = 0.f;
     std::vector<float> hw((size_t)2 * NB); std::vector<int> hh(NB);
     long added[2] = { 0, 0 };
     for (int v0 = 0; v0 < n_vol; v0 += NB) {
@@ -147,11 +162,13 @@ static int sva_insert_device(ppm_accum_t *a, const ppm_sva_cfg *cfg, const float
 
 // ------------------------------------------------------------------------------ sub-tomogram alignment
 // Sample list of the band (half space, shell by shell), common to all sub-volumes; the wedge is applied per volume.  Built and sorted
-// on the host, uploaded with its `pos` table and kept in ref->s_plan while the band-pass settings stay (S, shell_off: there).
+// on the host, uploaded with its `pos` table and kept in ref->sva_band while the band-pass settings stay (S, shell_off: there).
 static int sva_band_plan(ppm_ref *ref, const ppm_sva_cfg *cfg, double rband) {
     const int N = cfg->box, R = (int)std::ceil(rband);
-    const float plan_key[5] = { (float)N, cfg->highpass_cutoff, cfg->highpass_decay, cfg->lowpass_cutoff, cfg->lowpass_decay };
-    if (ref->s_plan.valid && std::memcmp(plan_key, ref->s_plan.key, sizeof(plan_key)) == 0) return 0;
+    SvaBandPlan &bp = ref->sva_band;
+    SvaBandKey key; key.box = (float)N; key.highpass_cutoff = cfg->highpass_cutoff; key.highpass_decay = cfg->highpass_decay;
+    key.lowpass_cutoff = cfg->lowpass_cutoff; key.lowpass_decay = cfg->lowpass_decay;
+    if (bp.valid && key == bp.key) return 0;
     std::vector<uint32_t> samples; std::vector<float> bandw; std::vector<int> shell_off(R + 2, 0);
     // one pass over the half space, bucketed by shell (the order inside a shell is the scan order kz, ky, kx)
     std::vector<std::vector<uint32_t>> sh_s(R + 1); std::vector<std::vector<float>> sh_w(R + 1);
@@ -187,13 +204,13 @@ static int sva_band_plan(ppm_ref *ref, const ppm_sva_cfg *cfg, double rband) {
     }
     const int S = (int)samples.size();
     if (S == 0) return fail(-22, "the band-pass filter leaves no Fourier samples");
-    ref->s_plan.valid = false; ref->s_plan.fw_valid = false;
-    if (int rc = ref->s_plan.samples.ensure(S)) return rc;
-    if (int rc = ref->s_plan.bandw.ensure(S)) return rc;
-    HIPCHK(hipMemcpyAsync(ref->s_plan.samples.p, samples.data(), (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice, cur_stream()));
-    HIPCHK(hipMemcpyAsync(ref->s_plan.bandw.p, bandw.data(), (size_t)S * sizeof(float), hipMemcpyHostToDevice, cur_stream()));
+    bp.valid = false; bp.fw_valid = false;
+    if (int rc = bp.samples.ensure(S)) return rc;
+    if (int rc = bp.bandw.ensure(S)) return rc;
+    HIPCHK(hipMemcpyAsync(bp.samples.p, samples.data(), (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice, cur_stream()));
+    HIPCHK(hipMemcpyAsync(bp.bandw.p, bandw.data(), (size_t)S * sizeof(float), hipMemcpyHostToDevice, cur_stream()));
     // where a coefficient (kx, kyi, kzi) of the pruned transform sits in the sample list (k_sva_yz16's z pass emits the samples itself)
-    const int KX = std::min(N / 2 + 1, R + 1), KYp = std::min(N, 2 * R + 1);
+    const int KX = sva_kx(N, R), KYp = sva_ky(N, R);
     std::vector<unsigned> pos((size_t)KX * KYp * KYp, 0x7fffffffu);
     for (int i = 0; i < S; i++) {
         int kx, ky, kz; sva_unpack(samples[i], kx, ky, kz);
@@ -201,10 +218,10 @@ static int sva_band_plan(ppm_ref *ref, const ppm_sva_cfg *cfg, double rband) {
         const int kyi = ky >= 0 ? ky : ky + KYp, kzi = kz >= 0 ? kz : kz + KYp;
         pos[((size_t)kx * KYp + kyi) * KYp + kzi] = (unsigned)i | (((kx + ky + kz) & 1) ? 0x80000000u : 0u);
     }
-    if (int rc = ref->s_plan.pos.ensure(pos.size())) return rc;
-    HIPCHK(hipMemcpyAsync(ref->s_plan.pos.p, pos.data(), pos.size() * sizeof(unsigned), hipMemcpyHostToDevice, cur_stream()));
+    if (int rc = bp.pos.ensure(pos.size())) return rc;
+    HIPCHK(hipMemcpyAsync(bp.pos.p, pos.data(), pos.size() * sizeof(unsigned), hipMemcpyHostToDevice, cur_stream()));
     HIPCHK(hipStreamSynchronize(cur_stream()));        // the host vectors go out of use here
-    std::memcpy(ref->s_plan.key, plan_key, sizeof(plan_key)); ref->s_plan.S = S; ref->s_plan.shell_off = shell_off; ref->s_plan.valid = true;
+    bp.key = key; bp.S = S; bp.shell_off = shell_off; bp.valid = true;
     return 0;
 }
 
@@ -223,8 +240,8 @@ struct SvaPlan {
 struct SvaSearch {
     SvaEvalP EP;
     int N = 0, R = 0; double rband = 0, bf = 3.0, rm_px = 0; const std::vector<int> *shell_off = nullptr;
-    double *d_poses = nullptr, *d_delta = nullptr, *d_out = nullptr; int *d_vmap = nullptr;
-    double *d_acc = nullptr, *d_dtrial = nullptr, *d_fpm = nullptr, *d_delta_t = nullptr, *d_tout = nullptr;     // the compass search's state (k_csp_step_*)
+    double *d_poses = nullptr, *d_delta = nullptr, *d_out = nullptr; int *d_vmap = nullptr;     // DevTmps of the call: they never move
+    CompassWs *compass = nullptr;       // the compass search's state (k_csp_step_*), the handle's: ensured for a chunk's states before the chunk loop
     std::vector<double> hp, hout;
     double acct_gathers = 0; long acct_sweeps = 0;      // for the roofline: band samples x rotations gathered, summed over the sweeps (wedge-masked samples included)
     int prefix_of(double rb) const { int rg = (int)std::ceil(rb); if (rg > R + 1) rg = R + 1; return (*shell_off)[rg]; }
@@ -271,19 +288,16 @@ static int sva_compass(SvaSearch &Q, std::vector<CUnit> &st, const std::vector<i
     if (int rc = sva_upload_states(Q, st, vm)) return rc;
     std::vector<double> hacc((size_t)ns * 6);
     for (int v = 0; v < ns; v++) std::memcpy(&hacc[(size_t)v * 6], st[v].acc, 6 * sizeof(double));
-    HIPCHK(hipMemcpyAsync(Q.d_acc, hacc.data(), hacc.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
-    CspStepP SP;
-    SP.kind = PPM_CSP_PARTICLES; SP.n_active = ns; SP.ncand = nc; SP.active = nullptr; SP.unit_slot = nullptr;
-    for (int i = 0; i < 6; i++) { SP.en[i] = en[i]; SP.tol[i] = tol[i]; }
-    SP.acc = Q.d_acc; SP.dtrial = Q.d_dtrial; SP.fpm = Q.d_fpm;
-    SP.delta_c = Q.d_delta; SP.delta_t = Q.d_delta_t; SP.Nmat = Q.d_poses; SP.pshift = Q.d_poses + 9; SP.tl = nullptr; SP.nstride = 12; SP.pstride = 12;
-    if (int rc = compass_enqueue(SP, Q.d_out, Q.d_tout, Tn, ha, hs,
+    HIPCHK(hipMemcpyAsync(Q.compass->acc.p, hacc.data(), hacc.size() * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    CompassPoses at;
+    at.n_active = ns; at.Nmat = Q.d_poses; at.nstride = 12; at.pshift = Q.d_poses + 9; at.pstride = 12; at.delta = Q.d_delta; at.mean = Q.d_out;
+    if (int rc = compass_enqueue(*Q.compass, at, en, tol, Tn, ha, hs,
             [&](double ha_, double hs_) { return march_band(Q.bf, Q.N, Q.rm_px, ha_, hs_, en[0] != 0, en[3] != 0, Q.rband); },
-            [&](const double *delta, int ncand, double rb, double *out) { return sva_launch_eval(Q, ns, ncand, delta == Q.d_delta ? nrot : 0, rb, delta, out); })) return rc;      // the compass sweep has the rotated candidates, the trial none
+            [&](const double *delta, int ncand, double rb, double *out) { return sva_launch_eval(Q, ns, ncand, ncand > 1 ? nrot : 0, rb, delta, out); })) return rc;      // the compass sweep has the rotated candidates, the trial (one candidate) none
     Q.EP.delta = Q.d_delta;
     Q.hp.resize((size_t)12 * ns);
     HIPCHK(hipMemcpyAsync(Q.hp.data(), Q.d_poses, Q.hp.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
-    HIPCHK(hipMemcpyAsync(hacc.data(), Q.d_acc, hacc.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
+    HIPCHK(hipMemcpyAsync(hacc.data(), Q.compass->acc.p, hacc.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
     HIPCHK(hipStreamSynchronize(cur_stream()));
     for (int v = 0; v < ns; v++) {
         pose_unpack(&Q.hp[(size_t)12 * v], st[v]);
@@ -310,9 +324,7 @@ static int sva_final_scores(SvaSearch &Q, const std::vector<CUnit> &st, const st
 static int sva_global_candidates(SvaSearch &Q, const SvaPlan &P, const std::vector<CUnit> &st, const float *d_grid, float *d_gscore,
                                  std::vector<CUnit> &cand, std::vector<int> &vm) {
     const int nb = (int)st.size(), n_grid = P.n_grid, Kc = P.Kc;
-    Q.hp.resize((size_t)12 * nb);
-    for (int v = 0; v < nb; v++) pose_pack(st[v], &Q.hp[(size_t)12 * v]);
-    HIPCHK(hipMemcpyAsync(Q.d_poses, Q.hp.data(), (size_t)12 * nb * sizeof(double), hipMemcpyHostToDevice, cur_stream()));
+    if (int rc = sva_upload_states(Q, st, nullptr)) return rc;
     const SvaEvalP &EP = Q.EP;
     SvaGlobalP GP;
     GP.cv = EP.cv; GP.samples = EP.samples; GP.bandw = EP.bandw; GP.F = EP.F; GP.S = EP.S; GP.N = EP.N; GP.S_used = Q.prefix_of(P.rg); GP.rmax2 = (float)(P.rg * P.rg);
@@ -403,40 +415,45 @@ static int sva_transform_chunk(ppm_ref *ref, const SvaXform &T, const float *dv,
     for (int v0 = 0; v0 < nb; v0 += NB) {
         const int m = std::min(NB, nb - v0);
         if (T.fast16) {
-            const float wkey[4] = { T.W.w[0], T.W.w[1], T.W.w[2], T.W.sigma };
-            if (!ref->s_plan.fw_valid || std::memcmp(wkey, ref->s_plan.wkey, sizeof(wkey)) != 0) {     // the window's own transform, once per window
-                if (int rc = ref->s_plan.Fw.ensure(T.S)) return rc;
-                if (int rc = sva_transform(T, 2, dv, 1, nullptr, ref->s_plan.Fw.p, nullptr)) return rc;
-                std::memcpy(ref->s_plan.wkey, wkey, sizeof(wkey)); ref->s_plan.fw_valid = true;
+            SvaBandPlan &bp = ref->sva_band;
+            SvaWindowKey wkey; for (int k = 0; k < 3; k++) wkey.w[k] = T.W.w[k];
+            wkey.sigma = T.W.sigma;
+            if (!bp.fw_valid || !(wkey == bp.wkey)) {     // the window's own transform, once per window
+                if (int rc = bp.Fw.ensure(T.S)) return rc;
+                if (int rc = sva_transform(T, 2, dv, 1, nullptr, bp.Fw.p, nullptr)) return rc;
+                bp.wkey = wkey; bp.fw_valid = true;
             }
         }
-        if (int rc = sva_transform(T, 1, dv + (size_t)v0 * n3, m, d_stats + 2 * v0, F + (size_t)v0 * T.S, T.fast16 ? ref->s_plan.Fw.p : nullptr)) return rc;
+        if (int rc = sva_transform(T, 1, dv + (size_t)v0 * n3, m, d_stats + 2 * v0, F + (size_t)v0 * T.S, T.fast16 ? ref->sva_band.Fw.p : nullptr)) return rc;
     }
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-// ppm_sva_align and ppm_sva_align_average: with an accumulator every chunk is added to the average at its refined poses while it is
-// still in device memory (host volumes cross PCIe once per iteration)
-static int sva_align_impl(ppm_ref_t *ref, ppm_accum_t *avg, const ppm_sva_cfg *cfg, const void *volumes, int volumes_on_device, int n_vol, const float *wedges,
-                          double *poses, double *scores, const long *index) {
-    if (!g.inited) return fail(-1, "ppm_init has not been called");
-    if (!ref || !cfg || !volumes || !poses) return fail(-22, "null argument");
-    StreamScope ss_(ref->stream, ref->copy);
-    if (n_vol <= 0) return 0;
-    const Trace trace_("ppm_sva_align");
-    const int N = cfg->box;
+namespace {
+// what is fixed before the chunk loop of ppm_sva_align / ppm_sva_align_average
+struct SvaRun {
+    ppm_ref *ref = nullptr; const ppm_sva_cfg *cfg = nullptr; const float *volumes = nullptr; bool on_device = false; int n_vol = 0;
+    int N = 0, R = 0; size_t n3 = 0; double rband = 0, bf = 3.0, rm_px = 0;
+    SvaPlan P; SvaXform T; SvaChunks ch;
+};
+// the call's device temporaries (freed on every exit) and the wedges' staging vector
+struct SvaTmp { DevTmp<float> wedges, grid, gscore; DevTmp<double> stats, poses, delta, out, partial, spart; DevTmp<int> vmap; std::vector<float> hw; };
+}  // namespace
+
+// validation, the band's sample list (ref->sva_band) and the search plan
+static int sva_plan_call(SvaRun &r) {
+    ppm_ref *ref = r.ref; const ppm_sva_cfg *cfg = r.cfg;
+    const int N = r.N = cfg->box;
     if (!box_ok(N) || N != ref->N) return fail(-22, "sub-volume box differs from the reference box (even, 32..512, prime factors 2, 3, 5, 7)");
     if (ref->pad != 1) return fail(-22, "sub-tomogram alignment needs a reference prepared with padding 1");
-    const double rband = sva_band_radius(*cfg);
-    if (rband > ref->B) return fail(-22, "low-pass limit exceeds the band the reference was prepared for");
-    const size_t n3 = (size_t)N * N * N;
-    const int R = (int)std::ceil(rband);
-    if (int rc = sva_band_plan(ref, cfg, rband)) return rc;
-    const int S = ref->s_plan.S;
-    const double bf = cfg->band_factor == 0 ? 3.0 : cfg->band_factor;
-    double rm_px = std::max(cfg->window[0], std::max(cfg->window[1], cfg->window[2]));
-    if (!(rm_px > 0)) rm_px = 0.4 * N;
+    r.rband = sva_band_radius(*cfg);
+    if (r.rband > ref->B) return fail(-22, "low-pass limit exceeds the band the reference was prepared for");
+    r.n3 = (size_t)N * N * N; r.R = (int)std::ceil(r.rband);
+    if (int rc = sva_band_plan(ref, cfg, r.rband)) return rc;
+    r.bf = cfg->band_factor == 0 ? 3.0 : cfg->band_factor;
+    r.rm_px = std::max(cfg->window[0], std::max(cfg->window[1], cfg->window[2]));
+    if (!(r.rm_px > 0)) r.rm_px = 0.4 * N;
     // the reference's point group cuts the global search's grid to the asymmetric unit; no other search mode reads the field
     char sym[9] = { 0 }; int nsym = 1;
     if (cfg->search_mode == 1) {
@@ -449,84 +466,92 @@ static int sva_align_impl(ppm_ref_t *ref, ppm_accum_t *avg, const ppm_sva_cfg *c
         if (nsym < 1 || (t == 'C' && nsym != order) || (t == 'D' && nsym != 2 * order))
             return fail(-22, std::string("unknown symmetry symbol '") + sym + "' in the sub-tomogram alignment settings (C1, Cn, Dn, T, O, I; at most 60 operators)");
     }
-    const SvaPlan P = sva_search_plan(cfg, sym, nsym, rband, rm_px, bf);
-    // ---- device buffers (RAII), chunks of sub-volumes
-    // chunks of sub-volumes: the search kernel runs one block per sub-volume, so a chunk should fill the chip (>= 256 blocks).  Resident
-    // volumes: limited by the band transforms (S float2 each, 4 GB); host volumes: two staging buffers of a chunk each (2 x 7 GB at
-    // 192^3 — small change on a 288 GB device), the next chunk uploaded while this one is searched.
-    int CH = (int)std::min<size_t>((size_t)n_vol, std::max<size_t>(1, ((size_t)4 << 30) / ((size_t)S * 8)));
-    if (!volumes_on_device) {
-        const int hc = getenv("PPM_SVA_CHUNK") ? std::max(1, atoi(getenv("PPM_SVA_CHUNK"))) : (int)std::max<size_t>(1, ((size_t)7 << 30) / (n3 * 4));
-        CH = std::min(CH, hc);
-    }
-    DevTmp<float> d_wedges, d_grid, d_gscore; DevTmp<double> d_stats, d_poses, d_delta, d_out, d_partial, d_spart; DevTmp<int> d_vmap;
-    const int NB = std::min(CH, 32);                     // sub-volumes transformed per launch (work array: NB x N x N x KX complex)
-    SvaXform T;
-    T.N = N; T.R = R; T.KX = std::min(N / 2 + 1, R + 1); T.KY = std::min(N, 2 * R + 1);      // x coefficients kept; |ky|, |kz| <= R are the lines the later passes touch
-    T.fast16 = N % 16 == 0 && getenv("PPM_SVA_GENERIC_FFT") == nullptr;
-    T.fold = !(getenv("PPM_SVA_FOLD") && atoi(getenv("PPM_SVA_FOLD")) == 0);
-    for (int k = 0; k < 3; k++) T.W.w[k] = cfg->window[k];
-    T.W.sigma = cfg->window_sigma;
-    if (int rc = ref->s_f.ensure((size_t)NB * N * N * T.KX)) return rc;
-    if (int rc = ref->s_F.ensure((size_t)CH * S)) return rc;
-    if (T.fast16) {
-        if (int rc = ref->s_g.ensure((size_t)NB * T.KX * T.KY * N)) return rc;
-        HIPCHK(d_spart.alloc((size_t)2 * NB * ((size_t)N * N / (N <= 256 ? 16 : 8))));
-    }
-    T.A = ref->s_f.p; T.B = ref->s_g.p; T.spart = d_spart.p; T.S = S; T.samples = ref->s_plan.samples.p; T.pos = ref->s_plan.pos.p;
-    const size_t CHS = (size_t)CH * (P.global ? P.Kc : 1);       // states per chunk: the global search refines Kc candidates per sub-volume
-    HIPCHK(d_stats.alloc((size_t)2 * CH)); HIPCHK(d_poses.alloc((size_t)12 * CHS)); HIPCHK(d_delta.alloc(CHS * P.ncand * 6)); HIPCHK(d_out.alloc(CHS * P.ncand));
-    HIPCHK(d_vmap.alloc(CHS)); HIPCHK(d_partial.alloc(CHS * kSvaParts * (2 * kMaxCand + 1)));
-    // the compass search's state on the device (ppm_csp_kernels.h: k_csp_step_*), kept in the handle like the constrained search's
-    // (allocating and freeing five more buffers per call cost 7 ms of a 57 ms call: hipFree waits for the device)
-    if (int rc = ref->c_acc.ensure(CHS * 6)) return rc;
-    if (int rc = ref->c_dtrial.ensure(CHS * 6)) return rc;
-    if (int rc = ref->c_fpm.ensure(CHS * 12)) return rc;
-    if (int rc = ref->c_delta_t.ensure(CHS * 6)) return rc;
-    if (int rc = ref->c_tmean.ensure(CHS)) return rc;
+    r.P = sva_search_plan(cfg, sym, nsym, r.rband, r.rm_px, r.bf);
+    return 0;
+}
+
+// Workspaces of the call and what points into them.  Every ensure of the handle's buffers that r.T and Q.EP name (sva.f, sva.g, sva.F; the
+// band's samples, pos and bandw were ensured by sva_band_plan) and the compass state's come first, then the pointers are read; nothing grows
+// those buffers again before the call returns.  sva_band.Fw, which sva_transform_chunk may grow, is read from its DevBuf there.
+static int sva_workspaces(SvaRun &r, SvaTmp &t, SvaSearch &Q) {
+    ppm_ref *ref = r.ref; const SvaPlan &P = r.P; const SvaBandPlan &bp = ref->sva_band;
+    const size_t CH = (size_t)r.ch.CH, CHS = r.ch.states;
+    if (int rc = sva_bind_work(r.T, ref->sva, r.ch.NB, t.spart)) return rc;
+    if (int rc = ref->sva.F.ensure(CH * bp.S)) return rc;
+    if (int rc = ref->compass.ensure(CHS)) return rc;
+    if (r.ch.staging) if (int rc = ref->sva.vols.ensure((size_t)r.ch.staging * CH * r.n3)) return rc;
+    HIPCHK(t.stats.alloc(2 * CH)); HIPCHK(t.poses.alloc(12 * CHS)); HIPCHK(t.delta.alloc(CHS * P.ncand * 6)); HIPCHK(t.out.alloc(CHS * P.ncand));
+    HIPCHK(t.vmap.alloc(CHS)); HIPCHK(t.partial.alloc(CHS * kSvaParts * (2 * kMaxCand + 1))); HIPCHK(t.wedges.alloc(2 * CH));
     if (P.global) {
         std::vector<float> gf(P.grid_d.begin(), P.grid_d.end());
-        HIPCHK(d_grid.alloc(gf.size())); HIPCHK(d_gscore.alloc((size_t)CH * P.n_grid));
-        HIPCHK(hipMemcpy(d_grid.p, gf.data(), gf.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(t.grid.alloc(gf.size())); HIPCHK(t.gscore.alloc(CH * P.n_grid));
+        HIPCHK(hipMemcpy(t.grid.p, gf.data(), gf.size() * sizeof(float), hipMemcpyHostToDevice));
     }
-    HIPCHK(d_wedges.alloc((size_t)2 * CH));
-    const bool two_bufs = !volumes_on_device && n_vol > CH;      // host volumes: the next chunk is uploaded by a helper thread while this one is searched
-    if (!volumes_on_device) if (int rc = ref->s_vols.ensure((size_t)(two_bufs ? 2 : 1) * CH * n3)) return rc;
-    float *d_vols = ref->s_vols.p;
-    SvaSearch Q;
-    Q.N = N; Q.R = R; Q.rband = rband; Q.bf = bf; Q.rm_px = rm_px; Q.shell_off = &ref->s_plan.shell_off;
-    Q.d_poses = d_poses.p; Q.d_delta = d_delta.p; Q.d_out = d_out.p; Q.d_vmap = d_vmap.p;
-    Q.d_acc = ref->c_acc.p; Q.d_dtrial = ref->c_dtrial.p; Q.d_fpm = ref->c_fpm.p; Q.d_delta_t = ref->c_delta_t.p; Q.d_tout = ref->c_tmean.p;
+    t.hw.resize(2 * CH);
+    r.T.S = bp.S; r.T.samples = bp.samples.p; r.T.pos = bp.pos.p;
+    Q.N = r.N; Q.R = r.R; Q.rband = r.rband; Q.bf = r.bf; Q.rm_px = r.rm_px; Q.shell_off = &bp.shell_off; Q.compass = &ref->compass;
+    Q.d_poses = t.poses.p; Q.d_delta = t.delta.p; Q.d_out = t.out.p; Q.d_vmap = t.vmap.p;
     SvaEvalP &EP = Q.EP;
     EP.cv = cube_view(ref);         // scale = 1: a reference with pad != 1 was refused above
-    EP.samples = T.samples; EP.bandw = ref->s_plan.bandw.p; EP.F = ref->s_F.p; EP.S = S; EP.N = N; EP.use_wedge = cfg->use_missing_wedge != 0;
+    EP.samples = bp.samples.p; EP.bandw = bp.bandw.p; EP.F = ref->sva.F.p; EP.S = bp.S; EP.N = r.N; EP.use_wedge = r.cfg->use_missing_wedge != 0;
     EP.tabR = ref->B + 4;           // every sample of the band (|k| <= B + 1) and its upper taps
-    EP.wedges = d_wedges.p; EP.poses = d_poses.p; EP.delta = d_delta.p; EP.out = d_out.p; EP.vmap = nullptr; EP.partial = d_partial.p;
-    std::vector<float> hw((size_t)2 * CH);
+    EP.wedges = t.wedges.p; EP.poses = t.poses.p; EP.delta = t.delta.p; EP.out = t.out.p; EP.vmap = nullptr; EP.partial = t.partial.p;
+    return 0;
+}
+
+// The volumes of chunk `ci` (from c0 on) in device memory: where the caller has them, or the staging buffer the helper thread filled,
+// whose upload of the NEXT chunk starts here (the host drives this chunk's search, a synchronisation per sweep: the copy gets its own
+// thread and stream).
+static int sva_stage_volumes(const SvaRun &r, SvaUploader &up, int c0, int ci, const float **dv) {
+    const size_t chunk = (size_t)r.ch.CH * r.n3;
+    *dv = r.volumes + (size_t)c0 * r.n3;
+    if (r.on_device) return 0;
+    up.join();
+    if (up.err != hipSuccess) return fail(-5, std::string("HIP: ") + hipGetErrorString(up.err) + " while uploading sub-volumes");
+    float *d_vols = r.ref->sva.vols.p;
+    *dv = d_vols + (r.ch.staging == 2 ? (size_t)(ci & 1) * chunk : 0);
+    if (c0 + r.ch.CH < r.n_vol) {
+        const int nn = std::min(r.ch.CH, r.n_vol - (c0 + r.ch.CH));
+        up.start(d_vols + (size_t)((ci + 1) & 1) * chunk, r.volumes + (size_t)(c0 + r.ch.CH) * r.n3, (size_t)nn * r.n3 * sizeof(float), g.device, cur_copy());
+    }
+    return 0;
+}
+
+// ppm_sva_align and ppm_sva_align_average: with an accumulator every chunk is added to the average at its refined poses while it is
+// still in device memory (host volumes cross PCIe once per iteration)
+static int sva_align_impl(ppm_ref_t *ref, ppm_accum_t *avg, const ppm_sva_cfg *cfg, const void *volumes, int volumes_on_device, int n_vol, const float *wedges,
+                          double *poses, double *scores, const long *index) {
+    if (!g.inited) return fail(-1, "ppm_init has not been called");
+    if (!ref || !cfg || !volumes || !poses) return fail(-22, "null argument");
+    StreamScope ss_(ref->stream, ref->copy);
+    if (n_vol <= 0) return 0;
+    const Trace trace_("ppm_sva_align");
+    SvaRun r;
+    r.ref = ref; r.cfg = cfg; r.volumes = (const float *)volumes; r.on_device = volumes_on_device != 0; r.n_vol = n_vol;
+    if (int rc = sva_plan_call(r)) return rc;
+    const SvaPlan &P = r.P;
+    const int knob = getenv("PPM_SVA_CHUNK") ? std::max(1, atoi(getenv("PPM_SVA_CHUNK"))) : 0;
+    r.ch = sva_chunks(n_vol, (size_t)ref->sva_band.S, r.n3, r.on_device, knob, P.global, P.Kc);
+    r.T = sva_xform(r.N, r.R, cfg);
+    SvaTmp t; SvaSearch Q;
+    if (int rc = sva_workspaces(r, t, Q)) return rc;
     trace_.mark("set up");
-    if (!volumes_on_device) {       // first chunk
-        HIPCHK(hipMemcpyAsync(d_vols, volumes, (size_t)std::min(CH, n_vol) * n3 * sizeof(float), hipMemcpyHostToDevice, cur_copy()));
+    const int CH = r.ch.CH;
+    if (!r.on_device) {       // first chunk
+        HIPCHK(hipMemcpyAsync(ref->sva.vols.p, volumes, (size_t)std::min(CH, n_vol) * r.n3 * sizeof(float), hipMemcpyHostToDevice, cur_copy()));
         HIPCHK(hipStreamSynchronize(cur_copy()));
     }
     SvaUploader up;
     for (int c0 = 0, ci = 0; c0 < n_vol; c0 += CH, ci++) {
         const int nb = std::min(CH, n_vol - c0);
-        const float *dv = (const float *)volumes + (size_t)c0 * n3;
-        if (!volumes_on_device) {
-            up.join();
-            if (up.err != hipSuccess) return fail(-5, std::string("HIP: ") + hipGetErrorString(up.err) + " while uploading sub-volumes");
-            dv = d_vols + (size_t)(ci & 1) * (two_bufs ? (size_t)CH * n3 : 0);
-            if (c0 + CH < n_vol) {      // the host drives the search of this chunk (a synchronisation per sweep): the copy of the next one gets its own thread and stream
-                const int nn = std::min(CH, n_vol - (c0 + CH));
-                up.start(d_vols + (size_t)((ci + 1) & 1) * CH * n3, (const float *)volumes + (size_t)(c0 + CH) * n3, (size_t)nn * n3 * sizeof(float), g.device, cur_copy());
-            }
-        }
-        if (int rc = stage_wedges(hw, wedges, (size_t)c0, nb, d_wedges.p)) return rc;
-        if (int rc = sva_transform_chunk(ref, T, dv, nb, NB, d_stats.p, ref->s_F.p)) return rc;
+        const float *dv = nullptr;
+        if (int rc = sva_stage_volumes(r, up, c0, ci, &dv)) return rc;
+        if (int rc = stage_wedges(t.hw, wedges, (size_t)c0, nb, t.wedges.p)) return rc;
+        if (int rc = sva_transform_chunk(ref, r.T, dv, nb, r.ch.NB, t.stats.p, ref->sva.F.p)) return rc;
         trace_.mark("chunk pre-processed");
         std::vector<CUnit> st(nb);
         for (int v = 0; v < nb; v++) pose_unpack(poses + (size_t)(c0 + v) * 12, st[v]);
-        if (int rc = sva_search_chunk(Q, P, cfg, st, d_grid.p, d_gscore.p)) return rc;
+        if (int rc = sva_search_chunk(Q, P, cfg, st, t.grid.p, t.gscore.p)) return rc;
         trace_.mark("chunk searched");
         if (int rc = sva_final_scores(Q, st, nullptr)) return rc;
         for (int v = 0; v < nb; v++) {
@@ -540,7 +565,7 @@ static int sva_align_impl(ppm_ref_t *ref, ppm_accum_t *avg, const ppm_sva_cfg *c
     }
     // ppm_refine_last_counts after an alignment: grid rotations of the global search, sweeps (k_sva_eval launches), samples of the band
     // (half space, before the wedge), band samples x gathered rotations per sub-volume summed over the sweeps
-    ref->last_counts[0] = P.n_grid; ref->last_counts[1] = Q.acct_sweeps; ref->last_counts[2] = S; ref->last_counts[3] = (long)(Q.acct_gathers / n_vol);
+    ref->last_counts[0] = P.n_grid; ref->last_counts[1] = Q.acct_sweeps; ref->last_counts[2] = ref->sva_band.S; ref->last_counts[3] = (long)(Q.acct_gathers / n_vol);
     return 0;
 }
 
@@ -568,11 +593,11 @@ extern "C" int ppm_sva_insert(ppm_accum_t *a, const ppm_sva_cfg *cfg, const void
     if (!box_ok(N) || N != a->N) return fail(-22, "sub-volume box differs from the accumulator's box (even, 32..512, prime factors 2, 3, 5, 7)");
     const size_t n3 = (size_t)N * N * N;
     const int NB = std::min(n_vol, kSvaInsBatch);
-    if (int rc = a->s_vols.ensure((size_t)NB * n3)) return rc;
+    if (int rc = a->sva.vols.ensure((size_t)NB * n3)) return rc;
     for (int v0 = 0; v0 < n_vol; v0 += NB) {            // host volumes: staged batch by batch
         const int m = std::min(NB, n_vol - v0);
-        HIPCHK(hipMemcpyAsync(a->s_vols.p, (const float *)volumes + (size_t)v0 * n3, (size_t)m * n3 * sizeof(float), hipMemcpyHostToDevice, cur_stream()));
-        if (int rc = sva_insert_device(a, cfg, a->s_vols.p, m, wedges ? wedges + 2 * (size_t)v0 : nullptr, poses + (size_t)v0 * 12, index ? index + v0 : nullptr, v0)) return rc;
+        HIPCHK(hipMemcpyAsync(a->sva.vols.p, (const float *)volumes + (size_t)v0 * n3, (size_t)m * n3 * sizeof(float), hipMemcpyHostToDevice, cur_stream()));
+        if (int rc = sva_insert_device(a, cfg, a->sva.vols.p, m, wedges ? wedges + 2 * (size_t)v0 : nullptr, poses + (size_t)v0 * 12, index ? index + v0 : nullptr, v0)) return rc;
     }
     return 0;
 }

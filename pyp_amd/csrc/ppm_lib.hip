@@ -26,6 +26,7 @@
 #include "ppm_sections.h"
 #include "ppm_overlap.h"
 #include "ppm_defocus_plan.h"
+#include "ppm_sva_plan.h"
 #include "ppm_kernels2.h"
 #include "ppm_csp_kernels.h"
 #include "ppm_frame_kernels.h"

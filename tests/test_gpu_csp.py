@@ -140,6 +140,28 @@ def test_csp_errors_are_loud(series):
         g.csp_refine(cfg, CspCfg.make(7), imgs, rows, parts, tilts)
 
 
+def test_a_refused_call_on_resident_images_leaves_the_handle_clean(series):
+    """The refusal of test_csp_errors_are_loud (a row of a missing particle) comes after the spectra of all rows were enqueued, with
+    the stack in device memory and so without a wait of its own: the call drains its stream before it returns, and the next call on
+    the same handle answers bit for bit what a fresh handle answers."""
+    import torch
+    from pyp_amd import host, lib
+    n, px, vol, imgs, rows, parts, tilts, cfg, g, o, O = series
+    dev = torch.as_tensor(imgs.copy()).cuda()
+    p2 = _perturb_particles(parts)
+    rows2 = synth.csp_rows_from_params(rows, parts, tilts, p2, tilts)
+    cc = CspCfg.make(CSP_PARTICLES, tol_angle=(8, 8, 8), tol_shift=4.0)
+    bad = rows.copy(); bad[3, 26] = 999
+    with pytest.raises(lib.PpmError, match="row 4 refers to a particle or tilt missing"):
+        g.csp_refine(cfg, CspCfg.make(CSP_PARTICLES), dev, bad, parts, tilts)
+    gr, gp, gt = g.csp_refine(cfg, cc, dev, rows2, p2, tilts)
+    fresh = host.Reference(vol, n / 2)
+    fr, fp, ft = fresh.csp_refine(cfg, cc, dev, rows2, p2, tilts)
+    fresh.close()
+    assert np.array_equal(gr, fr) and np.array_equal(gp, fp) and np.array_equal(gt, ft)
+    assert not np.array_equal(gp, p2)                                   # and it searched
+
+
 def test_csp_executable_extracts_then_refines_like_the_caller_drives_it(tmp_path):
     """The argv of create_csp_split_commands (local_run.py:364-376, :451-463): mode -2 per particle range into per-range
     stacks (merged like mrc.merge_fast), then mode 5 over particle ranges and mode 6 over tilts; the range outputs are

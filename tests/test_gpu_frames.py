@@ -239,6 +239,29 @@ def test_the_four_refusals(common, H):
             g.frame_refine(cfg, FC.fcfg(**{**dict(half_width=2), **kw}), imgs[:7], rows[:7])
 
 
+def test_a_refused_call_on_resident_images_leaves_the_handle_clean(common, H):
+    """None of the four refusals is reached after the spectra are enqueued (the plan's three come first of all, the doubled FIND while
+    the frame list is built, ahead of any device work), so this takes the earliest that touches the rows, the doubled FIND: the guard
+    that drains the stream on an error return does no harm, and the next call on the handle, on images in device memory, answers
+    bit for bit what a fresh handle answers."""
+    import torch
+    from pyp_amd import lib
+    g, imgs, rows, true, run = common
+    cfg, fc = FC.cfg_for(N), FC.fcfg(2)
+    dev = torch.as_tensor(imgs[:14].copy()).cuda()
+    r = rows[:14].copy()
+    r[4, C["FIND"]] = 2
+    with pytest.raises(lib.PpmError, match="FIND 2 occurs twice"):
+        g.frame_refine(cfg, fc, dev, r, maps=True)
+    out, info, own, pooled = g.frame_refine(cfg, fc, dev, rows[:14], maps=True)
+    fresh = H.Reference(FC.series()[0], N / 2)
+    o2, i2, w2, p2 = fresh.frame_refine(cfg, fc, dev, rows[:14], maps=True)
+    fresh.close()
+    assert info == i2 and info["groups"] == 2 and info["rows_refined"] == 14
+    assert np.array_equal(out, o2) and np.array_equal(own, w2) and np.array_equal(pooled, p2)
+    assert np.array_equal(own, run(2)[2][:14])                          # ... which is what the whole series gave for these groups
+
+
 # ------------------------------------------------------------------------------------------------ 6. drop-in
 TOML = ('data_set = "mov"\nscope_pixel = 1.5\ndata_bin = 1\nextract_bin = 1\nextract_box = 64\nparticle_rad = 38.4\nparticle_mw = 300\n'
         'refine_iter = 2\nrefine_rlref = 0.0\nrefine_rhref = 4.8\nrefine_fboost = false\ncsp_UseImagesForRefinementMin = %d\n'

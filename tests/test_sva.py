@@ -146,6 +146,47 @@ def test_host_volumes_in_several_chunks_equal_resident_volumes(monkeypatch):
 
 
 @pytest.mark.gpu
+def test_workspaces_that_regrow_between_calls_change_nothing():
+    """One handle: 3 sub-volumes, then 11 with the global search (25 states each: the compass state, the band transforms and the
+    staging buffer all grow and move), then the first 3 again - bit for bit the first answer."""
+    from pyp_amd import host
+    n = 32
+    vol, vols, poses, wedges = synth.make_subtomograms(n, 11, snr=0.5)
+    start = synth.perturb_poses(poses, 3.0, 1.0)
+    v = vols.numpy()
+    g = host.Reference(vol, n / 2)
+    first, fsc = g.sva_align(cfg_for(n), v[:3], wedges[:3], start[:3])
+    wide, wsc = g.sva_align(cfg_for(n, search_mode=1, global_step=20.0), v, wedges, start)
+    again, asc = g.sva_align(cfg_for(n), v[:3], wedges[:3], start[:3])
+    assert np.array_equal(first, again) and np.array_equal(fsc, asc)
+    assert not np.array_equal(first, start[:3]) and wsc.min() > 0.8 and wide.shape == (11, 12)
+    g.close()
+
+
+@pytest.mark.gpu
+def test_the_constrained_search_and_the_alignment_share_a_handle():
+    """The compass state is one workspace for ppm_csp_refine and ppm_sva_align: 8 particles, then 11 sub-volumes with the global search
+    (275 states: it grows), then the same 8 particles - bit for bit the first answer."""
+    from pyp_amd import host
+    from pyp_amd.abi import CSP_PARTICLES, CspCfg, RefineCfg
+    from test_csp_cpu import _perturb_particles
+    n, px = 32, 2.0
+    vol, vols, poses, wedges = synth.make_subtomograms(n, 11, snr=0.5)
+    _, stack, rows, parts, tilts = synth.make_tilt_series(n, 8, np.arange(-48, 49, 24.0), pixel=px, snr=0.3, vol=vol)
+    cfg = RefineCfg.make(box=n, pixel_size=px, mask_radius=0.4 * n * px, res_high=px * n / 12, res_signed_cc=30.0, global_search=0)
+    p2 = _perturb_particles(parts)
+    rows2 = synth.csp_rows_from_params(rows, parts, tilts, p2, tilts)
+    cc = CspCfg.make(CSP_PARTICLES, tol_angle=(8, 8, 8), tol_shift=4.0)
+    g = host.Reference(vol, n / 2)
+    r1, q1, t1 = g.csp_refine(cfg, cc, stack.numpy(), rows2, p2, tilts)
+    out, sc = g.sva_align(cfg_for(n, search_mode=1, global_step=20.0), vols.numpy(), wedges, synth.perturb_poses(poses, 3.0, 1.0))
+    r2, q2, t2 = g.csp_refine(cfg, cc, stack.numpy(), rows2, p2, tilts)
+    assert np.array_equal(r1, r2) and np.array_equal(q1, q2) and np.array_equal(t1, t2)
+    assert not np.array_equal(q1, p2) and sc.min() > 0.8
+    g.close()
+
+
+@pytest.mark.gpu
 def test_gpu_alignment_errors_are_loud():
     from pyp_amd import host, lib
     vol, vols, poses, wedges = synth.make_subtomograms(32, 2, snr=0.5)
