@@ -1,7 +1,8 @@
 // dropin_common.h — what the compiled drop-in executables (bin/refine3d, bin/reconstruct3d) share: the here-doc answers,
 // the `.cistem` table codec (src/pyp/inout/metadata/cistem_star_file.py:596-628, :694-776), the MRC header
 // (src/pyp/inout/image/mrc.py:74-116), the hand-over to the Python implementation, the per-GPU lock and the three-stage
-// stream (reader -> uploader -> compute) that moves a particle range from the stack file into device memory.
+// stream (reader -> uploader -> compute) that moves a particle range from the stack file into device memory, the loop that consumes
+// it, and the start-up thread of the one-shot programs.  The stream's plan is dropin_plan.h.
 //
 // No HIP in here: the executables use the C ABI only (include/ppm.h).
 #pragma once
@@ -30,6 +31,7 @@
 #include <vector>
 
 #include "../../include/ppm.h"
+#include "dropin_plan.h"
 
 extern char **environ;
 
@@ -49,10 +51,42 @@ inline std::string self_dir() {
     return p == std::string::npos ? "." : s.substr(0, p);
 }
 
+// what PYP's log scan looks for: every failure is reported on a line that says ERROR
+inline std::string error_line(const std::string &msg) { return msg.find("ERROR") != std::string::npos ? msg : "ERROR: " + msg; }
 [[noreturn]] inline void die(const std::string &msg) {
-    printf("%s\n", msg.find("ERROR") != std::string::npos ? msg.c_str() : ("ERROR: " + msg).c_str());
+    printf("%s\n", error_line(msg).c_str());
     fflush(stdout);
-    _exit(1);          // no destructors: helper threads may still be inside the library
+    _exit(1);          // no destructors: the library's reader pool is parked, not gone
+}
+inline int device_index() { const char *e = getenv("PPM_DEVICE"); return e ? atoi(e) : 0; }
+
+// all of [off, off + n) of a file, or false
+inline bool read_fully(int fd, void *p, size_t n, size_t off) {
+    for (size_t done = 0; done < n;) {
+        const ssize_t r = pread(fd, (char *)p + done, n - done, (off_t)(off + done));
+        if (r <= 0) return false;
+        done += (size_t)r;
+    }
+    return true;
+}
+inline bool write_fully(int fd, const void *p, size_t n, size_t off) {
+    for (size_t done = 0; done < n;) {
+        const ssize_t w = pwrite(fd, (const char *)p + done, std::min(n - done, (size_t)64 << 20), (off_t)(off + done));
+        if (w <= 0) return false;
+        done += (size_t)w;
+    }
+    return true;
+}
+// a file that is either complete or absent: fill(fd) writes it under a temporary name, renamed when fill says it is whole
+template <typename Fill> inline bool write_then_rename(const std::string &path, Fill fill) {
+    const std::string tmp = path + ".tmp" + std::to_string((long)getpid());
+    const int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) return false;
+    const bool ok = fill(fd);
+    close(fd);
+    if (ok && rename(tmp.c_str(), path.c_str()) == 0) return true;
+    unlink(tmp.c_str());
+    return false;
 }
 
 // Hand the call to the Python implementation (bin/<prog>.py) with the same stdin, as a CHILD process whose exit status becomes
@@ -62,15 +96,7 @@ inline std::string self_dir() {
 [[noreturn]] inline void hand_to_python(const char *script_name, const std::string &input) {
     fflush(stdout);
     int fd = memfd_create("dropin_stdin", 0);
-    if (fd >= 0) {
-        size_t done = 0;
-        while (done < input.size()) {
-            ssize_t w = write(fd, input.data() + done, input.size() - done);
-            if (w <= 0) break;
-            done += (size_t)w;
-        }
-        lseek(fd, 0, SEEK_SET);
-    }
+    if (fd >= 0) (void)write_fully(fd, input.data(), input.size(), 0);          // pwrite: the child reads from the start
     const std::string script = self_dir() + "/" + script_name;
     const char *py = getenv("PPM_PYTHON");
     const bool by_path = !(py && *py);
@@ -140,31 +166,40 @@ static const long long kCodes[32] = { 1, 4, 4194304, 8388608, 8, 16, 32, 64, 128
                                       524288, 1048576, 2097152, 8589934592LL, 17179869184LL, 20, 15, 35, 70, 55, 11, 121 };
 static const int kTypes[32] = { 9, 3, 3, 3, 3, 3, 3, 3, 3, 3, 2, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 2, 2, 2, 2, 2, 3, 3 };
 
+enum { kCistemHead = 8 + 9 * 32 };
+// the head of a .cistem file: column and row counts, then code and type of each column - the 32 standard columns in file order, or false
+inline bool cistem_head_is_standard(const unsigned char *b, int32_t &nrows) {
+    int32_t ncols;
+    memcpy(&ncols, b, 4); memcpy(&nrows, b + 4, 4);
+    if (ncols != 32 || nrows <= 0) return false;
+    for (int c = 0; c < 32; c++) {
+        int64_t code;
+        memcpy(&code, b + 8 + 9 * c, 8);
+        if (code != kCodes[c] || (int8_t)b[8 + 9 * c + 8] != kTypes[c]) return false;
+    }
+    return true;
+}
+// the cheap part of read_cistem's test
+inline bool cistem_is_standard(const std::string &path) {
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) return false;
+    unsigned char b[kCistemHead]; int32_t nrows;
+    const bool got = read_fully(fd, b, sizeof b, 0);
+    close(fd);
+    return got && cistem_head_is_standard(b, nrows);
+}
 // rows of a .cistem file as doubles (what Parameters.get_data() holds); false = not the plain standard layout (-> Python)
 inline bool read_cistem(const std::string &path, std::vector<double> &rows, long &n) {
-    int fd = open(path.c_str(), O_RDONLY);
+    const int fd = open(path.c_str(), O_RDONLY);
     if (fd < 0) return false;
     struct stat st;
-    if (fstat(fd, &st) != 0 || st.st_size < 8) { close(fd); return false; }
-    std::vector<unsigned char> buf((size_t)st.st_size);
-    size_t done = 0;
-    while (done < buf.size()) {
-        ssize_t r = pread(fd, buf.data() + done, buf.size() - done, (off_t)done);
-        if (r <= 0) { close(fd); return false; }
-        done += (size_t)r;
-    }
+    std::vector<unsigned char> buf;
+    bool ok = fstat(fd, &st) == 0 && st.st_size >= (off_t)kCistemHead;
+    if (ok) { buf.resize((size_t)st.st_size); ok = read_fully(fd, buf.data(), buf.size(), 0); }
     close(fd);
-    int32_t ncols, nrows;
-    memcpy(&ncols, buf.data(), 4); memcpy(&nrows, buf.data() + 4, 4);
-    if (ncols != 32 || nrows <= 0) return false;
-    size_t pos = 8;
-    if (buf.size() < pos + 9u * 32u) return false;
-    for (int c = 0; c < 32; c++) {
-        int64_t code; int8_t ty;
-        memcpy(&code, buf.data() + pos, 8); ty = (int8_t)buf[pos + 8]; pos += 9;
-        if (code != kCodes[c] || ty != kTypes[c]) return false;
-    }
-    if (buf.size() - pos < (size_t)nrows * 128u) return false;
+    int32_t nrows;
+    const size_t pos = kCistemHead;
+    if (!ok || !cistem_head_is_standard(buf.data(), nrows) || buf.size() - pos < (size_t)nrows * 128u) return false;
     n = nrows;
     rows.resize((size_t)nrows * 32);
     const unsigned char *p = buf.data() + pos;
@@ -182,7 +217,7 @@ inline bool read_cistem(const std::string &path, std::vector<double> &rows, long
 // the same table written back (pyp_amd/formats/cistem.py:write_parameters; the reference's writer, cistem_star_file.py:694-776):
 // integers are the double cast the way numpy's astype does it (truncation toward zero); under a temporary name, renamed when complete
 inline bool write_cistem(const std::string &path, const double *rows, long n) {
-    std::vector<unsigned char> buf(8 + 9 * 32 + (size_t)n * 128);
+    std::vector<unsigned char> buf(kCistemHead + (size_t)n * 128);
     const int32_t ncols = 32, nrows = (int32_t)n;
     memcpy(buf.data(), &ncols, 4); memcpy(buf.data() + 4, &nrows, 4);
     size_t pos = 8;
@@ -195,37 +230,7 @@ inline bool write_cistem(const std::string &path, const double *rows, long n) {
             else if (kTypes[c] == 2) { const int32_t q = (int32_t)v; memcpy(p, &q, 4); }
             else { const uint32_t q = (uint32_t)(long long)v; memcpy(p, &q, 4); }
         }
-    const std::string tmp = path + ".tmp" + std::to_string((long)getpid());
-    int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
-    if (fd < 0) return false;
-    size_t done = 0;
-    while (done < buf.size()) {
-        ssize_t w = write(fd, buf.data() + done, buf.size() - done);
-        if (w <= 0) { close(fd); unlink(tmp.c_str()); return false; }
-        done += (size_t)w;
-    }
-    close(fd);
-    if (rename(tmp.c_str(), path.c_str()) != 0) { unlink(tmp.c_str()); return false; }
-    return true;
-}
-
-// the cheap part of read_cistem's test: 32 standard columns in file order
-inline bool cistem_is_standard(const std::string &path) {
-    int fd = open(path.c_str(), O_RDONLY);
-    if (fd < 0) return false;
-    unsigned char b[8 + 9 * 32];
-    const bool got = pread(fd, b, sizeof b, 0) == (ssize_t)sizeof b;
-    close(fd);
-    if (!got) return false;
-    int32_t ncols, nrows;
-    memcpy(&ncols, b, 4); memcpy(&nrows, b + 4, 4);
-    if (ncols != 32 || nrows <= 0) return false;
-    for (int c = 0; c < 32; c++) {
-        int64_t code;
-        memcpy(&code, b + 8 + 9 * c, 8);
-        if (code != kCodes[c] || (int8_t)b[8 + 9 * c + 8] != kTypes[c]) return false;
-    }
-    return true;
+    return write_then_rename(path, [&](int fd) { return write_fully(fd, buf.data(), buf.size(), 0); });
 }
 
 struct MrcHead { int nx, ny, nz, mode; long offset; };
@@ -260,9 +265,42 @@ inline int gpu_lock(int dev) {
 }
 inline void gpu_unlock(int fd) { if (fd >= 0) { flock(fd, LOCK_UN); close(fd); } }
 
+struct Fail { std::string msg; };           // an ERROR the caller must see: one-shot -> die(), server -> status 1 + the text
+
+// ---- what a reconstruct3d and a refine3d call share: a range first..last of POSITION_IN_STACK over a stack of square float32 images
+enum { COL_POS = 0 };                       // POSITION_IN_STACK, 1-based
+struct RangeJob {
+    std::vector<std::string> a;             // the answers
+    std::string stack, params, symmetry;
+    long ifirst = 0, ilast = 0, n = 0; double px = 0; bool contiguous = true;
+    MrcHead mh{}; int box = 0; size_t sec = 0;              // sec: bytes of one image
+    std::vector<double> rin;                                // the n rows of the range, 32 columns each
+    double pos(long i) const { return rin[(size_t)i * 32 + COL_POS]; }
+    long long img_off(long i) const { return mh.offset + (long long)((long)pos(i) - 1) * (long long)sec; }     // image i of the range in the stack file
+};
+// the rows of `params` whose position lies in first..last -> rin, n, contiguous; every position must be in the stack; throws Fail
+inline void select_rows(RangeJob &j) {
+    std::vector<double> rows; long nrows = 0;
+    if (!read_cistem(j.params, rows, nrows)) throw Fail{ "ERROR: " + j.params + ": binary file is broken" };
+    j.rin.clear();
+    for (long i = 0; i < nrows; i++) {
+        const double pos = rows[(size_t)i * 32 + COL_POS];
+        if (pos >= j.ifirst && pos <= j.ilast) j.rin.insert(j.rin.end(), rows.begin() + (size_t)i * 32, rows.begin() + (size_t)(i + 1) * 32);
+    }
+    const long n = j.n = (long)(j.rin.size() / 32);
+    if (n == 0) throw Fail{ "ERROR: no rows with POSITION_IN_STACK in " + std::to_string(j.ifirst) + ".." + std::to_string(j.ilast) };
+    j.contiguous = true;
+    double pmax = 0, pmin = 1e300;
+    for (long i = 0; i < n; i++) {
+        pmax = std::max(pmax, j.pos(i)); pmin = std::min(pmin, j.pos(i));
+        if (i && j.pos(i) != j.pos(i - 1) + 1) j.contiguous = false;
+    }
+    if (pmax > j.mh.nz || pmin < 1) throw Fail{ "ERROR: " + j.stack + ": stack has " + std::to_string(j.mh.nz) + " images, rows ask for " + std::to_string((long)pmax) };
+}
+
 // ---- the three-stage stream: reader (ppm_host_read into page-locked buffers) -> uploader (ppm_device_upload into one of two
-// device buffers) -> the caller's compute on the other.  `stop` ends every wait: a stage that fails posts an error item, the
-// consumer calls abort(), and no thread is left blocked on a buffer that will never come back (a failed upload used to leave the
+// device buffers) -> the caller's compute on the other (consume()).  `stop` ends every wait: a stage that fails posts an error item,
+// the consumer calls abort(), and no thread is left blocked on a buffer that will never come back (a failed upload used to leave the
 // reader waiting for its page-locked buffer for ever).
 struct Stream {
     struct Item { long lo, hi; int slot; int err; };
@@ -273,15 +311,13 @@ struct Stream {
     void *pinned[3] = { nullptr, nullptr, nullptr }, *dbuf[2] = { nullptr, nullptr };
     void *resident = nullptr;                           // set: one device buffer holds the whole range (n x sec bytes; the resident server's
                                                         // stack cache) - chunks are uploaded to their final place, nothing is recycled
-    long n = 0, chunk = 1, group = 1; size_t sec = 0; int npin = 1, ndev = 1, nread = 8, fd = -1;
-    bool contiguous = true;
-    std::function<long long(long)> img_off;             // byte offset of image i of the range in the stack file
     std::function<bool(int)> wait_pinned;               // blocks until pinned[slot] has been page-locked (start-up thread); false = start-up failed
+    StreamPlan p; const RangeJob *j = nullptr; int fd = -1;
     double t_read = 0, t_up = 0, w_pin = 0, w_dev = 0;
     std::string err;
     std::thread reader_t, uploader_t;
 
-    template <typename Pred> bool wait_for(Pred p) { std::unique_lock<std::mutex> lk(m); cv.wait(lk, [&] { return stop.load() || p(); }); return !stop.load(); }
+    template <typename Pred> bool wait_for(Pred q) { std::unique_lock<std::mutex> lk(m); cv.wait(lk, [&] { return stop.load() || q(); }); return !stop.load(); }
     void post(std::deque<Item> &q, const Item &it) { { std::lock_guard<std::mutex> lk(m); q.push_back(it); } cv.notify_all(); }
     bool take(std::deque<Item> &q, Item &it) {
         std::unique_lock<std::mutex> lk(m);
@@ -292,21 +328,27 @@ struct Stream {
     }
     void fail(const std::string &msg) { { std::lock_guard<std::mutex> lk(m); if (err.empty()) err = msg; } post(ready, { 0, 0, 0, 1 }); }
     void abort() { stop = true; { std::lock_guard<std::mutex> lk(m); } cv.notify_all(); }
+    std::string error() { std::lock_guard<std::mutex> lk(m); return err; }
 
-    void start() {
+    // the rows of `job` (which outlives the stream) cut by `plan`, from job.stack; false = the stack file cannot be opened
+    bool start(const StreamPlan &plan, const RangeJob &job) {
+        p = plan; j = &job;
+        fd = open(job.stack.c_str(), O_RDONLY);
+        if (fd < 0) return false;
         reader_t = std::thread([this] {
-            for (long k = 0, lo = 0; lo < n; k++, lo += chunk) {
-                const long hi = std::min(lo + chunk, n); const int slot = (int)(k % npin);
+            const long n = j->n; const size_t sec = j->sec;
+            for (long k = 0, lo = 0; lo < n; k++, lo += p.chunk) {
+                const long hi = std::min(lo + p.chunk, n); const int slot = (int)(k % p.npin);
                 auto ta = Clock::now();
                 if (!wait_for([&] { return pin_free[slot]; })) return;
                 { std::lock_guard<std::mutex> lk(m); pin_free[slot] = false; }
                 if (wait_pinned && !wait_pinned(slot)) { fail("ERROR: page-locked staging memory could not be prepared"); return; }
                 auto tb = Clock::now();
-                if (contiguous) {
-                    if (ppm_host_read(fd, img_off(lo), pinned[slot], (size_t)(hi - lo) * sec, nread) != 0) { fail(std::string("ERROR: reading the particle stack failed: ") + ppm_last_error()); return; }
+                if (j->contiguous) {
+                    if (ppm_host_read(fd, j->img_off(lo), pinned[slot], (size_t)(hi - lo) * sec, p.nread) != 0) { fail(std::string("ERROR: reading the particle stack failed: ") + ppm_last_error()); return; }
                 } else {
                     for (long i = lo; i < hi; i++)                                                 // scattered rows: image by image
-                        if (ppm_host_read(fd, img_off(i), (char *)pinned[slot] + (size_t)(i - lo) * sec, sec, 1) != 0) { fail(std::string("ERROR: reading the particle stack failed: ") + ppm_last_error()); return; }
+                        if (ppm_host_read(fd, j->img_off(i), (char *)pinned[slot] + (size_t)(i - lo) * sec, sec, 1) != 0) { fail(std::string("ERROR: reading the particle stack failed: ") + ppm_last_error()); return; }
                 }
                 w_pin += secs(ta, tb); t_read += since(tb);
                 post(filled, { lo, hi, slot, 0 });
@@ -314,13 +356,14 @@ struct Stream {
             post(filled, { -1, -1, 0, 0 });
         });
         uploader_t = std::thread([this] {
+            const size_t sec = j->sec; const long group = p.group, chunk = p.chunk;
             long k = 0, glo = 0;
             const char *tf = getenv("PPM_TEST_FAIL_UPLOAD");           // test hook: the k-th upload (1-based) fails like a device error would
             const long fail_at = tf ? atol(tf) : 0;
             for (;;) {
                 Item it;
                 if (!take(filled, it) || it.lo < 0) return;
-                const int dslot = (int)((k / group) % ndev); const long part = k % group;
+                const int dslot = (int)((k / group) % p.ndev); const long part = k % group;
                 auto ta = Clock::now();
                 if (part == 0) {
                     if (!resident) {
@@ -339,20 +382,97 @@ struct Stream {
                 }
                 { std::lock_guard<std::mutex> lk(m); pin_free[it.slot] = true; } cv.notify_all();
                 w_dev += secs(ta, tb); t_up += since(tb);
-                if (part == group - 1 || it.hi == n) post(ready, { glo, it.hi, dslot, 0 });
+                if (part == group - 1 || it.hi == j->n) post(ready, { glo, it.hi, dslot, 0 });
                 k++;
             }
         });
+        return true;
     }
     // next group of uploaded images: [lo, hi) of the range in dbuf[slot]; false = a stage failed (err says why; the stream is aborted)
     bool next(Item &it) {
         if (!take(ready, it) || it.err) { abort(); return false; }
         return true;
     }
-    void *group_ptr(const Item &it) const { return resident ? (void *)((char *)resident + (size_t)it.lo * sec) : dbuf[it.slot]; }
+    void *group_ptr(const Item &it) const { return resident ? (void *)((char *)resident + (size_t)it.lo * j->sec) : dbuf[it.slot]; }
     void release(int dslot) { if (resident) return; { std::lock_guard<std::mutex> lk(m); dev_free[dslot] = true; } cv.notify_all(); }
-    void join() { if (reader_t.joinable()) reader_t.join(); if (uploader_t.joinable()) uploader_t.join(); }
+    // both threads joined (they end by themselves once the range is through, or at once after abort()), the file closed, the device buffers freed
+    void finish() {
+        if (reader_t.joinable()) reader_t.join();
+        if (uploader_t.joinable()) uploader_t.join();
+        if (fd >= 0) close(fd);
+        fd = -1;
+        for (void *&d : dbuf) { if (d) ppm_device_free(d); d = nullptr; }
+    }
 };
+
+// The consumer of a started stream: use(device pointer, lo, hi) runs the library call over each group [lo, hi) of the range and returns
+// its status.  `first` runs once, when the first group has arrived or failed to (refine3d waits there for its reference, which is
+// prepared while the first images arrive); false ends the loop.  err: empty, or why a stage, `first` or `use` failed - the stream is
+// aborted then, and finish() returns promptly.
+struct Consumed { std::string err; double t_comp = 0, w_data = 0; long ncalls = 0; };
+using Use = std::function<int(void *, long, long)>;
+inline Consumed consume(Stream &st, const char *prog, const Use &use, const std::function<bool()> &first = nullptr) {
+    Consumed c;
+    for (long lo = 0; lo < st.j->n && c.err.empty();) {
+        auto ta = Clock::now();
+        Stream::Item it;
+        const bool got = st.next(it);
+        if (lo == 0 && first && !first()) c.err = std::string("ERROR: ") + prog + ": the start-up failed";
+        else if (!got) { c.err = st.error(); if (c.err.empty()) c.err = std::string("ERROR: ") + prog + ": reading or uploading the particle stack failed"; }
+        else {
+            auto tb = Clock::now();
+            if (use(st.group_ptr(it), it.lo, it.hi) != 0) c.err = error_line(ppm_last_error());
+            else { st.release(it.slot); c.w_data += secs(ta, tb); c.t_comp += since(tb); c.ncalls++; lo = it.hi; }
+        }
+    }
+    if (!c.err.empty()) st.abort();
+    return c;
+}
+
+// ---- the start-up of a one-shot program, in a thread of its own while the parameter file is read: the context (ppm_init), then
+// `after_init` (reconstruct3d's accumulators; false = it failed), then the page-locked staging buffers one by one, so that the reader
+// starts on the first while the others are still being locked.  Never leave the process in the middle of it: finish() (and the
+// destructor) wait for the thread wherever it is.
+struct StartUp {
+    std::mutex m; std::condition_variable cv;
+    int stage = 0; std::string err;                     // 1 = device ready, 2 + k = pinned[k] ready, 99 = failed (err says why)
+    std::atomic<int> want_pinned{3};                    // the stream's plan may need fewer than three
+    double init_s = 0, ready_s = 0;                     // context / after_init done, seconds after the start
+    std::thread t;
+    StartUp(int dev, size_t pin_bytes, void **pinned, std::function<bool()> after_init = nullptr) {
+        t = std::thread([=] {
+            const auto t0 = Clock::now();
+            if (ppm_init(dev) != 0) return reach(99);
+            init_s = since(t0);
+            if (after_init && !after_init()) return reach(99);
+            ready_s = since(t0);
+            reach(1);
+            for (int k = 0; k < 3 && k < want_pinned.load(); k++) {
+                pinned[k] = ppm_host_alloc(pin_bytes);
+                if (!pinned[k]) return reach(99);
+                reach(2 + k);
+            }
+        });
+    }
+    void reach(int s) {
+        { std::lock_guard<std::mutex> lk(m); stage = s; if (s == 99) { const char *e = ppm_last_error(); err = e && *e ? e : "ERROR: device start-up failed"; } }
+        cv.notify_all();
+    }
+    bool wait_stage(int s) { std::unique_lock<std::mutex> lk(m); cv.wait(lk, [&] { return stage >= s; }); return stage != 99; }
+    bool wait_device() { return wait_stage(1); }
+    bool wait_pinned(int slot) { return wait_stage(2 + slot); }
+    std::string error() { std::lock_guard<std::mutex> lk(m); return err; }
+    void finish() { wait_device(); if (t.joinable()) t.join(); }
+    ~StartUp() { finish(); }
+};
+// The one way out of a one-shot program after an error: the stream is ended and joined, the start-up and the program's helper thread
+// have run to their end (none of them is left inside the library), then die().
+[[noreturn]] inline void leave(Stream &st, StartUp &up, std::thread *helper, const std::string &msg) {
+    st.abort(); st.finish();
+    up.finish();
+    if (helper && helper->joinable()) helper->join();
+    die(msg);
+}
 
 
 // ---- text the executable prints: straight to stdout in a one-shot process, collected and sent back by the resident server
@@ -367,8 +487,6 @@ struct Out {
         if (n > 0) sink->append(buf, std::min((size_t)n, sizeof buf - 1));
     }
 };
-struct Fail { std::string msg; };           // an ERROR the caller must see: one-shot -> die(), server -> status 1 + the text
-
 // identity of a file's contents for the resident caches: device, inode, size, modification time (ns)
 struct FileId {
     unsigned long long dev = 0, ino = 0, size = 0; long long mtime_ns = 0;
@@ -383,13 +501,11 @@ inline bool file_id(const std::string &path, FileId &id) {
 }
 
 // ---- the reconstruct3d call (39 answers; frealign.py:1780-1824), parsed and prepared up to the point where the GPU is needed
-enum { RC_POS = 0, RC_DF1 = 6, RC_DF2 = 7, RC_OCC = 11, RC_SCORE = 14 };
-struct ReconJob {
-    std::vector<std::string> a;
-    std::string stack, params, gstats, symmetry, res_file, dump1, dump2;
-    long ifirst = 0, ilast = 0, n = 0; double px = 0; bool crop = false, contiguous = true, have_gs = false;
-    MrcHead mh{}; int box = 0; size_t sec = 0;
-    std::vector<double> rin; ppm_recon_cfg rc{};
+enum { RC_DF1 = 6, RC_DF2 = 7, RC_OCC = 11, RC_SCORE = 14 };
+struct ReconJob : RangeJob {
+    std::string gstats, res_file, dump1, dump2;
+    bool crop = false, have_gs = false;
+    ppm_recon_cfg rc{};
 };
 // false = outside the compiled fast path (the Python implementation owns everything else, its refusals included)
 inline bool recon_parse(const std::string &input, ReconJob &j) {
@@ -430,26 +546,11 @@ inline bool recon_parse(const std::string &input, ReconJob &j) {
 // the rows of the range, the score regression and the mean score (pyp_amd/surface/cli.py:reconstruct3d_main); throws Fail
 inline void recon_rows(ReconJob &j) {
     const bool adjust = j.rc.score_average != 0.f;
-    std::vector<double> rows; long nrows = 0;
-    if (!read_cistem(j.params, rows, nrows)) throw Fail{ "ERROR: " + j.params + ": binary file is broken" };
     std::vector<double> gs; long ngs = 0;
     if (j.have_gs && !read_cistem(j.gstats, gs, ngs)) throw Fail{ "ERROR: " + j.gstats + ": binary file is broken" };
+    select_rows(j);
     std::vector<double> &rin = j.rin;
-    rin.clear();
-    for (long i = 0; i < nrows; i++) {
-        const double pos = rows[(size_t)i * 32 + RC_POS];
-        if (pos >= j.ifirst && pos <= j.ilast) rin.insert(rin.end(), rows.begin() + (size_t)i * 32, rows.begin() + (size_t)(i + 1) * 32);
-    }
-    const long n = j.n = (long)(rin.size() / 32);
-    if (n == 0) throw Fail{ "ERROR: no rows with POSITION_IN_STACK in " + std::to_string(j.ifirst) + ".." + std::to_string(j.ilast) };
-    j.contiguous = true;
-    double pmax = 0, pmin = 1e300;
-    for (long i = 0; i < n; i++) {
-        const double pos = rin[(size_t)i * 32 + RC_POS];
-        pmax = std::max(pmax, pos); pmin = std::min(pmin, pos);
-        if (i && pos != rin[(size_t)(i - 1) * 32 + RC_POS] + 1) j.contiguous = false;
-    }
-    if (pmax > j.mh.nz || pmin < 1) throw Fail{ "ERROR: " + j.stack + ": stack has " + std::to_string(j.mh.nz) + " images, rows ask for " + std::to_string((long)pmax) };
+    const long n = j.n;
     long nused = 0;
     for (long i = 0; i < n; i++) nused += rin[(size_t)i * 32 + RC_OCC] > 0;
     if (adjust && nused > 10) {
@@ -481,38 +582,33 @@ inline void recon_banner(const ReconJob &j, Out &o, const char *how) {
     if (j.crop) o.print("NOTE: crop = yes has no effect: the full box is transformed\n");
 }
 
-inline int write_dump_file(const std::string &path, int box, float pixel, long long count, const float *data, size_t nfloat) {
-    const std::string tmp = path + ".tmp" + std::to_string((long)getpid());
-    int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
-    if (fd < 0) return -1;
-    unsigned char head[24];
-    memcpy(head, "PPMDUMP1", 8); memcpy(head + 8, &box, 4); memcpy(head + 12, &pixel, 4); memcpy(head + 16, &count, 8);
-    const size_t bytes = nfloat * 4;
-    std::atomic<int> bad{0};
-    if (pwrite(fd, head, 24, 0) != 24 || ftruncate(fd, (off_t)(24 + bytes)) != 0) bad = 1;
-    std::vector<std::thread> th;
-    for (int k = 0; k < 4 && !bad; k++)
-        th.emplace_back([&, k] {
-            size_t a = bytes * k / 4, e = bytes * (k + 1) / 4;
-            while (a < e) {
-                ssize_t w = pwrite(fd, (const char *)data + a, std::min(e - a, (size_t)64 << 20), (off_t)(24 + a));
-                if (w <= 0) { bad = 1; return; }
-                a += (size_t)w;
-            }
-        });
-    for (auto &t : th) t.join();
-    close(fd);
-    if (bad || rename(tmp.c_str(), path.c_str()) != 0) { unlink(tmp.c_str()); return -1; }
-    return 0;
+// a dump file, written in four pieces at once
+inline bool write_dump_file(const std::string &path, int box, float pixel, long long count, const float *data, size_t nfloat) {
+    return write_then_rename(path, [&](int fd) {
+        unsigned char head[24];
+        memcpy(head, "PPMDUMP1", 8); memcpy(head + 8, &box, 4); memcpy(head + 12, &pixel, 4); memcpy(head + 16, &count, 8);
+        const size_t bytes = nfloat * 4;
+        if (!write_fully(fd, head, 24, 0) || ftruncate(fd, (off_t)(24 + bytes)) != 0) return false;
+        std::atomic<bool> ok{true};
+        std::vector<std::thread> th;
+        for (size_t k = 0; k < 4; k++)
+            th.emplace_back([&, k] { const size_t a = bytes * k / 4, e = bytes * (k + 1) / 4; if (!write_fully(fd, (const char *)data + a, e - a, 24 + a)) ok = false; });
+        for (auto &t : th) t.join();
+        return ok.load();
+    });
 }
-// downloads the two half maps (into h_even / h_odd, each ppm_accum_floats / 2 floats) and writes dumps + the .res file; throws Fail
-inline void recon_outputs(const ReconJob &j, ppm_accum_t *acc, float *h_even, float *h_odd, long &c0, long &c1) {
+// downloads the two half maps and writes dumps + the .res file; throws Fail (std::bad_alloc: no memory for the maps).  Each half goes
+// into one of the stream's staging buffers when those are page-locked and large enough (a half map of 256^3 is 203 MB), else into plain memory
+inline void recon_outputs(const ReconJob &j, ppm_accum_t *acc, void *const pinned[3], size_t pin_bytes, long &c0, long &c1) {
     const size_t half = ppm_accum_floats(j.box) / 2;
+    std::vector<float> plain;
+    float *h_even = (float *)pinned[0], *h_odd = (float *)pinned[1];
+    if (!h_even || !h_odd || pin_bytes < half * sizeof(float)) { plain.resize(2 * half); h_even = plain.data(); h_odd = h_even + half; }
     if (ppm_accum_download_range(acc, h_even, 0, half) != 0 || ppm_accum_download_range(acc, h_odd, half, half) != 0) throw Fail{ ppm_last_error() };
     c0 = ppm_accum_count(acc, 0); c1 = ppm_accum_count(acc, 1);
-    int e1 = 0, e2 = 0;
-    std::thread w2([&] { e2 = write_dump_file(j.dump2, j.box, (float)j.px, c0, h_even, half); });                   // even keys -> map 2
-    e1 = write_dump_file(j.dump1, j.box, (float)j.px, c1, h_odd, half);                                            // odd keys  -> map 1
+    bool e1 = false, e2 = false;
+    std::thread w2([&] { e2 = !write_dump_file(j.dump2, j.box, (float)j.px, c0, h_even, half); });                  // even keys -> map 2
+    e1 = !write_dump_file(j.dump1, j.box, (float)j.px, c1, h_odd, half);                                           // odd keys  -> map 1
     w2.join();
     if (e1 || e2) { unlink(j.dump1.c_str()); unlink(j.dump2.c_str()); throw Fail{ "ERROR: reconstruct3d: could not write " + (e1 ? j.dump1 : j.dump2) }; }
     if (FILE *f = fopen(j.res_file.c_str(), "w")) {
@@ -528,13 +624,11 @@ inline void recon_footer(Out &o) {
 }
 
 // ---- the refine3d call (50 answers; frealign.py:3918-3994)
-enum { RF_POS = 0, RF_PSI = 1, RF_THETA = 2, RF_PHI = 3, RF_SHX = 4, RF_SHY = 5, RF_SCORE = 14 };
-struct RefineJob {
-    std::vector<std::string> a;
-    std::string stack, params, reference, out_params, out_changes, symmetry;
-    long ifirst = 0, ilast = 0, n = 0; double px = 0; int pad = 1; bool contiguous = true;
-    MrcHead mh{}; int box = 0; size_t sec = 0;
-    std::vector<double> rin; ppm_refine_cfg cfg{};
+enum { RF_PSI = 1, RF_THETA = 2, RF_PHI = 3, RF_SHX = 4, RF_SHY = 5, RF_SCORE = 14 };
+struct RefineJob : RangeJob {
+    std::string reference, out_params, out_changes;
+    int pad = 1;
+    ppm_refine_cfg cfg{};
 };
 inline bool refine_parse(const std::string &input, RefineJob &j) {
     j.a = read_answers(input);
@@ -576,25 +670,6 @@ inline bool refine_parse(const std::string &input, RefineJob &j) {
     snprintf(cfg.symmetry, sizeof cfg.symmetry, "%.7s", j.symmetry.c_str());
     return true;
 }
-inline void refine_rows(RefineJob &j) {
-    std::vector<double> rows; long nrows = 0;
-    if (!read_cistem(j.params, rows, nrows)) throw Fail{ "ERROR: " + j.params + ": binary file is broken" };
-    j.rin.clear();
-    for (long i = 0; i < nrows; i++) {
-        const double pos = rows[(size_t)i * 32 + RF_POS];
-        if (pos >= j.ifirst && pos <= j.ilast) j.rin.insert(j.rin.end(), rows.begin() + (size_t)i * 32, rows.begin() + (size_t)(i + 1) * 32);
-    }
-    const long n = j.n = (long)(j.rin.size() / 32);
-    if (n == 0) throw Fail{ "ERROR: no rows with POSITION_IN_STACK in " + std::to_string(j.ifirst) + ".." + std::to_string(j.ilast) };
-    j.contiguous = true;
-    double pmax = 0, pmin = 1e300;
-    for (long i = 0; i < n; i++) {
-        const double pos = j.rin[(size_t)i * 32 + RF_POS];
-        pmax = std::max(pmax, pos); pmin = std::min(pmin, pos);
-        if (i && pos != j.rin[(size_t)(i - 1) * 32 + RF_POS] + 1) j.contiguous = false;
-    }
-    if (pmax > j.mh.nz || pmin < 1) throw Fail{ "ERROR: " + j.stack + ": stack has " + std::to_string(j.mh.nz) + " images, rows ask for " + std::to_string((long)pmax) };
-}
 inline void refine_banner(const RefineJob &j, Out &o, const char *how) {
     static const char *kNames[50] = { "stack", "input_params", "global_stats", "reference", "statistics", "use_statistics", "use_priors", "match_out", "output_params",
         "output_changes", "symmetry", "first", "last", "fraction", "pixel_size", "molecular_mass", "inner_radius", "outer_radius", "res_low", "res_high",
@@ -609,16 +684,11 @@ inline bool read_volume(const std::string &path, int n, std::vector<float> &vol)
     MrcHead h;
     if (!read_mrc_head(path, h) || h.mode != 2 || h.nx != n || h.ny != n || h.nz != n) return false;
     vol.resize((size_t)n * n * n);
-    int fd = open(path.c_str(), O_RDONLY);
+    const int fd = open(path.c_str(), O_RDONLY);
     if (fd < 0) return false;
-    size_t done = 0, want = vol.size() * 4;
-    while (done < want) {
-        ssize_t r = pread(fd, (char *)vol.data() + done, want - done, (off_t)(h.offset + done));
-        if (r <= 0) { close(fd); return false; }
-        done += (size_t)r;
-    }
+    const bool ok = read_fully(fd, vol.data(), vol.size() * 4, (size_t)h.offset);
     close(fd);
-    return true;
+    return ok;
 }
 // output tables + the log's table of the first rows; throws Fail
 inline void refine_outputs(const RefineJob &j, const std::vector<double> &rout, const std::string &note, Out &o, double &mean_score) {
@@ -627,7 +697,7 @@ inline void refine_outputs(const RefineJob &j, const std::vector<double> &rout, 
     std::vector<double> changes((size_t)n * 32);
     for (long i = 0; i < n; i++) {
         for (int c = 0; c < 32; c++) changes[(size_t)i * 32 + c] = rout[(size_t)i * 32 + c] - j.rin[(size_t)i * 32 + c];
-        changes[(size_t)i * 32 + RF_POS] = j.rin[(size_t)i * 32 + RF_POS];
+        changes[(size_t)i * 32 + COL_POS] = j.rin[(size_t)i * 32 + COL_POS];
     }
     if (!write_cistem(j.out_params, rout.data(), n)) throw Fail{ "ERROR: refine3d: could not write " + j.out_params };
     if (j.out_changes != "/dev/null" && j.out_changes != "null") {
@@ -639,7 +709,7 @@ inline void refine_outputs(const RefineJob &j, const std::vector<double> &rout, 
     for (long i = 0; i < n; i++) {
         const double *r = &rout[(size_t)i * 32];
         ssum += r[RF_SCORE];
-        if (i < 50) o.print("%7d%8.2f%8.2f%8.2f%10.2f%10.2f%10.4f%9.4f\n", (int)r[RF_POS], r[RF_PSI], r[RF_THETA], r[RF_PHI], r[RF_SHX], r[RF_SHY], r[RF_SCORE], changes[(size_t)i * 32 + RF_SCORE]);
+        if (i < 50) o.print("%7d%8.2f%8.2f%8.2f%10.2f%10.2f%10.4f%9.4f\n", (int)r[COL_POS], r[RF_PSI], r[RF_THETA], r[RF_PHI], r[RF_SHX], r[RF_SHY], r[RF_SCORE], changes[(size_t)i * 32 + RF_SCORE]);
     }
     mean_score = (double)(ssum / n);
 }

@@ -15,9 +15,13 @@
 // One request at a time (the server IS the per-GPU lock for its clients; it also takes the advisory file lock while it computes, so
 // one-shot processes of the same node wait their turn).  It exits after PPM_STACK_CACHE_IDLE_S seconds without a request (default 600).
 //
-// Wire format (unix stream socket $PPM_LOCK_DIR/pyp_amd_gpu<dev>.sock, mode 0600), little-endian:
-//   request : "PPMS" u32 program (1 reconstruct3d, 2 refine3d, 8 statistics, 9 stop) u32 len cwd u32 len stdin
-//   reply   : i32 status (0 ok, 1 ERROR, -100 hand over to Python) u32 len text
+// Wire format (unix stream socket <server_dir()>/pyp_amd_gpu<dev>.u<uid>.sock, mode 0600), little-endian; a blob is u32 length + bytes
+// (at most 64 MB).  One Request and one Reply per connection, send_request / recv_request and send_reply / recv_reply on both sides:
+//   request : "PPMS", u32 program (1 reconstruct3d, 2 refine3d, 8 statistics, 9 stop), blob cwd, blob stdin, blob settings (the
+//             client's "umask=<octal>" and PPM_* variables, one name=value per line), blob build id (ppm_build_id() "/p" kProtocol)
+//   reply   : i32 status (0 ok, 1 ERROR, -100 hand over to Python, -101 the build id is not the server's), blob text
+// Programs 1 and 2 are served only to a client of the server's own build: any other gets -101, stops the server, starts its own
+// and asks again (run_through_server).  Statistics and stop are answered whatever the id says.
 #pragma once
 #include <poll.h>
 #include <sys/socket.h>
@@ -28,7 +32,9 @@
 
 namespace dropin {
 
-enum { kProgRecon = 1, kProgRefine = 2, kProgHello = 7, kProgStats = 8, kProgStop = 9, kHandOver = -100 };
+enum { kProgRecon = 1, kProgRefine = 2, kProgStats = 8, kProgStop = 9, kHandOver = -100, kMismatch = -101 };
+enum { kProtocol = 2 };                     // goes up with every change of the wire format or of what the server does with a request
+inline std::string build_id() { return std::string(ppm_build_id()) + "/p" + std::to_string((int)kProtocol); }
 
 // Where the server's socket, its guard lock and its log live: PPM_LOCK_DIR, else the user's runtime directory, else /tmp — the names carry
 // the user id, so two users of a node run a server each (the GPU lock file itself, pyp_amd_gpu<N>.lock, stays shared between them).
@@ -71,13 +77,16 @@ inline int connect_server(int dev) {
 }
 // What a request carries besides its input: the CLIENT's file-creation mask and its PPM_* settings (PPM_IO_THREADS, the kernels' knobs),
 // one "name=value" per line — a call served by the resident process behaves like the one-shot run the client would have made, whoever
-// started the server.  The server's own settings (cache size, idle limit, lock directory, device) are not the caller's to change.
+// started the server.  The server's own settings (cache size, idle limit, lock directory, device, and how its context waits for the
+// GPU: PPM_SYNC is read once, by ppm_init) are not the caller's to change.
 inline bool server_owned_setting(const std::string &name) {
-    return name.compare(0, 15, "PPM_STACK_CACHE") == 0 || name == "PPM_LOCK_DIR" || name == "PPM_DEVICE";
+    return name.compare(0, 15, "PPM_STACK_CACHE") == 0 || name == "PPM_LOCK_DIR" || name == "PPM_DEVICE" || name == "PPM_SYNC";
 }
 inline std::string client_settings() {
     const mode_t m = umask(0); umask(m);
-    std::string s = "umask=" + std::to_string((unsigned)m) + "\n";
+    char mask[16];
+    snprintf(mask, sizeof mask, "umask=%o\n", (unsigned)m);
+    std::string s = mask;
     for (char **e = environ; e && *e; e++) {
         const std::string kv = *e;
         const size_t eq = kv.find('=');
@@ -105,7 +114,7 @@ struct RequestSettings {
             const size_t eq = kv.find('=');
             if (eq == std::string::npos) continue;
             const std::string k = kv.substr(0, eq), v = kv.substr(eq + 1);
-            if (k == "umask") { old_mask = umask((mode_t)(strtoul(v.c_str(), nullptr, 10) & 0777)); mask_set = true; }
+            if (k == "umask") { old_mask = umask((mode_t)(strtoul(v.c_str(), nullptr, 8) & 0777)); mask_set = true; }
             else if (k.compare(0, 4, "PPM_") == 0 && !server_owned_setting(k)) want.emplace_back(k, v);
         }
         for (const auto &k : mine) {
@@ -125,18 +134,30 @@ struct RequestSettings {
         if (mask_set) umask(old_mask);
     }
 };
+struct Request {
+    uint32_t prog = 0; std::string cwd, input, settings, build;
+    Request() {}
+    Request(int prog_, const std::string &input_) : prog((uint32_t)prog_), input(input_), settings(client_settings()), build(build_id()) {
+        char buf[4096];
+        if (getcwd(buf, sizeof buf)) cwd = buf;
+    }
+};
+struct Reply { int32_t status = 1; std::string text; };
+inline bool send_request(int fd, const Request &r) {
+    return write_all(fd, "PPMS", 4) && write_all(fd, &r.prog, 4) && send_blob(fd, r.cwd) && send_blob(fd, r.input) && send_blob(fd, r.settings) && send_blob(fd, r.build);
+}
+inline bool recv_request(int fd, Request &r) {
+    char magic[4];
+    return read_all(fd, magic, 4) && memcmp(magic, "PPMS", 4) == 0 && read_all(fd, &r.prog, 4) && recv_blob(fd, r.cwd) && recv_blob(fd, r.input) && recv_blob(fd, r.settings) && recv_blob(fd, r.build);
+}
+inline bool send_reply(int fd, const Reply &r) { return write_all(fd, &r.status, 4) && send_blob(fd, r.text); }
+inline bool recv_reply(int fd, Reply &r) { return read_all(fd, &r.status, 4) && recv_blob(fd, r.text); }
 // one request / reply; false = no server could be reached (the caller runs the call itself)
-inline bool server_call(int dev, int prog, const std::string &input, int &status, std::string &text) {
-    int fd = connect_server(dev);
+inline bool server_call(int dev, const Request &rq, Reply &rp) {
+    const int fd = connect_server(dev);
     if (fd < 0) return false;
-    char cwd[4096];
-    if (!getcwd(cwd, sizeof cwd)) { close(fd); return false; }
-    const uint32_t p = (uint32_t)prog;
-    bool ok = write_all(fd, "PPMS", 4) && write_all(fd, &p, 4) && send_blob(fd, cwd) && send_blob(fd, input) && send_blob(fd, client_settings());
-    int32_t st = 1;
-    ok = ok && read_all(fd, &st, 4) && recv_blob(fd, text);
+    const bool ok = !rq.cwd.empty() && send_request(fd, rq) && recv_reply(fd, rp);
     close(fd);
-    status = st;
     return ok;
 }
 // start bin/ppm_server for `dev` as a detached child (never an exec of this process) and wait until its socket answers
@@ -158,21 +179,21 @@ inline bool start_server(int dev, double wait_s = 20.0) {
     }
     return false;
 }
-// the client side of an executable: true = the call was served (status / text set); false = run it in this process
-inline bool run_through_server(int prog, const std::string &input, int &status, std::string &text) {
+// the client side of an executable: true = the call was served (rp set); false = run it in this process
+inline bool run_through_server(int prog, const std::string &input, Reply &rp) {
     const char *e = getenv("PPM_STACK_CACHE");
     if (!e || !*e || !strcmp(e, "0")) return false;
-    const int dev = getenv("PPM_DEVICE") ? atoi(getenv("PPM_DEVICE")) : 0;
-    // a server left over from an older build of the library (it answers with its own build id) is stopped and replaced
-    int hs = 0; std::string hello;
-    if (server_call(dev, kProgHello, "", hs, hello) && hello != ppm_build_id()) {
-        int st = 0; std::string t;
-        (void)server_call(dev, kProgStop, "", st, t);
+    const int dev = device_index();
+    const Request rq(prog, input);
+    bool ok = server_call(dev, rq, rp);
+    if (ok && rp.status == kMismatch) {             // a server left over from another build: stopped and replaced, the call asked once more
+        Reply bye;
+        (void)server_call(dev, Request(kProgStop, ""), bye);
         for (int i = 0; i < 250; i++) { int fd = connect_server(dev); if (fd < 0) break; close(fd); usleep(20000); }
+        ok = false;
     }
-    if (server_call(dev, prog, input, status, text)) return true;
-    if (!start_server(dev)) return false;
-    return server_call(dev, prog, input, status, text);
+    if (!ok) ok = start_server(dev) && server_call(dev, rq, rp);
+    return ok && rp.status != kMismatch;
 }
 
 // ---------------------------------------------------------------------------------------------- server side
@@ -185,6 +206,7 @@ struct Cache {
     std::vector<StackEntry> stacks; std::vector<RefEntry> refs;
     void *pinned[3] = { nullptr, nullptr, nullptr }; size_t pin_bytes = 0;
     long hits = 0, misses = 0, served = 0;
+    bool inited = false;                                // ppm_init has run (with the first request that needs the device)
     Clock::time_point t0 = Clock::now();
     double now() const { return since(t0); }
 
@@ -254,12 +276,12 @@ struct Cache {
 };
 
 // the particle range of a job in device memory: from the cache, or streamed from the file (and kept when it fits).  `use(ptr, lo, hi)`
-// is called for consecutive pieces [lo, hi) of the range with their device pointer; throws Fail.
-template <typename Job, typename Use>
-inline void with_stack(Cache &c, const Job &j, Out &o, long call_mb, long chunk_mb, Use use, const char *prog) {
+// is called for consecutive pieces [lo, hi) of the range with their device pointer and returns the library's status; throws Fail.
+// returns the seconds spent inside `use`
+inline double with_stack(Cache &c, const RangeJob &j, Out &o, long call_mb, long chunk_mb, const Use &use, const char *prog) {
     FileId id;
     if (!file_id(j.stack, id)) throw Fail{ std::string("ERROR: ") + prog + ": cannot stat " + j.stack };
-    const long pmin = (long)j.rin[RC_POS], pmax = (long)j.rin[(size_t)(j.n - 1) * 32 + RC_POS];
+    const long pmin = (long)j.pos(0), pmax = (long)j.pos(j.n - 1);
     const size_t sec = j.sec;
     const long per_call = std::max(1L, (long)(((size_t)call_mb << 20) / sec));
     if (j.contiguous) {
@@ -269,49 +291,28 @@ inline void with_stack(Cache &c, const Job &j, Out &o, long call_mb, long chunk_
             char *base = (char *)e->dptr + (size_t)(pmin - e->first) * sec;
             // resident data: calls as large as the library likes them (it chunks a call by itself)
             const long big = std::max(per_call, 1L << 17);
-            for (long lo = 0; lo < j.n; lo += big) { const long hi = std::min(j.n, lo + big); use(base + (size_t)lo * sec, lo, hi); }
-            return;
+            const auto tb = Clock::now();
+            for (long lo = 0; lo < j.n; lo += big) if (use(base + (size_t)lo * sec, lo, std::min(j.n, lo + big)) != 0) throw Fail{ ppm_last_error() };
+            return since(tb);
         }
     }
     c.misses++;
-    const size_t pin_bytes = std::min(std::max((size_t)16, ((size_t)chunk_mb << 20) / sec), (size_t)j.n) * sec;
+    const size_t pin_bytes = staging_bytes(j.n, sec, chunk_mb);
     if (!c.pin(pin_bytes)) throw Fail{ std::string("ERROR: ") + ppm_last_error() };
     Stream st;
     for (int k = 0; k < 3; k++) st.pinned[k] = c.pinned[k];
-    const long chunk = std::max(1L, std::min(j.n, (long)(pin_bytes / sec)));
-    const long nchunks = (j.n + chunk - 1) / chunk;
-    const long group = std::max(1L, std::min(nchunks, (long)(((size_t)call_mb << 20) / ((size_t)chunk * sec))));
-    st.n = j.n; st.chunk = chunk; st.group = group; st.sec = sec; st.contiguous = j.contiguous;
-    st.npin = (int)std::min(3L, nchunks); st.ndev = (int)std::min(2L, (nchunks + group - 1) / group);
-    st.nread = getenv("PPM_IO_THREADS") ? std::max(1, std::min(16, atoi(getenv("PPM_IO_THREADS")))) : 8;
-    void *resident = j.contiguous ? c.reserve(id, (size_t)j.n * sec) : nullptr;
-    st.resident = resident;
-    st.fd = open(j.stack.c_str(), O_RDONLY);
-    if (st.fd < 0) { if (resident) ppm_device_free(resident); throw Fail{ std::string("ERROR: ") + prog + ": cannot open " + j.stack }; }
-    const long long off0 = j.mh.offset;
-    const std::vector<double> &rin = j.rin;
-    st.img_off = [&rin, off0, sec](long i) { return off0 + (long long)((long)rin[(size_t)i * 32 + RC_POS] - 1) * (long long)sec; };
-    st.start();
-    std::string err;
-    try {
-        for (long lo = 0; lo < j.n;) {
-            Stream::Item it;
-            if (!st.next(it)) { err = !st.err.empty() ? st.err : std::string("ERROR: ") + prog + ": reading or uploading the particle stack failed"; break; }
-            use(st.group_ptr(it), it.lo, it.hi);
-            st.release(it.slot);
-            lo = it.hi;
-        }
-    } catch (const Fail &f) { err = f.msg; }
-    if (!err.empty()) st.abort();
-    st.join();
-    close(st.fd);
-    for (void *p : st.dbuf) if (p) ppm_device_free(p);
-    if (!err.empty()) { if (resident) ppm_device_free(resident); throw Fail{ err }; }
+    void *resident = st.resident = j.contiguous ? c.reserve(id, (size_t)j.n * sec) : nullptr;
+    Consumed done;
+    if (st.start(stream_plan(pin_bytes, j.n, sec, call_mb), j)) done = consume(st, prog, use);
+    else done.err = std::string("ERROR: ") + prog + ": cannot open " + j.stack;
+    st.finish();
+    if (!done.err.empty()) { if (resident) ppm_device_free(resident); throw Fail{ done.err }; }
     if (resident) {
         c.keep(id, pmin, j.n, j.box, resident, (size_t)j.n * sec);
         o.print("Stack: particles %ld..%ld uploaded and kept resident for the next call (%.1f GB of %.0f GB cached)\n", pmin, pmax, c.used / 1e9, c.budget / 1e9);
     } else o.print("Stack: streamed (not kept: %s)\n", j.contiguous ? "it does not fit the cache" : "the rows are not one contiguous range");
     o.print("Pipeline: reader: read %.2f s, waited for a buffer %.2f s; uploader: copied %.2f s, waited for a buffer %.2f s\n", st.t_read, st.w_pin, st.t_up, st.w_dev);
+    return done.t_comp;
 }
 
 inline int serve_reconstruct3d(Cache &c, const std::string &input, Out &o) {
@@ -324,20 +325,12 @@ inline int serve_reconstruct3d(Cache &c, const std::string &input, Out &o) {
     if (!acc) throw Fail{ ppm_last_error() };
     struct Guard { ppm_accum_t *a; ~Guard() { if (a) ppm_accum_destroy(a); } } guard{ acc };
     const auto t1 = Clock::now();
-    double t_comp = 0;
-    with_stack(c, j, o, 2048, 256, [&](void *ptr, long lo, long hi) {
-        const auto tb = Clock::now();
-        if (ppm_insert_batch(acc, &j.rc, ptr, 1, (int)(hi - lo), j.rin.data() + (size_t)lo * 32) != 0) throw Fail{ ppm_last_error() };
-        t_comp += since(tb);
+    const double t_comp = with_stack(c, j, o, 2048, 256, [&](void *ptr, long lo, long hi) {
+        return ppm_insert_batch(acc, &j.rc, ptr, 1, (int)(hi - lo), j.rin.data() + (size_t)lo * 32);
     }, "reconstruct3d");
     const auto t2 = Clock::now();
-    const size_t half = ppm_accum_floats(j.box) / 2;
-    std::vector<float> plain;
-    float *h_even, *h_odd;
-    if (c.pinned[0] && c.pinned[1] && c.pin_bytes >= half * sizeof(float)) { h_even = (float *)c.pinned[0]; h_odd = (float *)c.pinned[1]; }
-    else { plain.resize(2 * half); h_even = plain.data(); h_odd = h_even + half; }
     long c0 = 0, c1 = 0;
-    recon_outputs(j, acc, h_even, h_odd, c0, c1);
+    recon_outputs(j, acc, c.pinned, c.pin_bytes, c0, c1);
     o.print("\nInserted %ld of %ld particles in %.2f s\n", c0 + c1, j.n, since(t0));
     o.print("Timing: inputs %.2f s, particles %.2f s (insertion calls %.2f s), dumps %.2f s\n", secs(t0, t1), secs(t1, t2), t_comp, since(t2));
     recon_footer(o);
@@ -348,7 +341,7 @@ inline int serve_refine3d(Cache &c, const std::string &input, Out &o) {
     const auto t0 = Clock::now();
     RefineJob j;
     if (!refine_parse(input, j)) return kHandOver;
-    refine_rows(j);
+    select_rows(j);
     refine_banner(j, o, "native, resident server");
     FileId rid;
     if (!file_id(j.reference, rid)) throw Fail{ "ERROR: refine3d: cannot stat " + j.reference };
@@ -363,11 +356,8 @@ inline int serve_refine3d(Cache &c, const std::string &input, Out &o) {
     }
     const auto t1 = Clock::now();
     std::vector<double> rout((size_t)j.n * 32);
-    double t_comp = 0;
-    with_stack(c, j, o, 512, 64, [&](void *ptr, long lo, long hi) {
-        const auto tb = Clock::now();
-        if (ppm_refine_batch(ref, &j.cfg, ptr, 1, (int)(hi - lo), j.rin.data() + (size_t)lo * 32, rout.data() + (size_t)lo * 32) != 0) throw Fail{ ppm_last_error() };
-        t_comp += since(tb);
+    const double t_comp = with_stack(c, j, o, 512, 64, [&](void *ptr, long lo, long hi) {
+        return ppm_refine_batch(ref, &j.cfg, ptr, 1, (int)(hi - lo), j.rin.data() + (size_t)lo * 32, rout.data() + (size_t)lo * 32);
     }, "refine3d");
     const auto t2 = Clock::now();
     double mean = 0;
@@ -376,6 +366,45 @@ inline int serve_refine3d(Cache &c, const std::string &input, Out &o) {
     o.print("Timing: inputs + reference %.2f s, particles %.2f s (refinement calls %.2f s), outputs %.2f s\n", secs(t0, t1), secs(t1, t2), t_comp, since(t2));
     o.print("\nRefine3D: Normal termination\n\n");
     return 0;
+}
+
+// one request of a connected client -> its reply; leave: the server was asked to stop
+inline Reply serve_one(Cache &c, const Request &rq, bool &leave) {
+    Reply rp; rp.status = 0;
+    Out out; out.sink = &rp.text;
+    const bool recon = rq.prog == kProgRecon;
+    if (rq.prog == kProgStop) { out.print("ppm_server: stopping (served %ld calls, %ld resident hits, %ld uploads)\n", c.served, c.hits, c.misses); leave = true; }
+    else if (rq.prog == kProgStats) {
+        out.print("ppm_server: device %d, served %ld calls, %ld resident hits, %ld uploads, %.2f of %.0f GB cached\n", c.dev, c.served, c.hits, c.misses, c.used / 1e9, c.budget / 1e9);
+        for (const auto &e : c.stacks) out.print("  stack inode %llu: particles %ld..%ld, box %d, %.2f GB\n", e.id.ino, e.first, e.first + e.count - 1, e.box, e.bytes / 1e9);
+        for (const auto &e : c.refs) out.print("  reference inode %llu: box %d, padding %d\n", e.id.ino, e.box, e.pad);
+    } else if (!recon && rq.prog != kProgRefine) { rp.status = 1; out.print("ERROR: ppm_server: unknown request %u\n", rq.prog); }
+    else if (rq.build != build_id()) { rp.status = kMismatch; out.print("ppm_server: this server is build %s, the client %s\n", build_id().c_str(), rq.build.c_str()); }
+    else {
+        const auto t0 = Clock::now();
+        if (chdir(rq.cwd.c_str()) != 0) { rp.status = 1; out.print("ERROR: ppm_server: cannot enter %s\n", rq.cwd.c_str()); }
+        else {
+            const int lockfd = gpu_lock(c.dev);             // one-shot processes of the node wait their turn on the same lock
+            try {
+                // the context comes up under the server's own settings (PPM_SYNC), before the first caller's are applied
+                if (!c.inited) { if (ppm_init(c.dev) != 0) throw Fail{ ppm_last_error() }; c.inited = true; }
+                RequestSettings as_the_client(rq.settings);     // the caller's umask and PPM_* settings, for this request only
+                rp.status = recon ? serve_reconstruct3d(c, rq.input, out) : serve_refine3d(c, rq.input, out);
+            } catch (const Fail &f) {
+                rp.status = 1;
+                out.print("%s\n", error_line(f.msg).c_str());
+            } catch (const std::exception &e) {             // out of host memory, a bad table ...: the call fails, the server stays
+                rp.status = 1;
+                out.print("ERROR: ppm_server: %s\n", e.what());
+            }
+            gpu_unlock(lockfd);
+        }
+        c.served++;
+        printf("ppm_server: %s in %s -> status %d, %.2f s\n", recon ? "reconstruct3d" : "refine3d", rq.cwd.c_str(), rp.status, since(t0));
+        fflush(stdout);
+    }
+    if (rp.status == kHandOver) { rp.text.clear(); c.release_device(); }      // the client runs the call in a child process of its own, on this GPU: it gets the memory
+    return rp;
 }
 
 }  // namespace dropin
