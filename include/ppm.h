@@ -592,7 +592,9 @@ int ppm_fit_volume(const void *vol, int on_device, int n_in, double pixel_in, do
  * (src/pyp/extract/core.py:447-506) and normalize_image / extract_background / fix_empty_particles_in_place
  * (src/pyp/analysis/image.py:320-340, :406-417, :461-471).
  * image: rows x cols floats (row-major); coords: m x 2 doubles {box[0] (column coordinate), box[1] (row coordinate)}
- * in unbinned pixels; out: m * box * box floats. */
+ * in unbinned pixels; out: m * box * box floats.  Refused with -22 before anything is enqueued: a coordinate that is not finite
+ * or whose floor(coordinate / coordinate_binning) leaves no room for the box in an int (the message names its index), and a
+ * radius_px that is negative or not a number.  The rules are written out in DESIGN.md section 8a. */
 int ppm_extract_boxes(const void *image, int image_on_device, int rows, int cols, const double *coords, int m,
                       int box, double coordinate_binning, double radius_px, int normalize, int fix_empty,
                       void *out, int out_on_device);

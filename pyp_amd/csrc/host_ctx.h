@@ -484,6 +484,14 @@ int ppm_extract_boxes(const void *image, int image_on_device, int rows, int cols
     if (!g.inited) return fail(-1, "ppm_init has not been called");
     if (!image || !coords || !out) return fail(-22, "null argument");
     if (rows <= 0 || cols <= 0 || box < 2 || box > 4096 || !(coordinate_binning > 0)) return fail(-22, "bad extraction geometry");
+    if (!(radius_px >= 0)) return fail(-22, "ppm_extract_boxes: radius_px is negative or not a number");
+    // the kernel turns floor(coordinate / binning) into an int and adds the box to it: refuse what does not fit, before anything is enqueued
+    for (int i = 0; i < m; i++)
+        for (int a = 0; a < 2; a++) {
+            const double f = floor(coords[2 * i + a] / coordinate_binning);
+            if (!std::isfinite(coords[2 * i + a]) || !(fabs(f) <= 2147483647.0 - 2.0 * box))
+                return fail(-22, "ppm_extract_boxes: coordinate " + std::to_string(i) + (a ? " (y)" : " (x)") + " is not finite or too large");
+        }
     if (m <= 0) return 0;
     if (radius_px > box / 2.0) radius_px = box / 2.0;        // "Particle radius falls outside box" (image.py:323-331)
     float *d_img = nullptr, *d_out = nullptr;

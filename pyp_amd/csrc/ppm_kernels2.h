@@ -1021,10 +1021,20 @@ __device__ __forceinline__ unsigned hash32(unsigned x) { x ^= x >> 16; x *= 0x7f
 
 // Block = one particle.  Window bounds exactly as the reference computes them (including its habit of dropping
 // the last row / column when the window touches the far edge); pass 1 = mean of the inside part, pass 2 =
-// emptiness probes + background statistics, pass 3 = write.  The micrograph window is re-read from L2 / Infinity Cache.
+// majority vote + min / max + background statistics, (a counting pass where the vote leaves the question open), pass 3 =
+// write.  The micrograph window is re-read from L2 / Infinity Cache.
+//
+// Emptiness is the reference's rule: min == max, or fewer than 1 % of the pixels differ from the median, that is, one value
+// holds more than 99 % of the window (the median of a window is that value as soon as it holds more than half).  A
+// Boyer-Moore vote finds the only value that can: every thread votes over its own pixels, and (candidate, count) pairs
+// merge across lanes and waves (equal candidates add, different ones cancel).  The vote pairs off 2 k pixels of different
+// values and leaves `count` copies of the candidate, so a value with d pixels against it survives with count >= npx - 2 d:
+// count < npx - 2 (0.01 npx) settles "not empty" without another pass (any window of noise), otherwise the candidate is counted.
 __global__ void __launch_bounds__(256) k_extract(ExtractP P) {
     __shared__ double red[4][5];
     __shared__ double s_fill, s_mu, s_sd;
+    __shared__ float s_cand[4];
+    __shared__ int s_votes[4];
     __shared__ int s_empty;
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, box = P.box;
     const double bx = P.coords[2 * p], by = P.coords[2 * p + 1];
@@ -1069,9 +1079,8 @@ __global__ void __launch_bounds__(256) k_extract(ExtractP P) {
     if (tid == 0) s_fill = has_inside ? (red[0][0] + red[1][0] + red[2][0] + red[3][0]) / ((double)nX * nY) : 0.0;
     __syncthreads();
     const float fill = (float)s_fill;
-    // ---- pass 2: emptiness probes (three candidate "constant" values, min/max) together with the background statistics
-    // (outside radius_px of the box centre) of the window as it is; an "empty" window (rare) is replaced by noise and its
-    // statistics are taken again.
+    // ---- pass 2: majority vote and min / max together with the background statistics (outside radius_px of the box
+    // centre) of the window as it is; an "empty" window (rare) is replaced by noise and its statistics are taken again.
     const int npx = box * box;
     double b1 = 0, b2 = 0, bc = 0;
     auto stat_use = [&](int r, int c, float vf) {
@@ -1079,23 +1088,39 @@ __global__ void __launch_bounds__(256) k_extract(ExtractP P) {
         if ((float)(dr * dr + dc * dc) > P.radius2) { const double v = vf; b1 += v; b2 += v * v; bc += 1; }
     };
     if (P.fix_empty) {
-        const float c0 = raw_at(0, 0, fill), c1 = raw_at(box / 2, box / 2, fill), c2 = fill;
-        double n0 = 0, n1 = 0, n2 = 0; float mn = 3e38f, mx = -3e38f;
+        float cand = 0.f, mn = 3e38f, mx = -3e38f; int votes = 0;
+        auto merge = [](float &c, int &n, float oc, int on) {       // (candidate, count) pairs: equal candidates add, others cancel
+            if (oc == c) n += on; else if (on > n) { c = oc; n = on - n; } else n -= on;
+        };
         sweep(box, box, [&](int r, int c) { return raw_at(r, c, fill); }, [&](int r, int c, float v) {
-            n0 += v == c0; n1 += v == c1; n2 += v == c2; mn = fminf(mn, v); mx = fmaxf(mx, v);
+            if (votes == 0) { cand = v; votes = 1; } else votes += v == cand ? 1 : -1;
+            mn = fminf(mn, v); mx = fmaxf(mx, v);
             if (P.normalize) stat_use(r, c, v);
         });
-        for (int m = 32; m >= 1; m >>= 1) { mn = fminf(mn, __shfl_xor(mn, m, 64)); mx = fmaxf(mx, __shfl_xor(mx, m, 64)); }
-        __syncthreads();
-        block_sum(n0, 0); block_sum(n1, 1); block_sum(n2, 2); block_sum((double)mn, 3); block_sum((double)mx, 4);
-        __syncthreads();
-        if (tid == 0) {
-            double t0 = 0, t1 = 0, t2 = 0, gmn = 3e38, gmx = -3e38;
-            for (int w = 0; w < 4; w++) { t0 += red[w][0]; t1 += red[w][1]; t2 += red[w][2]; gmn = fmin(gmn, red[w][3]); gmx = fmax(gmx, red[w][4]); }
-            double most = fmax(t0, fmax(t1, t2));
-            s_empty = (gmn == gmx) || ((double)npx - most < 0.01 * npx);
+        for (int m = 32; m >= 1; m >>= 1) {
+            mn = fminf(mn, __shfl_xor(mn, m, 64)); mx = fmaxf(mx, __shfl_xor(mx, m, 64));
+            const float oc = __shfl_xor(cand, m, 64); const int on = __shfl_xor(votes, m, 64);
+            merge(cand, votes, oc, on);
         }
         __syncthreads();
+        if (lane == 0) { red[wave][3] = mn; red[wave][4] = mx; s_cand[wave] = cand; s_votes[wave] = votes; }
+        __syncthreads();
+        const double few = 0.01 * npx;                             // "fewer than 1 % differ": d < few
+        if (tid == 0) {
+            double gmn = 3e38, gmx = -3e38; float c = s_cand[0]; int n = s_votes[0];
+            for (int w = 0; w < 4; w++) { gmn = fmin(gmn, red[w][3]); gmx = fmax(gmx, red[w][4]); if (w) merge(c, n, s_cand[w], s_votes[w]); }
+            s_cand[0] = c;
+            s_empty = gmn == gmx ? 1 : (double)n < (double)npx - 2.0 * few ? 0 : -1;       // -1: the candidate has to be counted
+        }
+        __syncthreads();
+        if (s_empty < 0) {                                         // the same for the whole block
+            const float c = s_cand[0]; double same = 0;
+            sweep(box, box, [&](int r, int c2) { return raw_at(r, c2, fill); }, [&](int, int, float v) { same += v == c; });
+            block_sum(same, 3);
+            __syncthreads();
+            if (tid == 0) s_empty = (double)npx - (red[0][3] + red[1][3] + red[2][3] + red[3][3]) < few;
+            __syncthreads();
+        }
     } else {
         if (tid == 0) s_empty = 0;
         if (P.normalize) sweep(box, box, [&](int r, int c) { return raw_at(r, c, fill); }, stat_use);

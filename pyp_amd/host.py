@@ -307,7 +307,8 @@ def extract_boxes(micrograph, coords, box, radius_A, pixel_size, coordinate_binn
                   out=None, device=0):
     """Crop + normalise particle boxes (src/pyp/extract/core.py:447-506 with src/pyp/analysis/image.py:406-417).
     micrograph: 2-D float32 numpy array or CUDA tensor; coords: (M, 2) of (box[0], box[1]) = (column, row) coordinates;
-    out: optional CUDA tensor (M, box, box) to fill in place (resident stack).  Returns the stack."""
+    out: optional CUDA tensor (M, box, box) to fill in place (resident stack).  Returns the stack.  The rules are DESIGN.md section 8a;
+    coordinates that are not finite or do not fit an int with the box to spare, and a negative or NaN radius, raise PpmError."""
     lib.init(device)
     coords = np.ascontiguousarray(coords, dtype=np.float64).reshape(-1, 2)
     m = len(coords)
