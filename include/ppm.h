@@ -585,6 +585,77 @@ typedef struct ppm_fit_info {
 int ppm_fit_plan(int n_in, double pixel_in, double pixel_out, int box_out, ppm_fit_info *out);
 int ppm_fit_volume(const void *vol, int on_device, int n_in, double pixel_in, double pixel_out, int box_out, void *out, ppm_fit_info *info);
 
+/* The averaged periodogram of a micrograph or a movie: the spectrum stage of cistem2's `ctffind`, which PYP runs per micrograph, per
+ * tilt and per particle (src/pyp/ctf/core.py:130-468, :471-600, :715-787).  DESIGN.md section 2g defines it; it is pinned to the
+ * reference's own plain-numpy `periodogram_averaging` (ctf/core.py:1216-1337, power 2, binning 1):
+ *   tiles     T x T, origins 0, T/2, 2 T/2, ... along each axis (n / (T/2) of them, integer division), an origin whose tile would leave
+ *             the image pulled back to n - T; where T/2 divides n the last tile therefore repeats the one before it and counts twice,
+ *             as it does there.  The image need not be square; an axis shorter than T is refused.
+ *   movie     nframes > 1: frames are averaged in groups of `group` (in order; the last group holds what is left) and every group's
+ *             mean image is tiled; the average runs over the tiles of all groups.
+ *   power     |rfft2(tile)|^2 (unnormalised transform), averaged over the tiles: T rows (ky = 0 .. T-1 in transform order) of T/2 + 1
+ *             values (kx = 0 .. T/2), floats, kx fastest.
+ *   normalise != 0: the reference's own scaling - element [0, 0] set to 0, then everything divided by the maximum (an image whose
+ *             tiles are all constant gives 0 / 0 there and here).
+ *   order     tiles are summed in walk order (group, tile row, tile column) in chunks of 16, the chunks' partial sums in order: the
+ *             order depends on the sizes alone, no floating-point atomics, two calls agree bit for bit.
+ * T must be a size the transforms take (even, 32..512, prime factors 2, 3, 5, 7); the refusal names the nearest such sizes.  The handle
+ * owns the workspaces, sized by the plan before the first launch (ppm_ctf_spectrum_plan reports them; it needs no device and no
+ * initialised library); a workspace that cannot be had refuses the call.  on_device != 0: img is a device pointer; out_on_device
+ * likewise for out_power, which may be NULL: the result also stays in the handle, where ppm_ctf_last_power finds it (a device pointer,
+ * valid until the handle's next call), so that a later stage can read it without a trip through the host.  Refusals return -22 and
+ * write nothing. */
+typedef struct ppm_ctf ppm_ctf_t;
+typedef struct ppm_ctf_spectrum_info {
+    int tile, half_w, tiles_x, tiles_y, groups, vec;       /* vec: the sizes allow 16-byte loads (the image's address must too) */
+    long tiles, chunks, pass_tiles;                        /* tiles averaged, partial sums, tiles per trip through the two passes */
+    long half_bytes, part_bytes, out_floats;               /* the two workspaces and the size of the result */
+} ppm_ctf_spectrum_info;
+ppm_ctf_t *ppm_ctf_create(void);
+void ppm_ctf_destroy(ppm_ctf_t *h);
+int ppm_ctf_spectrum_plan(int nx, int ny, int nframes, int group, int tile, ppm_ctf_spectrum_info *out);
+int ppm_ctf_spectrum(ppm_ctf_t *h, const void *img, int on_device, int nx, int ny, int nframes, int group, int tile, int normalise,
+                     void *out_power, int out_on_device);
+const void *ppm_ctf_last_power(ppm_ctf_t *h);
+
+/* Defocus and astigmatism from power spectra: the estimator of DESIGN.md section 2g (build-defined: the program it stands in for is
+ * absent; tests/f64_ctf.py is its executable form).  Per spectrum [T][T/2 + 1] as ppm_ctf_spectrum leaves it (normalised or not: the
+ * score does not see the scale):
+ *   crop      a pixel below 1.4 A: the spectrum is centre-cropped in Fourier space to B = 2 floor(T pixel / 1.4 / 2), a = pixel T / B;
+ *             else B = T, a = pixel
+ *   condition A = sqrt(P); mean of A over integer rings r = floor(|k| + 1/2) <= B/2 of the half plane; background = that profile
+ *             box-averaged over +- ceil(B a / min_res) rings (ring 0, the image's mean, left out); samples = half-plane pixels with min_res >= 1/s >= max_res inside ring
+ *             B/2, kx = 0 with ky < 0 dropped; v = A - background(ring) - mean over the samples (sums in double)
+ *   score     sum v |c| / sqrt(sum v^2 sum c^2) - (D / tol)^2 / (2 n) (the last term with tol > 0 only), c the CTF of ppm_refine_batch
+ *             (same wavelength, Cs and amplitude-contrast phase) at mean defocus d, astigmatism D = df1 - df2 >= 0 and angle t
+ *   grid      d = lo, lo + step, ... <= hi; D = 0, step, ... up to tol (or 1000 A without a restraint); 12 angles of 15 degrees for
+ *             every D > 0; candidate index = i_d (1 + 12 n_D) + c, c = 0 for D = 0, else 1 + 12 (j_D - 1) + k_t; ties to the lowest index
+ *   search    from the grid winner: steps (step, step, 15 degrees); per level at most 8 sweeps over the six neighbours (D kept >= 0, t
+ *             fixed while D = 0), a move only to a strictly better score (ties to the first neighbour in the order +d -d +D -D +t -t);
+ *             the steps are halved 10 times
+ * out_rows: n x 8 doubles {df1 >= df2, angle in (-90, 90] degrees, score, grid winner's index, its score, samples fitted, fit resolution
+ * in A}.  avrot (host, may be NULL): n x 6 x (B/2 + 1) doubles, per ring r: frequency r / (B a) in 1/A; rotational average of A -
+ * background; the same averaged along equiphase lines (a pixel counts for ring floor(|k| sqrt(df(phi) / d) + 1/2)); the fitted 1-D |CTF|
+ * at mean defocus; quality = correlation of the last two over the rings r +- ceil(B a / min_res) inside 1 .. B/2; noise level = 1 /
+ * sqrt(pixels of that window).  The fit resolution is 1 / s of the first ring beyond min_res whose quality is below 0.5 (of the last
+ * ring when none is).  diag (host, may be NULL): n x B x B floats, centred: the conditioned spectrum where kx >= 0, the fitted |CTF|
+ * (with astigmatism) where kx < 0.  All of it in double on the device (k_ctf_profile).  def_lo / def_hi (host, both or neither): a window [lo, hi] per spectrum in place of cfg's; when all are the
+ * same a block scores one |c| against four spectra, which changes no spectrum's bits.  grid_scores (host, may be NULL): the whole
+ * score map, grid_ld floats per spectrum (a debug output; NaN past the candidates of a spectrum whose window is shorter than the longest).  spectra: n spectra one after the other; on_device != 0: a device pointer
+ * (ppm_ctf_last_power's, for one).  ppm_ctf_estimate runs both stages on one image without a trip through the host.  No floating-point
+ * atomics: a spectrum's result is bit-identical whatever the batch around it.  Refusals return -22 and write nothing. */
+typedef struct ppm_ctf_cfg { double pixel, kv, cs, wgh, min_res, max_res, min_def, max_def, step, tol; } ppm_ctf_cfg;
+typedef struct ppm_ctf_fit_info {
+    int tile, B, k2lo, k2hi, bg_w, nj, nc;       /* B_fit; samples have k2lo <= |k|^2 <= k2hi; background half width; D steps; candidates per d */
+    double a;                                    /* a_fit */
+    long ni, candidates, samples;                /* d steps of cfg's range, ni * nc, samples fitted */
+} ppm_ctf_fit_info;
+int ppm_ctf_fit_plan(int tile, const ppm_ctf_cfg *cfg, ppm_ctf_fit_info *out);
+int ppm_ctf_fit(ppm_ctf_t *h, const void *spectra, int on_device, int n, int tile, const ppm_ctf_cfg *cfg, const double *def_lo,
+                const double *def_hi, double *out_rows, float *grid_scores, long grid_ld, double *avrot, float *diag);
+int ppm_ctf_estimate(ppm_ctf_t *h, const void *img, int on_device, int nx, int ny, int nframes, int group, int tile,
+                     const ppm_ctf_cfg *cfg, double *out_row, double *avrot, float *diag);
+
 /* Particle extraction straight into a (resident) stack — the step before the path:
  * crop `box` x `box` windows around the picked coordinates, fill what falls outside the micrograph with the mean
  * of the inside part, replace empty boxes by white noise, subtract the background mean and divide by the background

@@ -204,6 +204,40 @@ class FitInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CtfSpectrumInfo(C.Structure):
+    """ppm_ctf_spectrum_info (include/ppm.h): the plan of an averaged periodogram - tile T and T / 2 + 1, tiles along x and y, frame
+    groups, whether the sizes allow 16-byte loads, tiles averaged, partial sums, tiles per trip, the two workspaces in bytes and the
+    floats of the result."""
+    _fields_ = [("tile", C.c_int), ("half_w", C.c_int), ("tiles_x", C.c_int), ("tiles_y", C.c_int), ("groups", C.c_int), ("vec", C.c_int),
+                ("tiles", C.c_long), ("chunks", C.c_long), ("pass_tiles", C.c_long), ("half_bytes", C.c_long), ("part_bytes", C.c_long),
+                ("out_floats", C.c_long)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class CtfCfg(C.Structure):
+    """ppm_ctf_cfg (include/ppm.h): pixel size in A, voltage in kV, spherical aberration in mm, amplitude contrast, the resolutions between
+    which the spectrum is fitted, the range and step of the mean-defocus grid in A, the astigmatism restraint in A (0: none)."""
+    _fields_ = [("pixel", C.c_double), ("kv", C.c_double), ("cs", C.c_double), ("wgh", C.c_double), ("min_res", C.c_double),
+                ("max_res", C.c_double), ("min_def", C.c_double), ("max_def", C.c_double), ("step", C.c_double), ("tol", C.c_double)]
+
+    @classmethod
+    def make(cls, pixel, kv=300.0, cs=2.7, wgh=0.07, min_res=30.0, max_res=5.0, min_def=5000.0, max_def=50000.0, step=500.0, tol=0.0):
+        return cls(float(pixel), float(kv), float(cs), float(wgh), float(min_res), float(max_res), float(min_def), float(max_def),
+                   float(step), float(tol))
+
+
+class CtfFitInfo(C.Structure):
+    """ppm_ctf_fit_info (include/ppm.h): the plan of a fit - B_fit, the |k|^2 range of the fitted samples, the background's half width,
+    astigmatism steps, candidates per mean defocus, a_fit, mean-defocus steps, candidates and samples."""
+    _fields_ = [("tile", C.c_int), ("B", C.c_int), ("k2lo", C.c_int), ("k2hi", C.c_int), ("bg_w", C.c_int), ("nj", C.c_int), ("nc", C.c_int),
+                ("a", C.c_double), ("ni", C.c_long), ("candidates", C.c_long), ("samples", C.c_long)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class PostCfg(C.Structure):
     """ppm_post_cfg (include/ppm.h)."""
     MASK = {"none": 0, "external": 1, "auto": 2}

@@ -39,6 +39,8 @@
 #include "ppm_resample_plan.h"
 #include "ppm_resample_kernels.h"
 #include "ppm_rank.h"
+#include "ppm_ctf_plan.h"
+#include "ppm_ctf_kernels.h"
 
 using namespace ppm;
 
@@ -54,3 +56,4 @@ using namespace ppm;
 #include "host_post.h"
 #include "host_locres.h"
 #include "host_resample.h"
+#include "host_ctf.h"

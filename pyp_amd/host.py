@@ -538,6 +538,198 @@ def fit_reference(vol, pixel_in, pixel_out, box, out=None, device=0):
     return res, info
 
 
+def periodogram_plan(shape, tile, group=1):
+    """The plan of periodogram() (ppm_ctf_spectrum_plan; no device needed): abi.CtfSpectrumInfo.  shape: (ny, nx) of an image or
+    (nframes, ny, nx) of a movie.  A refusal raises lib.PpmError."""
+    from .abi import CtfSpectrumInfo
+    shape = tuple(int(s) for s in shape)
+    if len(shape) not in (2, 3):
+        raise ValueError(f"ERROR: periodogram: expected an image [ny, nx] or a movie [nframes, ny, nx], got shape {shape}")
+    nf, ny, nx = ((1,) + shape)[-3:]
+    info = CtfSpectrumInfo()
+    lib.check(lib.load().ppm_ctf_spectrum_plan(nx, ny, nf, int(group), int(tile), C.byref(info)))
+    return info
+
+
+class CtfEstimator:
+    """Handle of the CTF estimation stages (ppm_ctf_create): owns their device workspaces, which are grown on demand, reused across
+    calls and freed with the handle."""
+
+    def __init__(self, device=0):
+        lib.init(device)
+        self.h = lib.load().ppm_ctf_create()
+        if not self.h:
+            raise lib.PpmError(lib.last_error())
+
+    def periodogram(self, image, tile, normalise=True, group=1, out=None):
+        """See host.periodogram."""
+        on_dev = bool(getattr(image, "is_cuda", False))
+        if not on_dev:
+            image = np.ascontiguousarray(image.numpy() if hasattr(image, "numpy") else image, dtype=np.float32)
+        elif str(image.dtype) != "torch.float32" or not image.is_contiguous():
+            raise ValueError("ERROR: periodogram: a device image must be contiguous float32")
+        info = periodogram_plan(image.shape, tile, group)
+        nf, ny, nx = ((1,) + tuple(int(s) for s in image.shape))[-3:]
+        oshape = (info.tile, info.half_w)
+        if on_dev:
+            import torch
+            res = torch.empty(oshape, dtype=torch.float32, device=image.device) if out is None else out
+            if tuple(res.shape) != oshape or str(res.dtype) != "torch.float32" or not res.is_contiguous() or not res.is_cuda:
+                raise ValueError(f"ERROR: periodogram: out must be a contiguous float32 device tensor of shape {oshape}")
+            for t in (image, res):
+                if not getattr(t, "ready", False):
+                    _sync_producer(t)
+            pi, po = C.c_void_p(image.data_ptr()), C.c_void_p(res.data_ptr())
+        else:
+            res = np.empty(oshape, dtype=np.float32) if out is None else out
+            if not isinstance(res, np.ndarray) or res.dtype != np.float32 or res.shape != oshape or not res.flags.c_contiguous:
+                raise ValueError(f"ERROR: periodogram: out must be a contiguous float32 array of shape {oshape}")
+            pi, po = lib.ptr(image), lib.ptr(res)
+        lib.check(lib.load().ppm_ctf_spectrum(self.h, pi, 1 if on_dev else 0, nx, ny, nf, int(group), int(tile), 1 if normalise else 0,
+                                              po, 1 if on_dev else 0))
+        return res
+
+    def fit(self, spectra, cfg, windows=None, grid_scores=False, profile=False):
+        """See host.estimate_ctf (the spectra form)."""
+        on_dev = bool(getattr(spectra, "is_cuda", False))
+        if not on_dev:
+            spectra = np.ascontiguousarray(spectra.numpy() if hasattr(spectra, "numpy") else spectra, dtype=np.float32)
+        elif str(spectra.dtype) != "torch.float32" or not spectra.is_contiguous():
+            raise ValueError("ERROR: estimate_ctf: device spectra must be contiguous float32")
+        shape = tuple(int(s) for s in spectra.shape)
+        if len(shape) == 2:
+            shape = (1,) + shape
+        if len(shape) != 3 or shape[2] != shape[1] // 2 + 1:
+            raise ValueError(f"ERROR: estimate_ctf: spectra must be [T, T / 2 + 1] or [n, T, T / 2 + 1], got shape {shape}")
+        n, tile = shape[0], shape[1]
+        info = fit_ctf_plan(tile, cfg)
+        lo = hi = None
+        ni_max = info.ni
+        if windows is not None:
+            w = np.ascontiguousarray(windows, dtype=np.float64).reshape(n, 2)
+            lo, hi = np.ascontiguousarray(w[:, 0]), np.ascontiguousarray(w[:, 1])
+            ni_max = int(np.floor((hi - lo) / cfg.step + 1e-9).max()) + 1 if (hi >= lo).all() else 1
+        rows = np.zeros((n, 8), dtype=np.float64)
+        scores = np.full((n, max(1, ni_max) * info.nc), np.nan, dtype=np.float32) if grid_scores else None
+        if on_dev and not getattr(spectra, "ready", False):
+            _sync_producer(spectra)
+        ps = C.c_void_p(spectra.data_ptr()) if on_dev else lib.ptr(spectra)
+        avrot = np.zeros((n, 6, info.B // 2 + 1), dtype=np.float64) if profile else None
+        diag = np.zeros((n, info.B, info.B), dtype=np.float32) if profile else None
+        lib.check(lib.load().ppm_ctf_fit(self.h, ps, 1 if on_dev else 0, n, tile, C.byref(cfg), None if lo is None else lib.ptr(lo),
+                                         None if hi is None else lib.ptr(hi), lib.ptr(rows), None if scores is None else lib.ptr(scores),
+                                         0 if scores is None else scores.shape[1], None if avrot is None else lib.ptr(avrot),
+                                         None if diag is None else lib.ptr(diag)))
+        out = (rows,) + ((scores,) if grid_scores else ()) + ((avrot, diag) if profile else ())
+        return out if len(out) > 1 else rows
+
+    def estimate(self, image, tile, cfg, group=1, profile=False):
+        """See host.estimate_ctf (the image form)."""
+        on_dev = bool(getattr(image, "is_cuda", False))
+        if not on_dev:
+            image = np.ascontiguousarray(image.numpy() if hasattr(image, "numpy") else image, dtype=np.float32)
+        elif str(image.dtype) != "torch.float32" or not image.is_contiguous():
+            raise ValueError("ERROR: estimate_ctf: a device image must be contiguous float32")
+        periodogram_plan(image.shape, tile, group)
+        nf, ny, nx = ((1,) + tuple(int(s) for s in image.shape))[-3:]
+        if on_dev and not getattr(image, "ready", False):
+            _sync_producer(image)
+        row = np.zeros((1, 8), dtype=np.float64)
+        info = fit_ctf_plan(tile, cfg)
+        avrot = np.zeros((1, 6, info.B // 2 + 1), dtype=np.float64) if profile else None
+        diag = np.zeros((1, info.B, info.B), dtype=np.float32) if profile else None
+        lib.check(lib.load().ppm_ctf_estimate(self.h, C.c_void_p(image.data_ptr()) if on_dev else lib.ptr(image), 1 if on_dev else 0, nx, ny, nf,
+                                              int(group), int(tile), C.byref(cfg), lib.ptr(row), None if avrot is None else lib.ptr(avrot),
+                                              None if diag is None else lib.ptr(diag)))
+        return (row, avrot, diag) if profile else row
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib.load().ppm_ctf_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_ctf_estimators = {}
+
+
+def periodogram(image, tile, normalise=True, group=1, out=None, device=0):
+    """Averaged periodogram of a micrograph [ny, nx] or a movie [nframes, ny, nx] (ppm_ctf_spectrum; the spectrum stage of
+    ctffind): |rfft2|^2 of tile x tile windows at stride tile / 2, the last row and column pulled back inside, averaged.  A movie's frames
+    are averaged in groups of `group` first.  normalise=True applies the reference's own scaling ([0, 0] = 0, divide by the maximum);
+    the result is then what its periodogram_averaging(image, tile, power=2) returns.  numpy array or CUDA torch tensor in, the same kind
+    out, float32 [tile, tile // 2 + 1].  The tile must be a size the transforms take; a refusal raises lib.PpmError and leaves `out`
+    as it was.  The workspaces belong to one CtfEstimator per device, kept for the life of the process."""
+    return _ctf_estimator(device).periodogram(image, tile, normalise=normalise, group=group, out=out)
+
+
+CTF_ROW = ("df1", "df2", "angle", "score", "grid_index", "grid_score", "samples", "fit_resolution")
+
+
+def fit_ctf_plan(tile, cfg):
+    """The plan of a fit (ppm_ctf_fit_plan; no device needed): abi.CtfFitInfo.  A refusal raises lib.PpmError."""
+    from .abi import CtfFitInfo
+    info = CtfFitInfo()
+    lib.check(lib.load().ppm_ctf_fit_plan(int(tile), C.byref(cfg), C.byref(info)))
+    return info
+
+
+def _ctf_estimator(device):
+    est = _ctf_estimators.get(device)
+    if est is None:
+        est = _ctf_estimators[device] = CtfEstimator(device)
+    return est
+
+
+def estimate_ctf(image_or_spectra, cfg, tile=None, group=1, windows=None, grid_scores=False, profile=False, device=0):
+    """Defocus and astigmatism on the GPU (ppm_ctf_fit / ppm_ctf_estimate; the work of ctffind).  cfg: abi.CtfCfg.
+    With tile=T the first argument is a micrograph [ny, nx] or a movie [nframes, ny, nx] (frames averaged in groups of `group`): its
+    averaged periodogram is fitted without leaving the device.  With tile=None it is one spectrum [T, T / 2 + 1] or a batch
+    [n, T, T / 2 + 1] as periodogram() returns them (numpy or CUDA tensor); windows [n, 2] then gives every spectrum its own
+    [min_def, max_def].  Returns float64 rows [n, 8], columns host.CTF_ROW; with grid_scores=True also the float32 score map
+    [n, candidates] of the grid search (NaN where a spectrum's window has fewer candidates); with profile=True also the six avrot rows
+    float64 [n, 6, B / 2 + 1] (frequency in 1/A, rotational average, average along equiphase lines, fit, quality, noise level) and the
+    diagnostic images float32 [n, B, B] (include/ppm.h)."""
+    est = _ctf_estimator(device)
+    if tile is not None:
+        if windows is not None or grid_scores:
+            raise ValueError("ERROR: estimate_ctf: windows and grid_scores go with spectra, not with an image")
+        return est.estimate(image_or_spectra, tile, cfg, group=group, profile=profile)
+    return est.fit(image_or_spectra, cfg, windows=windows, grid_scores=grid_scores, profile=profile)
+
+
+def local_ctf(stack, weights, cfg, meandef, tolerance=500.0, device=0, return_spectra=False):
+    """Per-particle defocus of one micrograph's particles (what the reference's ctffind_spr_local_estimate does with one process per
+    particle): the one-tile periodogram of every particle of stack [P, B, B], mixed on the device as weights @ spectra with the caller's
+    [P, P] weight matrix (the reference's distance weights), every mix fitted in one ppm_ctf_fit on meandef +- tolerance.  Returns the
+    float64 table [P, 4] the reference writes to <name>_ctf.txt: df1, df2, angle, score; with return_spectra=True also the mixed spectra
+    that were fitted (a CUDA tensor [P, B, B / 2 + 1])."""
+    import torch
+    est = _ctf_estimator(device)
+    on_dev = bool(getattr(stack, "is_cuda", False))
+    dev = stack.device if on_dev else torch.device("cuda", device)
+    st = stack if on_dev else torch.from_numpy(np.ascontiguousarray(stack, dtype=np.float32)).to(dev)
+    if st.dim() != 3 or st.shape[1] != st.shape[2]:
+        raise ValueError(f"ERROR: local_ctf: expected a stack [P, B, B], got shape {tuple(st.shape)}")
+    n, box = int(st.shape[0]), int(st.shape[1])
+    w = torch.as_tensor(np.asarray(weights, dtype=np.float32) if not hasattr(weights, "is_cuda") else weights, dtype=torch.float32, device=dev)
+    if tuple(w.shape) != (n, n):
+        raise ValueError(f"ERROR: local_ctf: weights must be [{n}, {n}]")
+    spectra = torch.empty((n, box, box // 2 + 1), dtype=torch.float32, device=dev)
+    for i in range(n):
+        est.periodogram(st[i], box, normalise=False, out=spectra[i])
+    mixed = (w @ spectra.reshape(n, -1)).reshape(spectra.shape).contiguous()
+    md = np.broadcast_to(np.asarray(meandef, dtype=np.float64), (n,))
+    rows = est.fit(mixed, cfg, windows=np.stack([md - tolerance, md + tolerance], axis=1))
+    table = np.ascontiguousarray(rows[:, :4])
+    return (table, mixed) if return_spectra else table
+
+
 class PinnedBuffer:
     """Page-locked host memory as a float32 numpy array (ppm_host_alloc): staging for uploads that overlap compute."""
 

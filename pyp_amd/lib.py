@@ -18,6 +18,8 @@ EXPORTS = [
     "ppm_device_free", "ppm_device_upload", "ppm_device_sync", "ppm_extract_boxes", "ppm_host_alloc", "ppm_host_free", "ppm_host_read",
     "ppm_comm_unique_id", "ppm_comm_create", "ppm_comm_count", "ppm_comm_destroy", "ppm_accum_reduce", "ppm_sva_insert", "ppm_sva_align_average", "ppm_mask_volume",
     "ppm_create_mask", "ppm_postprocess", "ppm_local_resolution", "ppm_resample", "ppm_resize", "ppm_fit_plan", "ppm_fit_volume",
+    "ppm_ctf_create", "ppm_ctf_destroy", "ppm_ctf_spectrum_plan", "ppm_ctf_spectrum", "ppm_ctf_last_power",
+    "ppm_ctf_fit_plan", "ppm_ctf_fit", "ppm_ctf_estimate",
 ]
 
 
@@ -96,6 +98,14 @@ def load():
     L.ppm_resize.argtypes = [vp, ci, ci, cl, ci, ci, ci, vp, vp]; L.ppm_resize.restype = ci
     L.ppm_fit_plan.argtypes = [ci, C.c_double, C.c_double, ci, vp]; L.ppm_fit_plan.restype = ci
     L.ppm_fit_volume.argtypes = [vp, ci, ci, C.c_double, C.c_double, ci, vp, vp]; L.ppm_fit_volume.restype = ci
+    L.ppm_ctf_create.argtypes = []; L.ppm_ctf_create.restype = vp
+    L.ppm_ctf_destroy.argtypes = [vp]; L.ppm_ctf_destroy.restype = None
+    L.ppm_ctf_spectrum_plan.argtypes = [ci, ci, ci, ci, ci, vp]; L.ppm_ctf_spectrum_plan.restype = ci
+    L.ppm_ctf_spectrum.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, ci]; L.ppm_ctf_spectrum.restype = ci
+    L.ppm_ctf_last_power.argtypes = [vp]; L.ppm_ctf_last_power.restype = vp
+    L.ppm_ctf_fit_plan.argtypes = [ci, vp, vp]; L.ppm_ctf_fit_plan.restype = ci
+    L.ppm_ctf_fit.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, cl, vp, vp]; L.ppm_ctf_fit.restype = ci
+    L.ppm_ctf_estimate.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]; L.ppm_ctf_estimate.restype = ci
     _lib = L
     return L
 
